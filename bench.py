@@ -1,6 +1,14 @@
 """bench.py -- the headline benchmark of BASELINE.json on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--full]
+                    [--dump-outputs DIR]
+
+A plain run measures the headline alone: it sets up, runs W untimed (waited) steps, times K
+steps, writes the outputs of one more such step under --dump-outputs DIR (dump_outputs) and
+prints the result line.  Everything else described below -- `synchronous`, `roofline` and the
+per-kernel times, the `query` / `counts` / `reads` / `depth` legs, `large`, `host_boundary`, the
+CPU baselines, the sharded side records of N > 1, and the host readout, index-build and CPU
+records of configs 4 and 5 -- is measured by `--full`, which adds those records to the same line.
 
 metric: "Mbp/s indexed (make.kmer.hash k=31) at 1/2/4/8 GPUs; seq.kmer.pos query Mbp/s".
 A step is one make.kmer.hash build (kmhg_build_device: radix partition of the windows by hash
@@ -538,6 +546,15 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the synchronous steps, "
+                         "per-kernel times and rooflines, the query / counts / reads / depth "
+                         "legs, the out-of-cache and sharded side records, the host-boundary "
+                         "rates and the CPU baselines (the options below trim a --full run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what one more build of the same step "
+                         "computed (its kmer.pos readout) as DIR/<name>.npy (float64; a fixed "
+                         "seeded sample of the rows where the whole would exceed 64 MB)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--no-reads", action="store_true",
                     help="skip the read-counting / depth legs (count.kmers.fq.sh.rp)")
@@ -561,6 +578,10 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench: --steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.config in (4, 5) or args.only_large):
+        raise SystemExit("bench: --dump-outputs writes the index build's outputs (configs 2, 3)")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` without a launcher: start the N ranks here, before this
         # process touches the GPU (it never does: it only waits for its child)
@@ -638,31 +659,34 @@ def main():
             check_build(info)
         return info
 
+    full = args.full
     progress("build steps")
-    # ---------------- build: W untimed warmups, 2 steps with events around every kernel (find the
-    # dominant one), then exactly K timed steps with events around the dominant kernel only, so
-    # the per-kernel events add no dead time to the rest of the timed region
+    # ---------------- build: W untimed warmups, then exactly K timed steps.  --full first runs the
+    # same K steps with a wait after each and 2 steps with events around every kernel (find the
+    # dominant one), and keeps events around the dominant kernel only in the timed steps, so the
+    # per-kernel events add no dead time to the rest of the timed region
     for _ in range(args.warmup):
         info = build_step(wait=True)
-    # the same steps with a wait after each (the synchronous make.kmer.hash of the R API)
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        info = build_step(wait=True)
-    barrier()
-    t_sync = time.perf_counter() - t0
-    D.timing_enable(True)
-    D.timing_select(None)
-    D.timing_reset()
-    n_id = 2
-    for _ in range(n_id):
-        info = build_step(wait=True)
-    wt = D.timing_report()
-    all_kernels = {n: v[1] / v[0] for n, v in wt.items() if v[0]}
-    per_step = {n: v[1] / n_id for n, v in wt.items() if v[0]}
-    dom = max(per_step, key=per_step.get)
-    D.timing_select(dom)
-    D.timing_reset()
+    t_sync, n_id, wt, all_kernels, per_step, dom = 0.0, 2, {}, {}, {}, None
+    if full:
+        # the same steps with a wait after each (the synchronous make.kmer.hash of the R API)
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            info = build_step(wait=True)
+        barrier()
+        t_sync = time.perf_counter() - t0
+        D.timing_enable(True)
+        D.timing_select(None)
+        D.timing_reset()
+        for _ in range(n_id):
+            info = build_step(wait=True)
+        wt = D.timing_report()
+        all_kernels = {n: v[1] / v[0] for n, v in wt.items() if v[0]}
+        per_step = {n: v[1] / n_id for n, v in wt.items() if v[0]}
+        dom = max(per_step, key=per_step.get)
+        D.timing_select(dom)
+        D.timing_reset()
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -670,9 +694,24 @@ def main():
     barrier()
     t_build = time.perf_counter() - t0
     info = build_step(wait=True)                   # totals of one more (waited) build
-    ktimes = D.timing_report()
-    D.timing_enable(False)
-    D.timing_select(None)
+    ktimes = {}
+    if full:
+        ktimes = D.timing_report()
+        D.timing_enable(False)
+        D.timing_select(None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, seq, k, stream)
+    if not full:
+        # the plain run: the headline alone
+        tb = torch.tensor([t_build], dtype=torch.float64, device=dev)
+        if distributed:
+            dist.all_reduce(tb, op=dist.ReduceOp.MAX)
+        if rank == 0:
+            _emit(headline(args, cfg, info, tb.item(), world, distributed, seed - rank))
+        if distributed:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---------------- N > 1: the headline is the owner-computes build of ONE genome of N x L
     # bases: rank 0 holds it and broadcasts it, every rank builds the k-mers of
@@ -880,7 +919,6 @@ def main():
         Nw = L - k + 1
         U, N = info["n_kmers"], info["n_positions"]
         mbp_total = L * world / 1e6
-        value = mbp_total * args.steps / t_build
         qvalue = mbp_total * leg_steps / t_query
         # dominant build kernel (largest time per step in the warm-up) and its roofline from
         # the HIP events recorded around it in the timed steps
@@ -897,22 +935,8 @@ def main():
         step_ms = t_build / args.steps * 1e3
         launches = {n: v[0] / n_id for n, v in wt.items() if v[0]}
         B = survey_bytes("build", L=L, U=U, N=N)
-        out = {
-            "metric": "Mbp/s indexed (make.kmer.hash k=31) at 1/2/4/8 GPUs; "
-                      "seq.kmer.pos query Mbp/s",
-            "value": round(value, 2),
-            "unit": "Mbp/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(t_build / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u64",
-            "data": "synthetic",
-            "config": {"workload": cfg["workload"], "seq_len": L, "k": k,
-                       "distinct_kmers": U, "positions": N, "parallelism": f"replicas{world}"},
+        out = headline(args, cfg, info, t_build, world, distributed, seed - rank)
+        out.update({
             "roofline": roofline(B, dom, dom_ms, step_ms, pmc,
                                  algorithmic_bytes(dom, L, Nw, U, N), launches,
                                  device_ms=sum(per_step.values())),
@@ -947,7 +971,7 @@ def main():
             "kernels_ms": {n: round(v, 5) for n, v in per.items()},
             "kernel_ms_per_step": round(sum(tot.values()), 5),
             "teardown_ms": round(t_free * 1e3, 4),
-        }
+        })
         if t_count:
             out["counts"] = {
                 "value": round(mbp_total * leg_steps / t_count, 2), "unit": "Mbp/s",
@@ -997,20 +1021,6 @@ def main():
             if "k_depth_probe" in dper:
                 out["depth"]["roofline"] = _leg_roofline(
                     dper, "k_depth_probe", depth_algorithmic_bytes("k_depth_probe", L, 2))
-        out["build_path"] = {"build": info["build"], "fallback": info["fallback"],
-                             "note": "kmhg_info of the waited builds: 2 = partitioned, lane-order "
-                                     "ranks; 3 = ballot ranks (the device failed the LDS "
-                                     "lane-order self-check); 1 = global-atomic; fallback = 1 "
-                                     "would mean a rebuild (the run fails instead)"}
-        out["config"]["parallelism"] = "single" if world == 1 and not distributed \
-            else f"replicas{world}"
-        if distributed:
-            out["config"]["workload"] = (
-                f"configs[{args.config - 1}] sharded by sequence: every rank indexes its own "
-                f"synthetic {L / 1e6:.0f} Mbp iid ACGT sequence (splitmix64 seed "
-                f"{seed - rank} + rank), k={k}, make.kmer.hash; n_gpus independent indices, no "
-                "data-path collective (weak scaling); the owner-computes build of ONE "
-                "n_gpus x L sequence is the sharded_build record")
         if sharded:
             # the owner-computes build of one genome as a side record: its part
             # step, and the rate at which the parts become an index every rank can query
@@ -1039,6 +1049,91 @@ def main():
     if distributed:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def headline(args, cfg, info: dict, t_build: float, world: int, distributed: bool,
+             seed0: int) -> dict:
+    """The result line of the timed build steps alone (what a plain run prints; --full adds its
+    records to it): t_build is the K asynchronous steps' wall time, max over the ranks."""
+    L, k = cfg["L"], cfg["k"]
+    out = {
+        "metric": "Mbp/s indexed (make.kmer.hash k=31) at 1/2/4/8 GPUs; "
+                  "seq.kmer.pos query Mbp/s",
+        "value": round(L * world / 1e6 * args.steps / t_build, 2),
+        "unit": "Mbp/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(t_build / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u64",
+        "data": "synthetic",
+        "config": {"workload": cfg["workload"], "seq_len": L, "k": k,
+                   "distinct_kmers": info["n_kmers"], "positions": info["n_positions"],
+                   "parallelism": "single" if world == 1 and not distributed
+                   else f"replicas{world}"},
+        "build_path": {"build": info["build"], "fallback": info["fallback"],
+                       "note": "kmhg_info of the waited builds: 2 = partitioned, lane-order "
+                               "ranks; 3 = ballot ranks (the device failed the LDS "
+                               "lane-order self-check); 1 = global-atomic; fallback = 1 "
+                               "would mean a rebuild (the run fails instead)"},
+        "full": bool(args.full),
+    }
+    if distributed:
+        out["config"]["workload"] = (
+            f"configs[{args.config - 1}] sharded by sequence: every rank indexes its own "
+            f"synthetic {L / 1e6:.0f} Mbp iid ACGT sequence (splitmix64 seed "
+            f"{seed0} + rank), k={k}, make.kmer.hash; n_gpus independent indices, no "
+            "data-path collective (weak scaling); the owner-computes build of ONE "
+            "n_gpus x L sequence is the sharded_build record")
+    return out
+
+
+DUMP_MAX_BYTES = 64 << 20    # --dump-outputs: the .npy files together stay below this
+DUMP_SEED = 20240531         # ... and a larger output is sampled by rows drawn from this seed
+
+
+def dump_sample(n_rows: int, row_bytes: int, budget: int, seed: int = DUMP_SEED):
+    """The rows of an (n_rows, ...) output that --dump-outputs keeps: None (all of them) where
+    n_rows * row_bytes fits the budget, else budget // row_bytes distinct row indices, ascending,
+    drawn from `seed` (the same rows in every run of the same arguments)."""
+    import numpy as np
+    keep = budget // row_bytes
+    if n_rows <= keep:
+        return None
+    return np.sort(np.random.default_rng(seed).choice(n_rows, size=keep, replace=False))
+
+
+def dump_outputs(path: str, seq, k: int, stream) -> None:
+    """--dump-outputs: one more build of the timed step's sequence, kept, and its kmer.pos readout
+    (what a caller of make.kmer.hash receives from the index: `pos`, the (k-mer row, position)
+    rows, and `count`, the occurrences per k-mer, both in the reference's order) written as
+    float64 .npy files with the index's totals.  Outputs too large for DUMP_MAX_BYTES keep a
+    seeded sample of their rows (dump_sample; the row indices are written beside them)."""
+    import numpy as np
+    import torch
+    from kmer_hasher_amd import device as D
+    os.makedirs(path, exist_ok=True)
+    idx = D.DeviceIndex.build(seq, k, stream)
+    info = idx.info()
+    check_build(info)
+    res = idx.positions(2 | 8, stream)
+    torch.cuda.synchronize()
+    totals = [info[f] for f in ("n_kmers", "n_positions", "n_pairs", "max_count")]
+    np.save(os.path.join(path, "totals.npy"), np.asarray(totals, np.float64))
+    # the budget: 16 B per pos row + 8 B per row index, 8 B per count + 8 B per row index
+    for name, t, budget in (("pos", res["pos"], DUMP_MAX_BYTES // 2),
+                            ("count", res["count"], DUMP_MAX_BYTES // 4)):
+        row_bytes = 8 * (t.numel() // max(1, t.shape[0])) + 8
+        rows = dump_sample(t.shape[0], row_bytes, budget)
+        if rows is not None:
+            t = t[torch.from_numpy(rows).to(t.device)]
+            np.save(os.path.join(path, f"{name}_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(path, f"{name}.npy"), t.cpu().numpy().astype(np.float64))
+    del res
+    idx.free()
 
 
 def _side_record(name: str, fn, *a):
@@ -1195,7 +1290,8 @@ def bench_large(args, dev) -> dict:
     t_gen = time.perf_counter() - t_gen
     stream = torch.cuda.current_stream()
     pmc = _load_pmc("large")
-    steps = max(1, args.steps)
+    # (a side record: at most 100 of its 17 + 5 ms steps, however long the headline is timed)
+    steps = max(1, min(args.steps, 100))
     # ---- build
     for _ in range(max(1, min(args.warmup, 2))):
         check_build(D.DeviceIndex.build(ta, k, stream).info())
@@ -1403,7 +1499,7 @@ def bench_readout(args, cfg, dev, world, rank):
     # (kmhg_positions_fill: pos rows and counts copied, pair rows written by host threads from
     # the position lists); the matrices' release is not timed
     host_ms = None
-    if not args.profile:
+    if args.full and not args.profile:
         import ctypes as _C
         import numpy as np
         from kmer_hasher_amd import _lib
@@ -1431,7 +1527,7 @@ def bench_readout(args, cfg, dev, world, rank):
         pmc = _load_pmc(4)
         B = survey_bytes("readout", U=U, N=N, P=P, opt=opt)
         cpu = None
-        if not args.no_cpu and not args.profile:
+        if args.full and not args.no_cpu and not args.profile:
             cpu = cpu_readout_baseline(host.tobytes(), k, opt)
         _emit({"metric": "kmer.pos pair.pos rows/s (config 4)", "value": round(P * world * args.steps / t / 1e9, 4),
                "unit": "G pair rows/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1785,7 +1881,7 @@ def bench_sharded_query(args, cfg, dev, world, rank):
     # build, then BUILD5_STEPS timed builds (each waited for and freed)
     build_rec = None
     cpu_sample = None
-    if rank == 0 and not args.profile:
+    if rank == 0 and args.full and not args.profile:
         A = synth.iid(L, 4)
         if not args.no_cpu:
             cpu_sample = (A[:CONFIG5_CPU_BP].tobytes(),

@@ -109,3 +109,35 @@ def test_sharded_roofline_splits_the_job_over_the_gpus():
     assert r["frac"] == pytest.approx(r["achieved"] / bench.HBM_PEAK_GBS, rel=1e-3)
     assert r["range_query_frac"] > r["frac"]
     assert bench.sharded_roofline(B, 0.0, 0.0, 1)["frac"] is None
+
+
+def test_headline_is_the_timed_steps_alone():
+    """The plain line: value = L x world x steps / t_build, ms_per_step = t_build / steps, and
+    the totals of the waited build; --full only marks it."""
+    import argparse
+    args = argparse.Namespace(steps=40, warmup=3, config=2, full=False)
+    info = {"n_kmers": 9_999_970, "n_positions": 9_999_970, "build": 2, "fallback": 0}
+    h = bench.headline(args, bench.CONFIGS[2], info, 40 * 0.25e-3, 1, False, 1)
+    assert h["value"] == pytest.approx(10.0 / 0.25e-3, rel=1e-6) and h["unit"] == "Mbp/s"
+    assert h["ms_per_step"] == pytest.approx(0.25) and h["steps"] == 40 and h["warmup"] == 3
+    assert h["higher_is_better"] is True and h["dtype"] == "u64" and h["full"] is False
+    assert h["config"]["parallelism"] == "single" and h["config"]["distinct_kmers"] == 9_999_970
+    for side in ("roofline", "synchronous", "query", "counts", "large", "cpu_baseline"):
+        assert side not in h
+    h8 = bench.headline(args, bench.CONFIGS[2], info, 40 * 0.25e-3, 8, True, 1)
+    assert h8["value"] == pytest.approx(8 * h["value"]) and h8["n_gpus"] == 8
+    assert h8["config"]["parallelism"] == "replicas8"
+
+
+def test_dump_sample_is_fixed_and_within_budget():
+    """--dump-outputs keeps every row of an output that fits its budget, else the same ascending
+    sample of distinct rows in every run."""
+    assert bench.dump_sample(1000, 24, 24 * 1000) is None
+    a = bench.dump_sample(1_000_000, 24, 24 * 1000)
+    b = bench.dump_sample(1_000_000, 24, 24 * 1000)
+    assert a.shape == (1000,) and (a == b).all()
+    assert (a[1:] > a[:-1]).all() and a[0] >= 0 and a[-1] < 1_000_000
+    # config 2's pos (16 B per row + its 8-B index) and count (8 + 8 B) together, 10 M rows each
+    n = 10_000_000
+    kept = sum(rb * (bench.DUMP_MAX_BYTES // d // rb) for rb, d in ((24, 2), (16, 4)))
+    assert kept <= bench.DUMP_MAX_BYTES * 3 // 4 and kept < 24 * n

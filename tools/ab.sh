@@ -10,7 +10,7 @@ VARS=()
 while [ $# -gt 0 ] && [ "$1" != "--" ]; do VARS+=("$1"); shift; done
 [ $# -gt 0 ] && shift
 ARGS=("$@")
-[ ${#ARGS[@]} -eq 0 ] && ARGS=(--no-cpu)
+[ ${#ARGS[@]} -eq 0 ] && ARGS=(--full --no-cpu)
 : > "$OUT/ab.log"
 for rep in 1 2; do
   for v in "${VARS[@]}"; do

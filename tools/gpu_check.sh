@@ -13,7 +13,7 @@ tail -3 "$OUT/pytest_gpu.log"
 timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 \
   || { echo "smoke failed"; tail -30 "$OUT/smoke.log"; exit 1; }
 cat "$OUT/smoke.log"
-timeout -k 10 300 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" \
+timeout -k 10 300 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" \
   || { echo "bench failed"; tail -30 "$OUT/bench.err"; exit 1; }
 cat "$OUT/bench.json"
 echo "check $TAG done"

@@ -7,7 +7,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/pmcq_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-ARGS=(--steps 5 --warmup 1 --profile)
+ARGS=(--full --steps 5 --warmup 1 --profile)
 timeout -k 10 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/f_diag" -o run \
   -- python3 "$REPO/bench.py" "${ARGS[@]}" > "$OUT/f_diag.log" 2>&1
 KMHG_QUERY_DIAG=0 timeout -k 10 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/f_table" -o run \

@@ -12,7 +12,7 @@ OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 ARGS=("$@")
-[ ${#ARGS[@]} -eq 0 ] && ARGS=(--steps 10 --warmup 2 --profile)
+[ ${#ARGS[@]} -eq 0 ] && ARGS=(--full --steps 10 --warmup 2 --profile)
 PROG=${PROG:-bench.py}
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/ktrace" -o run \
   -- python3 "$REPO/$PROG" "${ARGS[@]}" > "$OUT/ktrace.log" 2>&1

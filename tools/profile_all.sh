@@ -11,13 +11,13 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 cd "$REPO"
 run() { local tag=$1; shift; bash tools/profile.sh "$tag" "$@" || { echo "profile $tag failed"; exit 1; }; echo "profile $tag ok"; }
 if [ "$PART" = A ]; then
-  run ${P}p2 --steps 10 --warmup 2 --profile
-  run ${P}plegs --steps 3 --warmup 1 --no-cpu --no-large
-  run ${P}p3 --config 3 --steps 3 --warmup 1 --profile --no-cpu
+  run ${P}p2 --full --steps 10 --warmup 2 --profile
+  run ${P}plegs --full --steps 3 --warmup 1 --no-cpu --no-large
+  run ${P}p3 --full --config 3 --steps 3 --warmup 1 --profile --no-cpu
   PROG=tools/query_unrelated.py run ${P}punrel --steps 10
 else
-  run ${P}p4 --config 4 --steps 3 --warmup 1 --profile --no-cpu
-  run ${P}p5 --config 5 --steps 3 --warmup 1 --no-cpu
+  run ${P}p4 --full --config 4 --steps 3 --warmup 1 --profile --no-cpu
+  run ${P}p5 --full --config 5 --steps 3 --warmup 1 --no-cpu
   run ${P}plarge --only-large --steps 3 --warmup 1
   PROG=tools/query_unrelated.py run ${P}plargeunrel --L 500000000 --steps 10
 fi

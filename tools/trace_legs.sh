@@ -8,5 +8,5 @@ OUT=$REPO/gpurun_out/trace_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o run \
-  -- python3 "$REPO/bench.py" --no-cpu --steps 3 --warmup 1 > "$OUT/bench.log" 2>&1
+  -- python3 "$REPO/bench.py" --full --no-cpu --steps 3 --warmup 1 > "$OUT/bench.log" 2>&1
 echo "trace $TAG done"
