@@ -25,6 +25,10 @@
  *   kmhg_build_device_part / kmhg_part_info / kmhg_part_export
  *        <- the owner-computes partition of the reader pool  src/kmer_reader.c:28-39, 101-108
  *           (multi-GPU make.kmer.hash; no single reference entry point)
+ *   kmhg_part_first_mask / kmhg_part_positions_size / kmhg_part_positions_fill_device /
+ *   kmhg_merge_part_positions
+ *        <- .Call("kmer_positions", ptr, opt.flag)           src/kmer_hash.c:1054-1147
+ *           over that partition (src/kmer_reader.c:28-39), the parts never assembled
  *   KMHG_DEVICES=d0,d1,... (environment): kmhg_query_run splits seq.kmer.pos over those devices
  *           (index peer-copied once per device, rows copied straight into the caller's buffer)
  *   registration of the three symbols with arities 3/2/3    src/kmer_hash.c:1205-1224
@@ -171,6 +175,51 @@ int kmhg_query_tile_offsets(kmhg_query *q, uint64_t *d_out, int64_t *n_tiles, vo
 int kmhg_merge_part_rows(const void *d_rows, const uint64_t *d_seg_base,
                          const uint64_t *d_tile_off, int n_parts, int64_t n_tiles, int k,
                          int64_t w0, void *d_out, void *stream);
+/* kmer.pos over the PARTS of an owner-computes build (kmhg_build_device_part), without assembling
+ * them: .Call("kmer_positions", ptr, opt.flag), src/kmer_hash.c:1054-1147, of an index that
+ * stays split over the ranks as the reference's reader pool splits its k-mers
+ * (src/kmer_reader.c:28-39).  A k-mer's row label is its rank by first occurrence; every k-mer
+ * lives in one part, so the parts' first positions are disjoint and only an L-bit mask has to
+ * meet: each part marks its own (kmhg_part_first_mask), the caller ORs the masks (an all-reduce
+ * SUM of the words: no bit is set twice), each part writes its rows labelled with their rows in
+ * the whole result (kmhg_part_positions_fill_device), and the root places every part's segments
+ * (kmhg_merge_part_positions).  The merged result is byte for byte kmhg_positions_fill_device of
+ * the single-device index in KMHG_ORDER_FIRST.
+ * Limits: position indexes only, first-occurrence order only.  KMHG_ORDER_KHASH on a part is
+ * refused: the khash replay needs every key on one host, which is what not assembling avoids.
+ * kmhg_positions_size / _fill / _fill_device on a part keep refusing ("must be assembled").
+ * Errors: "not a part index" for any other index.
+ *
+ * kmhg_part_first_mask: d_mask <- ceil(L / 32) u32 words, bit (p - 1) & 31 of word (p - 1) >> 5
+ *   set for the 1-based first position p of every k-mer the part holds (all zero for a part that
+ *   owns no bucket).
+ * kmhg_part_positions_size: the part's own distinct k-mers (always: the labels are always
+ *   written), and its pos / pair rows for the set opt bits.  Needs no mask.
+ * kmhg_part_positions_fill_device: d_global_mask = the OR of every part's mask.  Writes, in
+ *   ascending label: d_labels[n_kmers] (always), and for the set opt bits d_counts[n_kmers],
+ *   d_kmers (n_kmers strings, stride k + 1), d_pos (label, pos) rows, d_pairs (label, x, y) rows
+ *   (j-outer / k-inner); pointers of unset bits may be NULL. */
+int kmhg_part_first_mask(kmhg_index *part, uint32_t *d_mask, void *stream);
+int kmhg_part_positions_size(kmhg_index *part, uint32_t opt, int64_t *n_kmers,
+                             int64_t *n_pos_rows, int64_t *n_pair_rows);
+int kmhg_part_positions_fill_device(kmhg_index *part, const uint32_t *d_global_mask, uint32_t opt,
+                                    int32_t *d_labels, char *d_kmers, int32_t *d_pos,
+                                    int32_t *d_pairs, int32_t *d_counts, void *stream);
+/* The root's merge of n_parts such segments, all in device memory on `stream`'s device.  Host
+ * arrays of n_parts entries: the parts' sizes (n_kmers; n_pos_rows / n_pair_rows for their opt
+ * bits) and device pointers (a part without k-mers, or without rows of a kind, may pass NULL
+ * there).  d_counts is read whenever opt has POS, PAIRS or COUNT -- the row offsets are scans of
+ * the merged counts -- so the parts are filled with KMHG_OPT_COUNT added in that case.  Writes the
+ * outputs of the set opt bits, sized by the sums of the parts' sizes: counts and strings placed
+ * by label, each k-mer's row run copied to its offset.  KMHG_EOVERFLOW ("result has more than
+ * 2^31-1 rows") when a sum exceeds int32. */
+int kmhg_merge_part_positions(int n_parts, uint32_t opt, int k, const int64_t *n_kmers,
+                              const int64_t *n_pos_rows, const int64_t *n_pair_rows,
+                              const int32_t *const *d_labels, const int32_t *const *d_counts,
+                              const char *const *d_kmers, const int32_t *const *d_pos,
+                              const int32_t *const *d_pairs, char *d_out_kmers,
+                              int32_t *d_out_pos, int32_t *d_out_pairs, int32_t *d_out_counts,
+                              void *stream);
 /* A device sequence as it crosses xGMI (C1 scatter / broadcast of the multi-GPU query and of
  * the owner-computes build): what the reference reads of a char -- its 2-bit code (c >> 1) & 3
  * and its N test, src/kmer_pos.c:81-83 -- as 16 chars per u32 code word and u16 N-flag word
@@ -321,7 +370,8 @@ int kmhg_image_import(const int64_t header[8], const void *d_table, const void *
  * is built on exactly one device, its positions ascending, with no all-to-all.  The parts,
  * concatenated in bucket order (positions in part order, list ends rebased by each part's first
  * position index), ARE the single-device index: the caller gathers them (RCCL) and imports the
- * result with kmhg_image_import.  A part index refuses queries and readout.
+ * result with kmhg_image_import.  A part index refuses the whole-index queries and readout; it
+ * is read in place by kmhg_query_run_device_part and the kmhg_part_* kmer.pos entries.
  *   info = {b0, nb, nb_total, slots per bucket, positions N, distinct k-mers U, pairs P, max n,
  *           owns the side slot (key ~0 at k = 32) 0/1, code block bytes}
  *   export: d_table <- its nb x capb slots with count >= 2 list ends + pos_base; d_side_slot <-

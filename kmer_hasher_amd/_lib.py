@@ -74,6 +74,12 @@ _PROTOS = {
     "kmhg_runs_expand": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp]),
     "kmhg_merge_part_rows": (C.c_int, [vp, vp, vp, C.c_int, C.c_int64, C.c_int, C.c_int64, vp,
                                        vp]),
+    "kmhg_part_first_mask": (C.c_int, [vp, vp, vp]),
+    "kmhg_part_positions_size": (C.c_int, [vp, C.c_uint32, i64p, i64p, i64p]),
+    "kmhg_part_positions_fill_device": (C.c_int, [vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp]),
+    "kmhg_merge_part_positions": (C.c_int, [C.c_int, C.c_uint32, C.c_int, i64p, i64p, i64p,
+                                            C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                            C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp, vp]),
     "kmhg_pairs_run": (C.c_int, [vp, vp, C.POINTER(vp), i64p]),
     "kmhg_pairs_run_device": (C.c_int, [vp, vp, vp, C.POINTER(vp), i64p]),
     "kmhg_query_fill": (C.c_int, [vp, vp]),

@@ -29,6 +29,7 @@
 
 #include "kmhg_common.h"
 #include "kmhg_kernels.h"
+#include "kmhg_parts_read.h"
 #include "kmhg_fastx.h"
 #include "kmhg_khash.h"
 #include "kmhg_sh.h"
@@ -2455,6 +2456,17 @@ void check_sh(const kmhg_index* idx) {
 }
 
 // ---------------------------------------------------------------------------- readout
+uint32_t side_bucket_of(uint32_t nb);
+// The slots a readout walks: a part's side slot is written only by the part that owns its
+// bucket (kmhg_part_info's info[8]); elsewhere it is not part of the table.
+uint64_t read_slots(const kmhg_index* idx) {
+  if (!idx->is_part) return idx->slots();
+  const Geom& G = idx->geom;
+  const uint32_t side_b = side_bucket_of(G.nbh);
+  const bool owns = G.nb && side_b >= G.b0 && side_b < G.b0 + G.nb;
+  return (uint64_t)G.nb * G.capb + (owns ? 1 : 0);
+}
+
 void prepare_canon(kmhg_index* idx, hipStream_t s) {
   ReleaseGroup rg(s);
   idx->stream = s;
@@ -2480,8 +2492,8 @@ void prepare_canon(kmhg_index* idx, hipStream_t s) {
   const uint32_t U = (uint32_t)idx->U;
   DBuf<uint2> F(L, s);
   HIPC(hipMemsetAsync(F.p, 0xFF, (size_t)L * 8, s));
-  if (U) LAUNCH("k_read_first", s, launch_read_first(idx->table.p, idx->slots(), idx->positions.p,
-                                                     F.p, s));
+  if (U) LAUNCH("k_read_first", s, launch_read_first(idx->table.p, read_slots(idx),
+                                                     idx->positions.p, F.p, s));
   const uint32_t nt = tiles_for(L);
   const size_t scratch_bytes = (size_t)nt * 24 + 64 + sizeof(ReadMeta);
   DBuf<uint8_t> scratch(scratch_bytes, s);
@@ -2604,6 +2616,141 @@ void positions_device(kmhg_index* idx, uint32_t opt, char* kmers, int32_t* pos, 
            launch_read_pairs(c.pkeys.p, c.pair_off.p, (uint32_t)c.n_multi, idx->P, c.rinfo.p,
                              idx->positions.p, tile_key.p, pairs, s));
   }
+}
+
+// ------------------------------------------------------------------ kmer.pos over resident parts
+// kmer.pos (src/kmer_hash.c:1054-1147) of an index that stays split in its owner-computes parts
+// (src/kmer_reader.c:28-39): kmhg_parts_read.h.  A part is read in its own first-occurrence
+// order (prepare_canon over its slots), which is ascending global label.
+kmhg_index* check_part_read(kmhg_index* idx) {
+  if (!idx) fail(KMHG_EINVAL, "null index");
+  if (!idx->is_part) fail(KMHG_EINVAL, "not a part index");
+  return idx;
+}
+
+void part_first_mask(kmhg_index* idx, uint32_t* mask, hipStream_t s) {
+  ReleaseGroup rg(s);
+  finish_build(idx);
+  idx->stream = s;
+  HIPC(hipMemsetAsync(mask, 0, mask_words(idx->L) * 4, s));
+  if (idx->U)                    // (a part that owns no bucket has no table to walk)
+    LAUNCH("k_part_mask", s,
+           launch_part_mask(idx->table.p, read_slots(idx), idx->positions.p, idx->L, mask, s));
+}
+
+void part_positions_device(kmhg_index* idx, const uint32_t* mask, uint32_t opt, int32_t* labels,
+                           char* kmers, int32_t* pos, int32_t* pairs, int32_t* counts,
+                           hipStream_t s) {
+  ReleaseGroup rg(s);
+  finish_build(idx);
+  if (idx->row_order != KMHG_ORDER_FIRST)
+    fail(KMHG_EINVAL, "kmer.pos over parts is in first-occurrence order only (the khash order "
+                      "needs every key on one host: assemble the parts)");
+  const uint32_t U = (uint32_t)idx->U;
+  if (!U) return;
+  if (!mask || !labels) fail(KMHG_EINVAL, "null argument");
+  if (((opt & KMHG_OPT_KMER) && !kmers) || ((opt & KMHG_OPT_COUNT) && !counts) ||
+      ((opt & KMHG_OPT_POS) && idx->N && !pos) || ((opt & KMHG_OPT_PAIRS) && idx->P && !pairs))
+    fail(KMHG_EINVAL, "null output for a requested opt bit");
+  prepare_canon(idx, s);
+  Canon& c = idx->canon;
+  const uint64_t W = mask_words(idx->L);
+  const uint32_t nt = tiles_for(W);
+  DBuf<uint32_t> wprefix(W, s);
+  DBuf<uint64_t> status((size_t)nt + 1, s);        // look-back words, then the ticket
+  HIPC(hipMemsetAsync(status.p, 0, ((size_t)nt + 1) * 8, s));
+  LAUNCH("k_mask_prefix", s,
+         launch_mask_prefix(mask, W, status.p, reinterpret_cast<uint32_t*>(status.p + nt),
+                            wprefix.p, s));
+  LAUNCH("k_part_labels", s,
+         launch_part_labels(c.rinfo.p, U, idx->positions.p, mask, wprefix.p, W, labels, s));
+  if (opt & (KMHG_OPT_KMER | KMHG_OPT_COUNT))
+    LAUNCH("k_read_keys", s,
+           launch_read_keys(c.perm.p, c.rinfo.p, U, idx->table.p, idx->k,
+                            (opt & KMHG_OPT_COUNT) ? counts : nullptr,
+                            (opt & KMHG_OPT_KMER) ? kmers : nullptr, s));
+  if ((opt & KMHG_OPT_POS) && idx->N) {
+    DBuf<uint32_t> tile_key((size_t)read_pos_tiles(idx->N) + 1, s);
+    LAUNCH("k_read_pos_labels", s,
+           launch_read_pos_labels(c.rinfo.p, c.canon_off.p, U, idx->N, idx->positions.p,
+                                  tile_key.p, labels, reinterpret_cast<int2*>(pos), s));
+  }
+  if ((opt & KMHG_OPT_PAIRS) && idx->P) {
+    DBuf<uint32_t> tile_key((size_t)read_pairs_tiles(idx->P) + 1, s);
+    LAUNCH("k_read_pairs_labels", s,
+           launch_read_pairs_labels(c.pkeys.p, c.pair_off.p, (uint32_t)c.n_multi, idx->P,
+                                    c.rinfo.p, idx->positions.p, tile_key.p, labels, pairs, s));
+  }
+  HIPC(hipGetLastError());
+}
+
+// The root's merge.  Per-key row runs keep their order inside a part, so a run only needs the
+// difference between where it starts in the whole result (the scan of the merged counts) and
+// where it starts in its part (the scan of the part's counts): delta, indexed by label.
+void merge_part_positions(int n_parts, uint32_t opt, int k, const int64_t* nk, const int64_t* np,
+                          const int64_t* npp, const int32_t* const* labels,
+                          const int32_t* const* counts, const char* const* kmers,
+                          const int32_t* const* pos, const int32_t* const* pairs, char* o_kmers,
+                          int32_t* o_pos, int32_t* o_pairs, int32_t* o_counts, hipStream_t s) {
+  ReleaseGroup rg(s);
+  const bool want_pos = opt & KMHG_OPT_POS, want_pairs = opt & KMHG_OPT_PAIRS;
+  const bool need_counts = want_pos || want_pairs || (opt & KMHG_OPT_COUNT);
+  uint64_t Ut = 0, Nt = 0, Pt = 0, Umax = 0;
+  for (int r = 0; r < n_parts; ++r) {
+    if (nk[r] < 0 || (want_pos && np[r] < 0) || (want_pairs && npp[r] < 0))
+      fail(KMHG_EINVAL, "bad merge arguments");
+    Ut += (uint64_t)nk[r];
+    Umax = std::max<uint64_t>(Umax, (uint64_t)nk[r]);
+    if (want_pos) Nt += (uint64_t)np[r];
+    if (want_pairs) Pt += (uint64_t)npp[r];
+    if (nk[r] && (!labels[r] || (need_counts && !counts[r]) ||
+                  ((opt & KMHG_OPT_KMER) && !kmers[r]) || (want_pos && np[r] && !pos[r]) ||
+                  (want_pairs && npp[r] && !pairs[r])))
+      fail(KMHG_EINVAL, "null argument");
+  }
+  if (Ut > (uint64_t)INT32_MAX || Nt > (uint64_t)INT32_MAX || Pt > (uint64_t)INT32_MAX)
+    fail(KMHG_EOVERFLOW, "result has more than 2^31-1 rows");
+  if (!Ut) return;
+  if (((opt & KMHG_OPT_KMER) && !o_kmers) || ((opt & KMHG_OPT_COUNT) && !o_counts) ||
+      (want_pos && Nt && !o_pos) || (want_pairs && Pt && !o_pairs))
+    fail(KMHG_EINVAL, "null output for a requested opt bit");
+  const uint32_t U = (uint32_t)Ut;
+  DBuf<int32_t> gc_own;
+  int32_t* gcount = nullptr;
+  if (need_counts) {
+    if (opt & KMHG_OPT_COUNT) gcount = o_counts;
+    else { gc_own.reset(U); gc_own.bind(s); gcount = gc_own.p; }
+  }
+  for (int r = 0; r < n_parts; ++r)
+    if (nk[r])
+      LAUNCH("k_merge_keys", s,
+             launch_merge_keys(labels[r], need_counts ? counts[r] : nullptr,
+                               (opt & KMHG_OPT_KMER) ? kmers[r] : nullptr, (uint32_t)nk[r], k, U,
+                               gcount, (opt & KMHG_OPT_KMER) ? o_kmers : nullptr, s));
+  if ((want_pos && Nt) || (want_pairs && Pt)) {
+    DBuf<uint64_t> goff(U, s), loff(Umax, s), scr(scan_u64_scratch(U) + 1, s), total(2, s);
+    DBuf<int64_t> delta(U, s);
+    for (int pass = 0; pass < 2; ++pass) {           // pos rows, then pair rows
+      const bool pr = pass == 1;
+      const uint64_t n_out = pr ? Pt : Nt;
+      if (!(pr ? want_pairs : want_pos) || !n_out) continue;
+      LAUNCH("k_rows_per_key", s, launch_rows_per_key(gcount, U, pr, goff.p, s));
+      LAUNCH("k_scan_u64", s, launch_scan_u64(goff.p, U, total.p, scr.p, s));
+      for (int r = 0; r < n_parts; ++r) {
+        const uint64_t nr = (uint64_t)(pr ? npp[r] : np[r]);
+        if (!nk[r] || !nr) continue;
+        const uint32_t Up = (uint32_t)nk[r];
+        LAUNCH("k_rows_per_key", s, launch_rows_per_key(counts[r], Up, pr, loff.p, s));
+        LAUNCH("k_scan_u64", s, launch_scan_u64(loff.p, Up, total.p + 1, scr.p, s));
+        LAUNCH("k_merge_delta", s,
+               launch_merge_delta(labels[r], loff.p, goff.p, Up, U, delta.p, s));
+        LAUNCH("k_merge_rows", s,
+               launch_merge_rows(pr ? pairs[r] : pos[r], nr, pr ? 3 : 2, delta.p, U, n_out,
+                                 pr ? o_pairs : o_pos, s));
+      }
+    }
+  }
+  HIPC(hipGetLastError());
 }
 
 // ------------------------------------------------------------------ multi-device seq.kmer.pos
@@ -3635,6 +3782,58 @@ int kmhg_merge_part_rows(const void* d_rows, const uint64_t* d_seg_base, const u
                                   (uint32_t)n_parts, (uint32_t)n_tiles, k, w0,
                                   reinterpret_cast<int2*>(d_out), s));
     HIPC(hipGetLastError());
+  });
+}
+
+int kmhg_part_first_mask(kmhg_index* part, uint32_t* d_mask, void* stream) {
+  return guarded([&] {
+    check_part_read(part);
+    if (!d_mask) fail(KMHG_EINVAL, "null argument");
+    DeviceGuard g(part->device);
+    part_first_mask(part, d_mask, (hipStream_t)stream);
+  });
+}
+
+int kmhg_part_positions_size(kmhg_index* part, uint32_t opt, int64_t* n_kmers,
+                             int64_t* n_pos_rows, int64_t* n_pair_rows) {
+  return guarded([&] {
+    check_part_read(part);
+    DeviceGuard g(part->device);
+    finish_build(part);
+    if (n_kmers) *n_kmers = (int64_t)part->U;
+    if (n_pos_rows) *n_pos_rows = (opt & KMHG_OPT_POS) ? (int64_t)part->N : 0;
+    if (n_pair_rows) *n_pair_rows = (opt & KMHG_OPT_PAIRS) ? (int64_t)part->P : 0;
+  });
+}
+
+int kmhg_part_positions_fill_device(kmhg_index* part, const uint32_t* d_global_mask, uint32_t opt,
+                                    int32_t* d_labels, char* d_kmers, int32_t* d_pos,
+                                    int32_t* d_pairs, int32_t* d_counts, void* stream) {
+  return guarded([&] {
+    check_part_read(part);
+    DeviceGuard g(part->device);
+    part_positions_device(part, d_global_mask, opt, d_labels, d_kmers, d_pos, d_pairs, d_counts,
+                          (hipStream_t)stream);
+  });
+}
+
+int kmhg_merge_part_positions(int n_parts, uint32_t opt, int k, const int64_t* n_kmers,
+                              const int64_t* n_pos_rows, const int64_t* n_pair_rows,
+                              const int32_t* const* d_labels, const int32_t* const* d_counts,
+                              const char* const* d_kmers, const int32_t* const* d_pos,
+                              const int32_t* const* d_pairs, char* d_out_kmers,
+                              int32_t* d_out_pos, int32_t* d_out_pairs, int32_t* d_out_counts,
+                              void* stream) {
+  return guarded([&] {
+    if (n_parts < 1 || k < 1 || k > 32) fail(KMHG_EINVAL, "bad merge arguments");
+    if (!n_kmers || !d_labels || ((opt & KMHG_OPT_POS) && (!n_pos_rows || !d_pos)) ||
+        ((opt & KMHG_OPT_PAIRS) && (!n_pair_rows || !d_pairs)) ||
+        ((opt & KMHG_OPT_KMER) && !d_kmers) ||
+        ((opt & (KMHG_OPT_POS | KMHG_OPT_PAIRS | KMHG_OPT_COUNT)) && !d_counts))
+      fail(KMHG_EINVAL, "null argument");
+    merge_part_positions(n_parts, opt, k, n_kmers, n_pos_rows, n_pair_rows, d_labels, d_counts,
+                         d_kmers, d_pos, d_pairs, d_out_kmers, d_out_pos, d_out_pairs,
+                         d_out_counts, (hipStream_t)stream);
   });
 }
 

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include "kmhg_common.h"
 #include "kmhg_kernels.h"
+#include "kmhg_parts_read.h"
 #include "kmhg_device.h"
 
 namespace kmhg {
@@ -1099,10 +1100,14 @@ k_row_tiles(const Off* __restrict__ off, uint32_t nkeys, uint64_t nrows, uint32_
   if (blockIdx.x == 0 && threadIdx.x == 0) tile_key[ntiles] = nkeys - 1;
 }
 
+// LAB (kmer.pos over owner-computes parts, kmhg_parts_read.h): row c is labelled labels[c], its
+// rank in the whole index, instead of c + 1.
+template <bool LAB>
 __global__ void __launch_bounds__(BLOCK)
 k_read_pos(const uint2* __restrict__ rinfo, const uint32_t* __restrict__ canon_off,
            const uint32_t* __restrict__ tile_key, uint64_t nrows,
-           const int32_t* __restrict__ positions, int2* __restrict__ out) {
+           const int32_t* __restrict__ positions, const int32_t* __restrict__ labels,
+           int2* __restrict__ out) {
   __shared__ uint32_t off[TILE + 1];
   __shared__ __attribute__((aligned(16))) int2 stage[TILE];
   const uint64_t r0 = (uint64_t)blockIdx.x * TILE;
@@ -1119,12 +1124,17 @@ k_read_pos(const uint2* __restrict__ rinfo, const uint32_t* __restrict__ canon_o
     uint32_t lo = 0, hi = nk - 1;
     while (lo < hi) { uint32_t mid = (lo + hi + 1) >> 1; if (off[mid] <= rb) lo = mid; else hi = mid - 1; }
     uint2 v = rinfo[c0 + lo];
+    int32_t lab = LAB ? labels[c0 + lo] : (int32_t)(c0 + lo + 1);
     uint32_t t = (uint32_t)(rb - off[lo]);
     const uint32_t nr = (uint32_t)min<uint64_t>(WPT, r1 - rb);
     for (uint32_t i = 0; i < nr; ++i) {
-      if (i > 0 && ++t == v.x) { v = rinfo[c0 + ++lo]; t = 0; }
+      if (i > 0 && ++t == v.x) {
+        v = rinfo[c0 + ++lo];
+        t = 0;
+        lab = LAB ? labels[c0 + lo] : (int32_t)(c0 + lo + 1);
+      }
       const int32_t p = v.x == 1 ? (int32_t)v.y : positions[v.y - v.x + t];
-      stage[threadIdx.x * WPT + i] = make_int2((int32_t)(c0 + lo + 1), p);
+      stage[threadIdx.x * WPT + i] = make_int2(lab, p);
     }
   }
   __syncthreads();
@@ -1157,11 +1167,12 @@ constexpr int PR_HALF = PR_PER / 2;
 constexpr int PR_TILE = BLOCK * PR_PER;
 static_assert(PR_TILE <= 65536, "offsets inside a tile are 16-bit");
 
+template <bool LAB>                        // LAB: as k_read_pos
 __global__ void __launch_bounds__(BLOCK, 6)
 k_read_pairs(const uint32_t* __restrict__ pkeys, const uint64_t* __restrict__ pair_off,
              const uint32_t* __restrict__ tile_key, uint64_t nrows,
              const uint2* __restrict__ rinfo, const int32_t* __restrict__ positions,
-             int32_t* __restrict__ out) {
+             const int32_t* __restrict__ labels, int32_t* __restrict__ out) {
   __shared__ uint16_t offr[PR_TILE];        // key start rows - r0 (the first key's clamped to 0)
   __shared__ __attribute__((aligned(16))) int32_t stage[3 * BLOCK * PR_HALF];
   __shared__ uint64_t first_off;
@@ -1189,6 +1200,7 @@ k_read_pairs(const uint32_t* __restrict__ pkeys, const uint64_t* __restrict__ pa
       while (lo < hi) { uint32_t mid = (lo + hi + 1) >> 1; if (offr[mid] <= rel) lo = mid; else hi = mid - 1; }
       uint32_t c = pkeys[m0 + lo];
       uint2 v = rinfo[c];
+      uint32_t lab = LAB ? (uint32_t)labels[c] : c + 1;
       uint32_t n = v.x;
       const uint64_t t = lo == 0 ? rb - first_off : (uint64_t)(rel - offr[lo]);
       // largest j with S(j) = j*(2n-j-1)/2 <= t
@@ -1214,6 +1226,7 @@ k_read_pairs(const uint32_t* __restrict__ pkeys, const uint64_t* __restrict__ pa
           if (++j == n - 1) {
             c = pkeys[m0 + ++lo];
             v = rinfo[c];
+            lab = LAB ? (uint32_t)labels[c] : c + 1;
             n = v.x;
             base = v.y - v.x;
             j = 0;
@@ -1222,7 +1235,7 @@ k_read_pairs(const uint32_t* __restrict__ pkeys, const uint64_t* __restrict__ pa
         }
         ij[i] = base + j;
         iq[i] = base + q;
-        cc[i] = c + 1;
+        cc[i] = lab;
       }
       int32_t pj[PR_HALF], pq[PR_HALF];
 #pragma unroll
@@ -1823,8 +1836,18 @@ void launch_read_pos(const uint2* rinfo, const uint32_t* canon_off, uint32_t U, 
   const uint32_t nt = grid_for(nrows, TILE);
   hipLaunchKernelGGL(k_row_tiles<uint32_t>, dim3(std::min(grid_for(U, BLOCK), 16384u)),
                      dim3(BLOCK), 0, s, canon_off, U, nrows, (uint32_t)TILE, tile_key, nt);
-  hipLaunchKernelGGL(k_read_pos, dim3(nt), dim3(BLOCK), 0, s, rinfo, canon_off, tile_key, nrows,
-                     positions, out);
+  hipLaunchKernelGGL(k_read_pos<false>, dim3(nt), dim3(BLOCK), 0, s, rinfo, canon_off, tile_key,
+                     nrows, positions, (const int32_t*)nullptr, out);
+}
+void launch_read_pos_labels(const uint2* rinfo, const uint32_t* canon_off, uint32_t U,
+                            uint64_t nrows, const int32_t* positions, uint32_t* tile_key,
+                            const int32_t* labels, int2* out, hipStream_t s) {
+  if (!nrows) return;
+  const uint32_t nt = grid_for(nrows, TILE);
+  hipLaunchKernelGGL(k_row_tiles<uint32_t>, dim3(std::min(grid_for(U, BLOCK), 16384u)),
+                     dim3(BLOCK), 0, s, canon_off, U, nrows, (uint32_t)TILE, tile_key, nt);
+  hipLaunchKernelGGL(k_read_pos<true>, dim3(nt), dim3(BLOCK), 0, s, rinfo, canon_off, tile_key,
+                     nrows, positions, labels, out);
 }
 uint32_t read_pos_tiles(uint64_t nrows) { return grid_for(nrows, TILE); }
 void launch_read_pairs(const uint32_t* pkeys, const uint64_t* pair_off, uint32_t M,
@@ -1834,8 +1857,19 @@ void launch_read_pairs(const uint32_t* pkeys, const uint64_t* pair_off, uint32_t
   const uint32_t nt = grid_for(nrows, PR_TILE);
   hipLaunchKernelGGL(k_row_tiles<uint64_t>, dim3(std::min(grid_for(M, BLOCK), 16384u)),
                      dim3(BLOCK), 0, s, pair_off, M, nrows, (uint32_t)PR_TILE, tile_key, nt);
-  hipLaunchKernelGGL(k_read_pairs, dim3(nt), dim3(BLOCK), 0, s, pkeys, pair_off, tile_key, nrows,
-                     rinfo, positions, out);
+  hipLaunchKernelGGL(k_read_pairs<false>, dim3(nt), dim3(BLOCK), 0, s, pkeys, pair_off, tile_key,
+                     nrows, rinfo, positions, (const int32_t*)nullptr, out);
+}
+void launch_read_pairs_labels(const uint32_t* pkeys, const uint64_t* pair_off, uint32_t M,
+                              uint64_t nrows, const uint2* rinfo, const int32_t* positions,
+                              uint32_t* tile_key, const int32_t* labels, int32_t* out,
+                              hipStream_t s) {
+  if (!nrows) return;
+  const uint32_t nt = grid_for(nrows, PR_TILE);
+  hipLaunchKernelGGL(k_row_tiles<uint64_t>, dim3(std::min(grid_for(M, BLOCK), 16384u)),
+                     dim3(BLOCK), 0, s, pair_off, M, nrows, (uint32_t)PR_TILE, tile_key, nt);
+  hipLaunchKernelGGL(k_read_pairs<true>, dim3(nt), dim3(BLOCK), 0, s, pkeys, pair_off, tile_key,
+                     nrows, rinfo, positions, labels, out);
 }
 uint32_t read_pairs_tiles(uint64_t nrows) { return grid_for(nrows, PR_TILE); }
 

@@ -256,6 +256,88 @@ class DevicePart(DeviceIndex):
                 C.byref(q), C.byref(h)))
         return DeviceQuery(q.value, h.value, seq.device)
 
+    # ---- kmer.pos over resident parts (no assembly) --------------------------------------
+    def first_mask(self, stream=None) -> torch.Tensor:
+        """kmhg_part_first_mask: ceil(L / 32) int32 words, one bit per first position of the
+        k-mers this part holds.  The parts' masks are disjoint: their sum is their union."""
+        mask = torch.empty((self.L + 31) // 32, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().kmhg_part_first_mask(self._h, C.c_void_p(mask.data_ptr()),
+                                                       _stream_ptr(stream)))
+        return mask
+
+    def positions_part(self, mask: torch.Tensor, opt: int, stream=None) -> dict:
+        """kmhg_part_positions_fill_device: this part's kmer.pos rows labelled with their rows in
+        the whole index, given the union `mask` of every part's first_mask.  {'labels': int32
+        (U_part,), and for the requested bits 'kmer', 'pos', 'pair.pos', 'count' as
+        DeviceIndex.positions}, all in ascending label."""
+        if mask.dtype != torch.int32 or mask.numel() != (self.L + 31) // 32 or \
+                mask.device != self.device or not mask.is_contiguous():
+            raise ValueError("mask must be the contiguous int32 words of first_mask()")
+        L = _lib.lib()
+        nk, npos, npair = C.c_int64(), C.c_int64(), C.c_int64()
+        _lib.check(L.kmhg_part_positions_size(self._h, opt, C.byref(nk), C.byref(npos),
+                                              C.byref(npair)))
+        dev = self.device
+        out = {"labels": torch.empty((nk.value,), dtype=torch.int32, device=dev),
+               "kmer": None, "pos": None, "pair.pos": None, "count": None}
+        if opt & 1:
+            out["kmer"] = torch.empty((nk.value, self.k + 1), dtype=torch.uint8, device=dev)
+        if opt & 2:
+            out["pos"] = torch.empty((npos.value, 2), dtype=torch.int32, device=dev)
+        if opt & 4:
+            out["pair.pos"] = torch.empty((npair.value, 3), dtype=torch.int32, device=dev)
+        if opt & 8:
+            out["count"] = torch.empty((nk.value,), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.kmhg_part_positions_fill_device(
+                self._h, C.c_void_p(mask.data_ptr()), opt, _dptr(out["labels"]),
+                _dptr(out["kmer"]), _dptr(out["pos"]), _dptr(out["pair.pos"]),
+                _dptr(out["count"]), _stream_ptr(stream)))
+        return out
+
+
+def _dptr(t):
+    """A tensor's device pointer, NULL for None or an empty tensor."""
+    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+
+
+def merge_part_positions(segs: list[dict], opt: int, k: int, stream=None) -> dict:
+    """kmhg_merge_part_positions: every part's positions_part() dict (on one device; each with
+    'count' whenever opt has bit 2, 4 or 8) into the dict DeviceIndex.positions(opt) of the whole
+    index returns: counts and strings placed by label, each k-mer's rows at its offset."""
+    if (opt & 14) and any(s.get("count") is None for s in segs):
+        raise ValueError("merging pos / pair.pos / count needs every part's 'count'")
+    dev = segs[0]["labels"].device
+    n = len(segs)
+    nk = [int(s["labels"].numel()) for s in segs]
+    npos = [int(s["pos"].shape[0]) if opt & 2 else 0 for s in segs]
+    npair = [int(s["pair.pos"].shape[0]) if opt & 4 else 0 for s in segs]
+    U, N, P = sum(nk), sum(npos), sum(npair)
+    out = {"kmer": None, "pos": None, "pair.pos": None, "count": None}
+    if opt & 1:
+        out["kmer"] = torch.empty((U, k + 1), dtype=torch.uint8, device=dev)
+    if opt & 2:
+        out["pos"] = torch.empty((N, 2), dtype=torch.int32, device=dev)
+    if opt & 4:
+        out["pair.pos"] = torch.empty((P, 3), dtype=torch.int32, device=dev)
+    if opt & 8:
+        out["count"] = torch.empty((U,), dtype=torch.int32, device=dev)
+    keep = [s[f].contiguous() if s.get(f) is not None else None
+            for f in ("labels", "count", "kmer", "pos", "pair.pos") for s in segs]
+
+    def ptrs(j):
+        return (C.c_void_p * n)(*[t.data_ptr() if t is not None and t.numel() else None
+                                  for t in keep[j * n:(j + 1) * n]])
+
+    i64 = lambda v: (C.c_int64 * n)(*v)  # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().kmhg_merge_part_positions(
+            n, opt, k, i64(nk), i64(npos), i64(npair), ptrs(0), ptrs(1), ptrs(2), ptrs(3),
+            ptrs(4), _dptr(out["kmer"]), _dptr(out["pos"]), _dptr(out["pair.pos"]),
+            _dptr(out["count"]), _stream_ptr(stream)))
+    return out
+
 
 def merge_part_rows(rows: torch.Tensor, seg_base: list[int], tile_off: torch.Tensor, k: int,
                     w0: int = 0, stream=None) -> torch.Tensor:

@@ -640,3 +640,100 @@ def owner_query(engine, seq: torch.Tensor | None, k: int, dst: int = 0, src: int
                          ("merge", t4 - t3)):
             timings[name] = timings.get(name, 0.0) + dt
     return out
+
+
+# ------------------------------------------------------- kmer.pos over resident parts (no assembly)
+class HipPartReadEngine:
+    """Adapter: this rank's DevicePart (libkmhgpu) as a kmer.pos part engine."""
+
+    def __init__(self, part):
+        self.part = part
+        self.k, self.L, self.device = part.k, part.L, part.device
+
+    def part_info(self) -> dict:
+        return self.part.part_info()
+
+    def first_mask(self) -> torch.Tensor:
+        """ceil(L / 32) int32 words: the first positions of this part's k-mers."""
+        return self.part.first_mask()
+
+    def positions_part(self, mask: torch.Tensor, opt: int) -> dict:
+        """This part's rows under their labels in the whole index ('labels' + the opt bits)."""
+        return self.part.positions_part(mask, opt)
+
+    def merge(self, segs: list[dict], opt: int) -> dict:
+        from .device import merge_part_positions
+        return merge_part_positions(segs, opt, self.k)
+
+
+SEG_FIELDS = (("labels", 0, torch.int32, ()), ("count", 14, torch.int32, ()),
+              ("kmer", 1, torch.uint8, None), ("pos", 2, torch.int32, (2,)),
+              ("pair.pos", 4, torch.int32, (3,)))
+
+
+def owner_kmer_pos(part, opt: int, dst: int = 0, group=None, timings: dict | None = None):
+    """kmer.pos (src/kmer_hash.c:1054-1147) of an index that stays split in its owner-computes
+    parts, one per rank (src/kmer_reader.c:28-39): no assembly, the index never moves.  A k-mer's
+    row label is its rank by first occurrence, and every k-mer lives in one part, so: each rank
+    marks its k-mers' first positions in an L-bit mask; the masks are all-reduced (SUM of int32
+    words -- the bits are disjoint, so the sum is the union, on gloo and RCCL alike); each rank
+    reads its part out under the global labels (set bits at or before a first position); the
+    segments' sizes are all-gathered and the segments sent to `dst`, which places them
+    (kmhg_merge_part_positions).  `part`: a DevicePart, or any engine shaped like
+    HipPartReadEngine.  Returns on `dst` the dict DeviceIndex.positions(opt) returns ('kmer',
+    'pos', 'pair.pos', 'count'; first-occurrence order), None elsewhere.  No rank but `dst` holds
+    more than its part, the mask and its own segments.  `timings` receives 'mask', 'readout',
+    'gather' and 'merge' seconds."""
+    import time
+    eng = part if hasattr(part, "positions_part") and hasattr(part, "merge") \
+        else HipPartReadEngine(part)
+    world = dist.get_world_size(group)
+    rank = dist.get_rank(group)
+    dev = eng.device
+
+    def mark():
+        if timings is not None and dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+        return time.perf_counter()
+
+    part_info_all(eng, dev, group)           # a failed part build raises on every rank
+    t0 = mark()
+    mask = eng.first_mask()
+    if world > 1:
+        dist.all_reduce(mask, op=dist.ReduceOp.SUM, group=group)
+    t1 = mark()
+    part_opt = opt | (8 if opt & 6 else 0)   # the merge's row offsets are scans of the counts
+    seg = eng.positions_part(mask, part_opt)
+    del mask
+    t2 = mark()
+    fields = [(f, dt, tail) for f, bits, dt, tail in SEG_FIELDS if bits == 0 or part_opt & bits]
+    sizes = torch.tensor([seg["labels"].numel(), seg["pos"].shape[0] if opt & 2 else 0,
+                          seg["pair.pos"].shape[0] if opt & 4 else 0], dtype=torch.int64,
+                         device=dev)
+    got = [torch.zeros_like(sizes) for _ in range(world)]
+    dist.all_gather(got, sizes, group=group)
+    got = [g.tolist() for g in got]
+
+    def shape(f, tail, sz):
+        rows = sz[1] if f == "pos" else sz[2] if f == "pair.pos" else sz[0]
+        return (rows,) + ((eng.k + 1,) if tail is None else tail)
+
+    segs = None
+    if rank == dst:
+        segs = [seg if r == dst else
+                {f: torch.empty(shape(f, tail, got[r]), dtype=dt, device=dev)
+                 for f, dt, tail in fields} for r in range(world)]
+        p2p([("recv", segs[r][f], r) for r in range(world) if r != dst
+             for f, _, _ in fields if segs[r][f].numel()], group)
+    else:
+        p2p([("send", seg[f].contiguous(), dst) for f, _, _ in fields if seg[f].numel()], group)
+    t3 = mark()
+    out = None
+    if rank == dst:
+        out = eng.merge(segs, opt)
+    t4 = mark()
+    if timings is not None:
+        for name, dt in (("mask", t1 - t0), ("readout", t2 - t1), ("gather", t3 - t2),
+                         ("merge", t4 - t3)):
+            timings[name] = timings.get(name, 0.0) + dt
+    return out
