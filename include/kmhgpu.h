@@ -389,6 +389,12 @@ int kmhg_part_export(kmhg_index *idx, int64_t pos_base, void *d_table, void *d_s
  * fall back).  Writes the same-digit lane pairs found out of order and the pairs checked. */
 int kmhg_check_lds_lane_order(uint64_t *out_of_order, uint64_t *checked);
 
+/* Test build only (libkmhgpu_test.so; the product library counts nothing and writes zeros): the
+ * bucket kernel's one-batch position buckets since the last reset -- out[0] placed by home-slot
+ * counts, out[1] fallen back to the CAS pass for a repeated key, out[2] fallen back for a second
+ * wrap.  Waits for the device; reset != 0 zeroes the counters after reading them. */
+int kmhg_bucket_place_counters(uint64_t out[3], int reset);
+
 /* Per-kernel HIP-event timing (KMHG_TIMING=1 also enables it).  The report is JSON:
  * {"kernel": [launches, total_ms], ...}; events are recorded on the kernels' own stream. */
 int kmhg_timing_enable(int on);

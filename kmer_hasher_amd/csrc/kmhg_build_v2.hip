@@ -1014,6 +1014,11 @@ __device__ __forceinline__ bool stream_out_of_order(const uint32_t* __restrict__
 // registers of the thread that owns the slot for the write-out (slot q * TB + t), and `val`
 // becomes the inline position of a key seen once or the list cursor of a repeated key, tagged
 // VAL_MULTI so that pass B can tell them apart.
+// Pass A of a one-batch bucket of code-word keys is first tried by placement (home-slot counts,
+// one block scan, plain stores: no CAS, no counts pass; see "pass A by placement" below); a
+// bucket with a repeated key falls back to the CAS pass.  Measured at config 2, interleaved with
+// the parent on one device: headline 44.3 -> 48.2 Gbp/s.  The key-stream and
+// packed variants keep the CAS pass (the placement spills VGPRs there).
 // (Removed in round 4 after measurement, see DESIGN.md §5: one wave per 256-window bucket, a
 // 16-B-per-slot table, 8-wave workgroups, a one-atomic fingerprint insert, a sort-based bucket
 // build, and slot tags written by the build.)
@@ -1077,7 +1082,7 @@ k_v2_bucket_wg(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ p
                int32_t* __restrict__ positions, BucketStats* __restrict__ bstats,
                BuildMeta* __restrict__ meta, const uint32_t* __restrict__ code, int k,
                const uint32_t* __restrict__ n_ptr, uint32_t nw, uint8_t* __restrict__ TG,
-               uint32_t* __restrict__ rep) {
+               uint32_t* __restrict__ rep, uint32_t place, uint32_t* __restrict__ place_ctr) {
   static_assert(!(CK && COUNT_ONLY), "code-word keys belong to position builds");
   static_assert(!(TAGS && (CK || COUNT_ONLY)), "build-time tags: key-stream position builds");
   static_assert(!(AOS && (CK || COUNT_ONLY)), "packed streams carry keys and positions");
@@ -1171,11 +1176,210 @@ k_v2_bucket_wg(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ p
   cut(s0);
   STAMP_WG(b, 1);
   STAMP_WG_DRAIN(b, 6);
+  // Stream order of a one-batch bucket (multi-batch buckets check it with a neighbour load per
+  // element in load()): element (c, wave, lane) follows (c, wave, lane - 1) -- a DPP shift --
+  // and lane 0 follows lane 63 of the wave before (of row c - 1 for wave 0), exchanged through
+  // `edge` (order_write) and read after a barrier (order_read).  Both run after pass A, when the
+  // positions have long arrived, so the check makes no load wait earlier than it did.
+  const bool chk = !COUNT_ONLY && one_batch;
+  // (edge: row `wave` holds that wave's lane-63 positions, EW per row, written and read as
+  // pairs -- a handful of LDS instructions per wave: single-lane LDS instructions cost nearly a
+  // full one each in this LDS-bound kernel)
+  auto order_write = [&]() {
+    if (!chk) return;
+    if (threadIdx.x == 0) edge[EW * NW] = 0u;
+#pragma unroll
+    for (int c = 0; c < PER; ++c) {
+      // lane - 1's position by a DPP wave shift (a VALU move; __shfl_up is an LDS permute)
+      const uint32_t up = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)ps[c], 0x138 /* wave_shr:1 */,
+                                                                0xF, 0xF, false);
+      if (lane > 0 && elem(s0, c) < s1 && up >= ps[c]) disorder = true;
+    }
+    if (lane == 63) {
+#pragma unroll
+      for (int q = 0; q < PER; q += 2)
+        *reinterpret_cast<uint2*>(&edge[EW * wave + q]) = make_uint2(ps[q], q + 1 < PER ? ps[q + 1] : 0u);
+    }
+  };
+  auto order_read = [&]() {
+    if (!(chk && lane == 0)) return;
+    // lane 0 of wave w follows lane 63 of wave w - 1 (same row); wave 0 follows wave NW - 1
+    const uint32_t* row = edge + EW * (wave ? wave - 1 : NW - 1);
+    uint32_t pv[PER + 1];
+#pragma unroll
+    for (int q = 0; q < PER; q += 2) {
+      const uint2 v = *reinterpret_cast<const uint2*>(&row[q]);
+      pv[q] = v.x;
+      pv[q + 1] = v.y;
+    }
+    bool bad = false;
+#pragma unroll
+    for (int c = 0; c < PER; ++c) {
+      const uint32_t e = elem(s0, c);
+      const uint32_t prev = wave ? pv[c] : (c ? pv[c - 1] : 0u);   // wave 0: row c - 1
+      bad |= e > s0 && e < s1 && prev >= ps[c];
+    }
+    if (bad) edge[EW * NW] = 1u;             // read after the next barrier
+  };
+  // pass A by placement (one-batch position buckets): a linear-probing layout is fixed by how
+  // many keys have each home slot, so a bucket WITHOUT a repeated key -- every bucket of an
+  // i.i.d. sequence -- needs no find-or-insert: one u32 LDS add per element counts the keys of
+  // its home and ranks the element among them (r), a block scan over the homes turns the counts
+  // c(h) into the start of each home's group in the table that inserting the keys in home order
+  // would give, and each element stores its key at start + r.  With S the exclusive prefix sum
+  // of c and M(h) = max(0, max_{j <= h}(j - S(j))), home h's group starts at p(h) = S(h) + M(h)
+  // (p(h) = max(h, p(h-1) + c(h-1))).  The last cluster may run past the end by
+  // over = max(0, n + M(last) - CAPW) slots, which wrap into [0, over) and push the first
+  // cluster: p'(h) = S(h) + max(M(h), over).  The pushed layout reaches the end again only if
+  // over > M(last), that is n > CAPW -- a bucket the CAS pass reports as full.  A repeated key
+  // shows as two equal keys in one home's group (each element reads the group members of lower
+  // rank); such a bucket, or one with a crowded home (so no element reads more than CROWD - 1
+  // keys), clears the table and takes the CAS pass below, which stays the one place that
+  // handles repeats.  Homes are scanned thread-contiguous (V2_CAPW / TB per thread).
+  bool placed = false;                                // block-uniform
+  uint32_t n_real = 0;                                // placed: the bucket's keys but the sentinel
+  // (code-word keys only: the key-stream and packed variants, 8 elements per thread, spill 9-10
+  // VGPRs to scratch at 8 workgroups per CU with this path compiled in, so they keep the CAS pass)
+  if (CK && one_batch && place) {
+    constexpr uint32_t HB = V2_SLOT_BITS_WG, HM = (1u << HB) - 1u;
+    constexpr uint32_t HPT = V2_CAPW / TB;            // homes per thread
+    static_assert(HPT % 2 == 0 && (sizeof(W.key) % 8) == 0, "the scan reads counts as pairs");
+    static_assert(BATCH < (1u << (32 - HB - 1)), "(home, rank) packs into slot[c]");
+    constexpr uint32_t CROWD = 8, OFF = 2048;         // OFF >= BATCH keeps j + OFF - S(j) >= 0
+    static_assert(BATCH <= OFF && V2_CAPW + OFF < 0x10000u, "the scan's per-wave record: 16-bit fields");
+    bool rpt = false;
+#pragma unroll
+    for (int c = 0; c < PER; ++c) {
+      slot[c] = -1;
+      if (elem(s0, c) < s1) {
+        const uint64_t h = mix64(key[c]);
+        if (bucket_local(h, g) != b) disorder = true;
+        if (key[c] == EMPTY_KEY) {                    // the side slot holds one key
+          rpt |= atomicAdd(&W.val[V2_CAPW], 1u) != 0u;
+          slot[c] = (int)V2_CAPW;
+        } else {
+          const uint32_t home = local_home(h, V2_CAPW);
+          slot[c] = (int)(home | (atomicAdd(&W.val[home], 1u) << HB));
+        }
+      }
+    }
+    if (CK) {
+#pragma unroll
+      for (int c = 0; c < PER; ++c)
+        if (elem(s0, c) < s1 && ps[c] - 1u >= nw) disorder = true;
+    }
+    __syncthreads();
+    uint32_t cn[HPT];
+    uint2* vp = reinterpret_cast<uint2*>(&W.val[HPT * threadIdx.x]);
+#pragma unroll
+    for (uint32_t i = 0; i < HPT; i += 2) {
+      const uint2 v = vp[i / 2];
+      cn[i] = v.x;
+      cn[i + 1] = v.y;
+    }
+    uint32_t ls = 0, tmax = 0;
+    bool crowded = false;
+#pragma unroll
+    for (uint32_t i = 0; i < HPT; ++i) {              // j + OFF - (S(j) inside the thread)
+      tmax = max(tmax, HPT * threadIdx.x + i + OFF - ls);
+      ls += cn[i];
+      crowded |= cn[i] > CROWD;
+    }
+    const uint32_t inc = wave_incl_scan_u32(ls);      // S inside the wave
+    const uint32_t wex = inc - ls;
+    const uint32_t minc = wave_incl_max(tmax - wex);  // j + OFF - (S(j) inside the wave)
+    const uint32_t mex = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)minc, 0x138 /* wave_shr:1 */,
+                                                               0xF, 0xF, false);
+    const bool wcrowd = __ballot(crowded) != 0;
+    if (lane == 63) sh[wave] = (uint64_t)inc | ((uint64_t)minc << 16) | ((uint64_t)wcrowd << 32);
+    __syncthreads();
+    int wbase = 0, Mw = 0, Mall = 0, ntot = 0;
+    bool crowd = false;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      const uint64_t x = sh[w];
+      const int G = (int)((uint32_t)(x >> 16) & 0xFFFFu) - (int)OFF - ntot;
+      if (w < wave) {
+        Mw = max(Mw, G);
+        wbase = ntot + (int)((uint32_t)x & 0xFFFFu);
+      }
+      Mall = max(Mall, G);
+      ntot += (int)((uint32_t)x & 0xFFFFu);
+      crowd |= (x >> 32) != 0;
+    }
+    n_real = (uint32_t)__builtin_amdgcn_readfirstlane(ntot);
+    int which = crowd ? 1 : 2;                        // fallback: a repeat / a second wrap
+    if (!crowd && n_real <= V2_CAPW) {                // block-uniform
+      which = 1;
+      const int over = max(0, ntot + Mall - (int)V2_CAPW);
+      int m = max(Mw, (int)mex - (int)OFF - wbase);   // (lane 0: mex = 0, below every term)
+      int sx = wbase + (int)wex;
+#pragma unroll
+      for (uint32_t i = 0; i < HPT; ++i) {
+        m = max(m, (int)(HPT * threadIdx.x + i) - sx);
+        const uint32_t c = cn[i];
+        cn[i] = (uint32_t)(sx + max(m, over));        // p'(h) in [0, 2 CAPW)
+        sx += (int)c;
+      }
+#pragma unroll
+      for (uint32_t i = 0; i < HPT; i += 2) vp[i / 2] = make_uint2(cn[i], cn[i + 1]);
+      __syncthreads();
+#pragma unroll
+      for (int c = 0; c < PER; ++c) {
+        if (elem(s0, c) < s1 && slot[c] != (int)V2_CAPW) {
+          const uint32_t r = (uint32_t)slot[c] >> HB;
+          uint32_t j = W.val[(uint32_t)slot[c] & HM] + r;
+          if (j >= V2_CAPW) j -= V2_CAPW;
+          W.key[j] = key[c];
+          slot[c] = (int)(j | (r << HB));
+        }
+      }
+      order_write();
+      __syncthreads();
+#pragma unroll
+      for (int c = 0; c < PER; ++c) {
+        if (elem(s0, c) < s1) {
+          const uint32_t r = (uint32_t)slot[c] >> HB, j = (uint32_t)slot[c] & HM;
+          uint32_t q = j >= r ? j - r : j + V2_CAPW - r;   // the group's first slot
+          for (uint32_t i = 0; i < r; ++i) {          // r < CROWD; addresses known up front
+            rpt |= W.key[q] == key[c];
+            if (++q == V2_CAPW) q = 0;
+          }
+          slot[c] = (int)j;
+        }
+      }
+      // one reduction for both verdicts: bit 0 a repeated key, bit 1 a stream error
+      const uint32_t wf = (__ballot(rpt) ? 1u : 0u) | (__ballot(ovf || disorder) ? 2u : 0u);
+      if (lane == 0) red[1][wave] = wf;
+      __syncthreads();
+      uint32_t bf = 0;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) bf |= red[1][w];
+      if (bf & 2u) {
+        if (threadIdx.x == 0) atomicOr(&meta->overflow, 1u);
+        return;
+      }
+      if (!(bf & 1u)) {
+        placed = true;
+        which = 0;
+        order_read();
+      }
+    }
+    if (!placed) {                                    // nobody reads the table past the barriers above
+      for (uint32_t j = threadIdx.x; j <= V2_CAPW; j += TB) {
+        W.key[j] = EMPTY_KEY;
+        W.val[j] = 0u;
+      }
+      __syncthreads();
+    }
+    // test build only: buckets placed / fallen back for a repeat / for a second wrap
+    if (place_ctr && threadIdx.x == 0) atomicAdd(&place_ctr[which], 1u);
+  }
   // pass A: distinct keys + counts (CAS on a table shared by the four waves).  (Measured round
   // 3, A/B in one run: letting the claiming occurrence skip the count add -- counts pass adds 1
   // per occupied slot -- made the kernel 100 -> 142 us, as in round 2; and issuing the first
   // CAS of all 8 elements of a lane back to back before resolving any, 98 -> 112 us.)
-  for (uint32_t i0 = s0; i0 < s1; i0 += BATCH) {
+  for (uint32_t i0 = s0; i0 < (placed ? s0 : s1); i0 += BATCH) {
     if (i0 != s0) { load(i0); cut(i0); }
 #pragma unroll
     for (int c = 0; c < PER; ++c) {
@@ -1196,59 +1400,24 @@ k_v2_bucket_wg(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ p
         if (elem(i0, c) < s1 && ps[c] - 1u >= nw) disorder = true;
     }
   }
-  // Stream order of a one-batch bucket (multi-batch buckets check it with a neighbour load per
-  // element in load()): element (c, wave, lane) follows (c, wave, lane - 1) -- a DPP shift --
-  // and lane 0 follows lane 63 of the wave before (of row c - 1 for wave 0), exchanged through
-  // `edge` and read after the barrier below.  Here, after pass A, the positions have long
-  // arrived, so the check makes no load wait earlier than it did.
-  const bool chk = !COUNT_ONLY && one_batch;
-  // (edge: row `wave` holds that wave's lane-63 positions, EW per row, written and read as
-  // pairs -- a handful of LDS instructions per wave: single-lane LDS instructions cost nearly a
-  // full one each in this LDS-bound kernel)
-  if (chk) {
-    if (threadIdx.x == 0) edge[EW * NW] = 0u;
-#pragma unroll
-    for (int c = 0; c < PER; ++c) {
-      // lane - 1's position by a DPP wave shift (a VALU move; __shfl_up is an LDS permute)
-      const uint32_t up = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)ps[c], 0x138 /* wave_shr:1 */,
-                                                                0xF, 0xF, false);
-      if (lane > 0 && elem(s0, c) < s1 && up >= ps[c]) disorder = true;
+  if (!placed) {
+    order_write();
+    if (__syncthreads_or(ovf || disorder)) {
+      if (threadIdx.x == 0) atomicOr(&meta->overflow, 1u);
+      return;
     }
-    if (lane == 63) {
-#pragma unroll
-      for (int q = 0; q < PER; q += 2)
-        *reinterpret_cast<uint2*>(&edge[EW * wave + q]) = make_uint2(ps[q], q + 1 < PER ? ps[q + 1] : 0u);
-    }
-  }
-  if (__syncthreads_or(ovf || disorder)) {
-    if (threadIdx.x == 0) atomicOr(&meta->overflow, 1u);
-    return;
-  }
-  if (chk && lane == 0) {
-    // lane 0 of wave w follows lane 63 of wave w - 1 (same row); wave 0 follows wave NW - 1
-    const uint32_t* row = edge + EW * (wave ? wave - 1 : NW - 1);
-    uint32_t pv[PER + 1];
-#pragma unroll
-    for (int q = 0; q < PER; q += 2) {
-      const uint2 v = *reinterpret_cast<const uint2*>(&row[q]);
-      pv[q] = v.x;
-      pv[q + 1] = v.y;
-    }
-    bool bad = false;
-#pragma unroll
-    for (int c = 0; c < PER; ++c) {
-      const uint32_t e = elem(s0, c);
-      const uint32_t prev = wave ? pv[c] : (c ? pv[c - 1] : 0u);   // wave 0: row c - 1
-      bad |= e > s0 && e < s1 && prev >= ps[c];
-    }
-    if (bad) edge[EW * NW] = 1u;             // read after the counts pass's barrier
+    order_read();                            // its verdict: read after the counts pass's barrier
   }
   STAMP_WG(b, 2);
   // counts: thread t owns slots t, t + TB, ... (lane-contiguous: conflict-free LDS; thread-
   // contiguous runs of 6 slots ran 0.104 ms against 0.096 for the kernel)
   constexpr uint32_t SPT = (V2_CAPW + 1 + TB - 1) / TB;
+  // (a placed bucket has no counts pass: every occupied slot counts 1, taken from the key at
+  // the write-out)
   uint32_t cnt[SPT];
   uint32_t cs = 0;
+  bool has_multi = false;
+  if (!placed) {
 #ifndef KMHG_NO_LEAN_COUNTS
   // The bucket's distinct keys by ballots (no cross-lane shuffles: each __shfl_xor is an LDS
   // permute, in a kernel bound by its LDS instructions); the count maximum and the pairs only
@@ -1265,7 +1434,7 @@ k_v2_bucket_wg(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ p
     occ_w += (uint32_t)__popcll(__ballot(c != 0));
   }
   if (lane == 0) red[0][wave] = occ_w;
-  const bool has_multi = __syncthreads_or(multi);
+  has_multi = __syncthreads_or(multi);
   if (has_multi) {                         // block-uniform
     uint32_t mx = 0;
     uint64_t pairs = 0;
@@ -1307,11 +1476,12 @@ k_v2_bucket_wg(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ p
     red[1][wave] = mx;
     sh[NW + wave] = pairs;                 // sh[NW..2NW): the block scan below uses sh[0..NW)
   }
-  const bool has_multi = __syncthreads_or(mx > 1);
+  has_multi = __syncthreads_or(mx > 1);
 #endif
   if (chk && edge[EW * NW]) {                // stream out of order at a wave / row boundary
     if (threadIdx.x == 0) atomicOr(&meta->overflow, 1u);
     return;
+  }
   }
   // list offsets (only repeated keys have lists): any slot order gives each key a contiguous
   // range of [s0, s1), here slot q * TB + t in (t, q) order
@@ -1332,6 +1502,11 @@ k_v2_bucket_wg(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ p
     st.n_kmers = 0;
     st.max_count = 0;
     st.n_pairs = 0;
+    if (placed) {                          // no repeated key: every window is a key
+      st.n_kmers = s1 - s0;
+      st.max_count = s1 > s0 ? 1u : 0u;
+      bstats[b] = st;
+    } else {
 #pragma unroll
     for (int w = 0; w < NW; ++w) st.n_kmers += red[0][w];
 #ifndef KMHG_NO_LEAN_COUNTS
@@ -1347,6 +1522,7 @@ k_v2_bucket_wg(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ p
       }
     }
     bstats[b] = st;
+    }
   }
   // pass B: keys seen once keep their position inline (val); repeated keys are ranked in
   // position order, the waves taking turns so that wave w follows waves < w
@@ -1392,6 +1568,10 @@ k_v2_bucket_wg(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ p
     }
   }
   __syncthreads();
+  if (placed && chk && edge[EW * NW]) {      // (placed: order_read's verdict, behind pass B's barrier)
+    if (threadIdx.x == 0) atomicOr(&meta->overflow, 1u);
+    return;
+  }
   STAMP_WG(b, 4);
   // the bucket's sub-table, coalesced 16-B slots, counts from the registers of the slot's owner
   Slot* Tb = T + (uint64_t)b * V2_CAPW;
@@ -1409,15 +1589,17 @@ k_v2_bucket_wg(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ p
     const uint32_t j = q * TB + threadIdx.x;
     if (j < V2_CAPW) {
       const uint64_t kk = W.key[j];
-      const uint32_t aux = COUNT_ONLY ? 0u : (W.val[j] & ~VAL_MULTI);
+      // placed: val holds the group starts where no key landed
+      const uint32_t cq = placed ? (kk != EMPTY_KEY ? 1u : 0u) : cnt[q];
+      const uint32_t aux = COUNT_ONLY ? 0u : (placed && kk == EMPTY_KEY) ? 0u : (W.val[j] & ~VAL_MULTI);
       if (CK && NT_TABLE) {
         // code-word keys: the table streams past the L2 (nontemporal), which keeps the code
         // words every bucket gathers from resident there
         typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-        const u32x4 sv = {(uint32_t)kk, (uint32_t)(kk >> 32), cnt[q], aux};
+        const u32x4 sv = {(uint32_t)kk, (uint32_t)(kk >> 32), cq, aux};
         __builtin_nontemporal_store(sv, reinterpret_cast<u32x4*>(&Tb[j]));
       } else {
-        *reinterpret_cast<uint4*>(&Tb[j]) = make_uint4((uint32_t)kk, (uint32_t)(kk >> 32), cnt[q], aux);
+        *reinterpret_cast<uint4*>(&Tb[j]) = make_uint4((uint32_t)kk, (uint32_t)(kk >> 32), cq, aux);
       }
       if (TAGS)      // one byte per slot: 64 consecutive bytes per wave and row q
         TG[(uint64_t)b * V2_CAPW + j] = kk == EMPTY_KEY ? (uint8_t)0 : slot_tag(mix64(kk));
@@ -1425,7 +1607,8 @@ k_v2_bucket_wg(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ p
   }
 #endif
   if (threadIdx.x == 0 && side_bucket(b, g)) {
-    const uint2 c = make_uint2(cnt[V2_CAPW / TB], COUNT_ONLY ? 0u : (W.val[V2_CAPW] & ~VAL_MULTI));
+    // (placed: the windows that are not among the table's keys hold the sentinel key)
+    const uint2 c = make_uint2(placed ? s1 - s0 - n_real : cnt[V2_CAPW / TB], COUNT_ONLY ? 0u : (W.val[V2_CAPW] & ~VAL_MULTI));
     *reinterpret_cast<uint4*>(&T[side_slot(g)]) = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, c.x, c.y);
   }
   STAMP_WG(b, 5);
@@ -1787,14 +1970,15 @@ void launch_v2_scatter_nopos(const uint64_t* kin, const uint32_t* n_ptr, Geom g,
 void launch_v2_bucket_wg(const uint64_t* keys, const uint32_t* pos, const uint32_t* start, Geom g,
                          Slot* T, int32_t* positions, BucketStats* bstats, BuildMeta* meta,
                          bool count_only, hipStream_t s, const uint32_t* n_ptr, uint32_t nw,
-                         const uint32_t* code, int k, bool aos, uint8_t* TG, uint32_t* rep) {
+                         const uint32_t* code, int k, bool aos, uint8_t* TG, uint32_t* rep,
+                         bool place, uint32_t* place_ctr) {
   const bool ballot = ballot_ranks();
   const bool tags = TG != nullptr && !count_only && !code;
   const dim3 gr(g.nb), bl(BLOCK);
 #define KMHG_BUCKET(CO, CKK, BAL, AO, TG_)                                                     \
   hipLaunchKernelGGL((k_v2_bucket_wg<CO, CKK, BAL, AO, TG_>), gr, bl, 0, s, keys, pos, start, g, \
                      T, positions, bstats, meta, CKK ? code : nullptr, CKK ? k : 0, n_ptr, nw,   \
-                     TG, rep)
+                     TG, rep, place ? 1u : 0u, place_ctr)
   if (aos && tags)
     { if (ballot) KMHG_BUCKET(false, false, true, true, true); else KMHG_BUCKET(false, false, false, true, true); }
   else if (aos)

@@ -42,7 +42,8 @@
 // KMHG_FUSE_BOUNDS, KMHG_TEST_BALLOT, KMHG_QUERY_TAGS, KMHG_QUERY_DIAG, KMHG_DIAG_CODES,
 // KMHG_COUNT_TABLE, KMHG_COUNT_WALK, KMHG_CO_SPREAD, KMHG_CO_GLOBAL, KMHG_PART_COMPACT,
 // KMHG_ROW_ORDER_SORT, KMHG_PACK8, KMHG_NB_ROUND, KMHG_SLICE_POISON, KMHG_TEST_REPLICA,
-// KMHG_DIGIT_STREAM, KMHG_DS_BID, KMHG_DS_U8, KMHG_DS_PACK, KMHG_BUILD_TAGS), which choose
+// KMHG_DIGIT_STREAM, KMHG_DS_BID, KMHG_DS_U8, KMHG_DS_PACK, KMHG_BUILD_TAGS,
+// KMHG_BUCKET_PLACE), which choose
 // between equivalent paths and change no result; fault injection (KMHG_TEST_DISORDER); and the
 // A/B-only switches (KMHG_D2H, KMHG_D2H_HUGE, KMHG_HOST_RUNS, KMHG_HOST_PAIRS, KMHG_HOST_POOL,
 // KMHG_COUNT_BID, KMHG_RK_CAP, KMHG_POOL_DEPTH, KMHG_POOL_BESTFIT, KMHG_POOL_TRACE).
@@ -1142,6 +1143,33 @@ int co_spread_for(double distinct, uint64_t total) {
 // (co_spread_for), read back while the radix passes run.
 // skip_empty (count-only key streams of k <= 31): EMPTY_KEY entries are padding, not keys --
 // the first pass drops them, and the valid count comes from its scan.
+// Pass A by placement in the bucket kernel (kmhg_build_v2.hip): on unless KMHG_BUCKET_PLACE=0
+// (test build) forces the CAS pass everywhere.  The test build also counts, per device buffer
+// made once and kept, the buckets placed / fallen back for a repeated key / fallen back for a
+// second wrap (kmhg_bucket_place_counters); the product library passes no counters.
+bool bucket_place_on() {
+  const char* e = test_build_knob("KMHG_BUCKET_PLACE");
+  return !(e && e[0] == '0');
+}
+#ifdef KMHG_TEST_BUILD
+static std::mutex g_place_mu;
+static uint32_t* g_place_ctr = nullptr;              // 3 x u32 on g_place_dev
+static int g_place_dev = -1;
+uint32_t* bucket_place_counters() {
+  std::lock_guard<std::mutex> lk(g_place_mu);
+  int dev = 0;
+  HIPC(hipGetDevice(&dev));
+  if (!g_place_ctr) {
+    HIPC(hipMalloc(&g_place_ctr, 3 * sizeof(uint32_t)));
+    HIPC(hipMemset(g_place_ctr, 0, 3 * sizeof(uint32_t)));
+    g_place_dev = dev;
+  }
+  return dev == g_place_dev ? g_place_ctr : nullptr;
+}
+#else
+uint32_t* bucket_place_counters() { return nullptr; }
+#endif
+
 kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t s,
                             const uint64_t* d_keys = nullptr, int64_t n_keys = 0,
                             bool count_only = false, int co_spread = 1, bool skip_empty = false,
@@ -1627,7 +1655,7 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
   LAUNCH("k_v2_bucket_wg", s,
          launch_v2_bucket_wg(kin, pin, start.p, gb, idx->table.p, idx->positions.p, idx->bstats.p,
                              meta, no_pos, s, n_valid, (uint32_t)Nw, bid ? db.code : nullptr, k,
-                             aos, tg, rep));
+                             aos, tg, rep, bucket_place_on(), bucket_place_counters()));
   idx->tags_built = tg != nullptr;
   LAUNCH("k_v2_stats", s, launch_v2_stats(idx->bstats.p, gb.nb, n_valid, meta, idx->rec.meta, s));
   idx->bstats_nb = gb.nb;
@@ -4099,6 +4127,29 @@ int kmhg_timing_report(char* buf, size_t cap) {
     js += "}";
     if (!buf || cap < js.size() + 1) fail(KMHG_EINVAL, "timing report buffer too small");
     memcpy(buf, js.c_str(), js.size() + 1);
+  });
+}
+
+int kmhg_bucket_place_counters(uint64_t out[3], int reset) {
+  return guarded([&] {
+    if (!out) fail(KMHG_EINVAL, "null result pointer");
+    out[0] = out[1] = out[2] = 0;
+#ifdef KMHG_TEST_BUILD
+    std::lock_guard<std::mutex> lk(g_place_mu);
+    if (!g_place_ctr) return;
+    int dev = 0;
+    HIPC(hipGetDevice(&dev));
+    HIPC(hipSetDevice(g_place_dev));
+    uint32_t h[3] = {0, 0, 0};
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(h, g_place_ctr, sizeof(h), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && reset) e = hipMemset(g_place_ctr, 0, sizeof(h));
+    (void)hipSetDevice(dev);
+    hip_check(e, "bucket placement counters");
+    for (int i = 0; i < 3; ++i) out[i] = h[i];
+#else
+    (void)reset;
+#endif
   });
 }
 

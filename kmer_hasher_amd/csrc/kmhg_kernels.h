@@ -324,7 +324,11 @@ void launch_v2_bucket_wg(const uint64_t* keys, const uint32_t* pos, const uint32
                          Slot* T, int32_t* positions, BucketStats* bstats, BuildMeta* meta,
                          bool count_only, hipStream_t s, const uint32_t* n_ptr, uint32_t nw,
                          const uint32_t* code = nullptr, int k = 0, bool aos = false,
-                         uint8_t* TG = nullptr, uint32_t* rep = nullptr);
+                         uint8_t* TG = nullptr, uint32_t* rep = nullptr, bool place = true,
+                         uint32_t* place_ctr = nullptr);
+// place: one-batch position buckets try pass A by placement (home-slot counts + a scan) before
+// the CAS pass; place_ctr (test build, else null): three device counters -- buckets placed,
+// fallen back to the CAS pass for a repeated key, fallen back for a second wrap
 // TG / rep (key-stream position builds): the build also writes the diagonal path's slot tags and
 // sets the repeated keys' window bits in rep (zeroed by the caller); the first query then runs
 // launch_diag_valid(..., multi_in = true) instead of launch_diag_prep
