@@ -395,6 +395,12 @@ int kmhg_check_lds_lane_order(uint64_t *out_of_order, uint64_t *checked);
  * wrap.  Waits for the device; reset != 0 zeroes the counters after reading them. */
 int kmhg_bucket_place_counters(uint64_t out[3], int reset);
 
+/* Test build only (the product library writes zeros): bucket-id builds started since the last
+ * reset -- out[0] with the packed middle stream (one digit-pos word per window between the two
+ * radix passes), out[1] every other bucket-id build (bucket id and position arrays).  reset != 0
+ * zeroes the counters after reading them. */
+int kmhg_bid_pack_counters(uint64_t out[2], int reset);
+
 /* Per-kernel HIP-event timing (KMHG_TIMING=1 also enables it).  The report is JSON:
  * {"kernel": [launches, total_ms], ...}; events are recorded on the kernels' own stream. */
 int kmhg_timing_enable(int on);

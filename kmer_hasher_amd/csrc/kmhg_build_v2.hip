@@ -85,6 +85,13 @@ __device__ __forceinline__ uint32_t digit_of_b(uint32_t b, const Digit& D) {
   const uint32_t q = div_magic(b, D.mdiv);
   return q - div_magic(q, D.mR) * D.R;
 }
+// ... and the quotient above it, floor(b / (div R)): in a two-pass plan (b < R^2) the next pass's
+// digit, for free (the digit-pos word of the packed bucket-id stream)
+__device__ __forceinline__ uint32_t digit_of_b_hi(uint32_t b, const Digit& D, uint32_t& hi) {
+  const uint32_t q = div_magic(b, D.mdiv);
+  hi = div_magic(q, D.mR);
+  return q - hi * D.R;
+}
 __device__ __forceinline__ uint32_t digit_of_h(uint64_t h, const Geom& g, const Digit& D) {
   return digit_of_b(bucket_local(h, g), D);
 }
@@ -365,7 +372,8 @@ k_v2_hist(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ n_ptr,
 // streams), so whole-tile loads stay inside it.
 // MODE: 0 = u64 keys, 1 = u32 bucket ids, 2 = packed 12-B {key lo, key hi, pos} elements (the
 // position builds' key streams), 3 = packed 8-B elements (Pack8: the key is e >> sh), 4 = the
-// previous pass's digit stream (u16 digits, DS in V_scatter), 5 = the same in u8 digits.
+// previous pass's digit stream (u16 digits, DS in V_scatter), 5 = the same in u8 digits, 6 =
+// digit-pos words (the packed bucket-id stream, V_scatter BM 8): the digit is w >> 24.
 template <int MODE>
 __global__ void __launch_bounds__(BLOCK)
 k_v2_histp(const uint64_t* __restrict__ in, const uint32_t* __restrict__ n_ptr, Geom g, Digit D,
@@ -383,7 +391,7 @@ k_v2_histp(const uint64_t* __restrict__ in, const uint32_t* __restrict__ n_ptr, 
   if (save_col0 && tile_at(0) == 0)
     for (uint32_t d = threadIdx.x; d < R; d += BLOCK) save_col0[d] = hist[(size_t)d * ntiles];
   for (uint32_t d = threadIdx.x; d < R; d += BLOCK) lh[d] = 0;
-  constexpr bool BID = MODE == 1;
+  constexpr bool BID = MODE == 1 || MODE == 6;
   if constexpr (MODE == 2) {
     // packed 12-B elements: thread t takes elements t + 256 j of the tile (j < 8), so every
     // load instruction reads 768 contiguous bytes per wave (one element per lane, dwordx3); a
@@ -419,7 +427,7 @@ k_v2_histp(const uint64_t* __restrict__ in, const uint32_t* __restrict__ n_ptr, 
     return;
   }
   constexpr bool DIG = MODE == 4, DIG8 = MODE == 5;
-  constexpr int NV = DIG || DIG8 ? 1 : MODE == 1 ? 2 : 4;   // 16-B loads per thread per tile
+  constexpr int NV = DIG || DIG8 ? 1 : BID ? 2 : 4;   // 16-B loads per thread per tile
   uint4 nx[NV];
   auto prefetch = [&](uint32_t tile) {
     if constexpr (DIG8) {                              // 8 u8 digits: one 8-B load
@@ -455,7 +463,7 @@ k_v2_histp(const uint64_t* __restrict__ in, const uint32_t* __restrict__ n_ptr, 
         } else if (BID) {
           const uint4 w = cur[j >> 2];
           const uint32_t id = (j & 3) == 0 ? w.x : (j & 3) == 1 ? w.y : (j & 3) == 2 ? w.z : w.w;
-          dg = digit_of_b(id, D);
+          dg = MODE == 6 ? id >> 24 : digit_of_b(id, D);
         } else {
           const uint4 w = cur[j >> 1];
           const uint64_t e = (j & 1) ? (((uint64_t)w.w << 32) | w.z) : (((uint64_t)w.y << 32) | w.x);
@@ -570,16 +578,18 @@ k_v2_hll_final(const uint32_t* __restrict__ part, uint32_t n_part, double* __res
 // schedule with per-chunk histograms, -10 %: each workgroup's open digit-run heads overflow the
 // L2.)
 constexpr int SC_NWV = 4;                       // waves per scatter workgroup
-template <class KT>
+// KEY / POS / STG: the mode stages keys / positions / the tile's chars (the digit-pos modes, BM 8
+// and 9, drop what they never touch: 33.4 -> 24.1 KB per workgroup)
+template <class KT, bool KEY = true, bool POS = true, bool STG = true>
 struct ScatterLDS {
   static constexpr uint32_t MAXR = V2_MAXR_IL;
   uint32_t wc[SC_NWV][MAXR];   // per-wave digit counts -> per-wave tile-local cursors
   uint32_t tstart[MAXR];       // tile-local start of each digit
   uint32_t gbase[MAXR];        // global start of each digit for this tile (scanned histogram)
-  KT skey[PTILE];
-  uint32_t spos[PTILE];
+  KT skey[KEY ? PTILE : 1];
+  uint32_t spos[POS ? PTILE : 1];
   uint32_t sdst[PTILE];
-  PStage st;
+  typename std::conditional<STG, PStage, uint32_t>::type st;
 };
 
 // Exclusive scan over the NWV * 64 threads of a block (one value per thread), lds >= NWV u64.
@@ -629,6 +639,13 @@ __device__ __forceinline__ uint32_t block_excl_scan_n32(uint32_t v, uint64_t* ld
 // code words by the bucket kernel; 2 = the last pass: (bucket id, pos) in, positions only out.
 // kin / kout then point at u32 arrays.  8 B per element instead of 12 through the middle passes,
 // 4 B out of the last.
+// 8 / 9 = the two passes of a two-pass bucket-id build at a radix <= 256 and < 2^24 windows with
+// ONE u32 per window between them, the digit-pos word (pass-1 digit << 24) | pos: 8 = pass 0
+// (KEYS0: V_hist0's ids in, positions implicit) writes the words to kout, nothing to pout; 9 =
+// the last pass reads them (digit = w >> 24, no division) and writes w & 0xFFFFFF to pout.  The
+// pass-0 digit is implied by where the word lies, and the fused bucket-start level reads only
+// this pass's digit too.  4 B per window through the middle instead of 8, one run per tile and
+// digit instead of two.
 // 3 = packed (key, pos) elements, 12 B each in kin / kout ({key lo, key hi, pos}; pin / pout
 // unused): a tile's digit run leaves as ONE contiguous piece instead of an 8 c-byte piece of
 // keys and a 4 c-byte piece of positions in two arrays; 4 = (key, pos) arrays in, packed out
@@ -651,14 +668,19 @@ k_v2_scatter(const uint8_t* __restrict__ seq, int64_t L, int k, int64_t Nw,
              const uint32_t* __restrict__ hist, uint32_t ntiles,
              uint64_t* __restrict__ kout, uint32_t* __restrict__ pout, uint32_t pad,
              int skip_empty, BoundsFuse bf, Pack8 pk, DigitOut dso) {
-  constexpr bool BIDS = BM == 1 || BM == 2;      // bucket-id streams
+  constexpr bool DPW0 = BM == 8, DPW1 = BM == 9;  // digit-pos words out / in
+  constexpr bool BIDS = BM == 1 || BM == 2 || DPW0 || DPW1;      // bucket-id streams
+  constexpr bool KEYOUT = BM != 2 && !DPW1;       // the pass writes kout
+  constexpr bool POSOUT = !NOPOS && BM != 6 && !DPW0;   // ... pout (packed streams: see AOS)
   constexpr bool AOS = BM == 3 || BM == 4 || BM == 7;   // packed 12-B (key, pos) elements out
   constexpr bool AIN = BM == 3;                   // ... and in
   constexpr bool P8OUT = BM == 6;                 // packed 8-B (key << sh | window) out
   constexpr bool P8IN = BM == 7;                  // ... in
   using KT = typename std::conditional<BIDS, uint32_t, uint64_t>::type;
-  using SL = ScatterLDS<KT>;
-  static_assert(!DS || BM != 2, "the last bucket-id pass has no next pass");
+  using SL = ScatterLDS<KT, !DPW1, !DPW0, !(DPW0 || DPW1)>;
+  static_assert(!DS || (BM != 2 && !DPW0 && !DPW1), "no digit stream out of these passes");
+  static_assert(!DPW0 || (KEYS0 && !FROM_SEQ), "the digit-pos words start from V_hist0's ids");
+  static_assert(!DPW1 || (!KEYS0 && !FROM_SEQ), "the digit-pos words' second pass");
   static_assert(BM == 0 || !NOPOS, "bucket-id and packed streams carry positions");
   static_assert(!(AOS && KEYS0), "packed streams start from the sequence");
   // KEYS0 with BM: the first pass over V_hist0's per-window bucket ids (~0: not indexed)
@@ -709,7 +731,7 @@ k_v2_scatter(const uint8_t* __restrict__ seq, int64_t L, int k, int64_t Nw,
   auto prefetch = [&](uint32_t tv) {
     const uint64_t t0 = (uint64_t)tv * PTILE;
     load_bases(tv);
-    if (FROM_SEQ) {
+    if constexpr (FROM_SEQ) {
       stage_load<PSTAGE_W16, true>(nchars, seq, L, (int64_t)t0 - HALO, true);
     } else {
 #pragma unroll
@@ -726,7 +748,7 @@ k_v2_scatter(const uint8_t* __restrict__ seq, int64_t L, int k, int64_t Nw,
           npos[cc] = 0u;
         } else {
           nkey[cc] = kinT[e];
-          npos[cc] = NOPOS ? 0u : pin[e];
+          npos[cc] = NOPOS || DPW1 ? 0u : pin[e];
         }
       }
     }
@@ -740,8 +762,8 @@ k_v2_scatter(const uint8_t* __restrict__ seq, int64_t L, int k, int64_t Nw,
     if (AOS) {
       reinterpret_cast<uint3*>(kout)[pad + threadIdx.x] = make_uint3(0u, 0u, 0u);
     } else {
-      if (BM != 2) koutT[pad + threadIdx.x] = 0;
-      if (!NOPOS && !P8OUT) pout[pad + threadIdx.x] = 0;
+      if (KEYOUT) koutT[pad + threadIdx.x] = 0;
+      if (POSOUT) pout[pad + threadIdx.x] = 0;
     }
     if constexpr (DS) {
       if (dso.out8) dso.out8[pad + threadIdx.x] = 0;
@@ -757,7 +779,7 @@ k_v2_scatter(const uint8_t* __restrict__ seq, int64_t L, int k, int64_t Nw,
     uint32_t cursor[DPT];
 #pragma unroll
     for (int q = 0; q < DPT; ++q) cursor[q] = ngb[q];
-    if (FROM_SEQ) {
+    if constexpr (FROM_SEQ) {
       stage_pack(nchars, S.st);
     } else {
 #pragma unroll
@@ -773,7 +795,7 @@ k_v2_scatter(const uint8_t* __restrict__ seq, int64_t L, int k, int64_t Nw,
     for (int c = 0; c < PER; ++c) {
       const uint32_t w = wbase + (uint32_t)c * 64 + lane;     // element index inside the tile
       const uint64_t e = tile0 + w;
-      if (FROM_SEQ) {
+      if constexpr (FROM_SEQ) {
         uint64_t kk = 0;
         act[c] = e < n && window_key(S.st, HALO + (int)w, (int64_t)e, L, k, kk);
         ps[c] = (uint32_t)(e + 1);
@@ -798,6 +820,20 @@ k_v2_scatter(const uint8_t* __restrict__ seq, int64_t L, int k, int64_t Nw,
         }
         ps[c] = (uint32_t)((((uint64_t)lo << pk.sh) | ((uint64_t)key[c] & ((1ull << pk.sh) - 1ull))) + 1);
         key[c] = (KT)kk;
+      } else if (DPW0) {
+        // both digits from one division: this pass's, and the quotient (< R <= 256: two passes)
+        // that is the next pass's, packed over the position (< 2^24)
+        const uint32_t id = (uint32_t)key[c];
+        uint32_t hi;
+        const uint32_t lo = digit_of_b_hi(id, D, hi);
+        act[c] = e < n && id != ~0u;
+        dg[c] = act[c] ? lo : 0;
+        key[c] = (KT)((hi << 24) | ps[c]);
+      } else if (DPW1) {
+        const uint32_t w = (uint32_t)key[c];
+        act[c] = e < n;
+        dg[c] = act[c] ? w >> 24 : 0;
+        ps[c] = w & 0xFFFFFFu;
       } else if (BIDS) {
         act[c] = e < n && !(KEYS0 && (uint32_t)key[c] == ~0u);
         dg[c] = act[c] ? digit_of_b((uint32_t)key[c], D) : 0;
@@ -866,8 +902,8 @@ k_v2_scatter(const uint8_t* __restrict__ seq, int64_t L, int k, int64_t Nw,
         if (act[c]) {
           const uint32_t d = dg[c] & 0xFFFFu;
           const uint32_t ld = S.wc[wave][d] + (dg[c] >> 16);
-          if (BM != 2) S.skey[ld] = key[c];      // the last bucket-id pass writes positions only
-          S.spos[ld] = ps[c];
+          if (KEYOUT) S.skey[ld] = key[c];       // the last bucket-id pass writes positions only
+          if (!DPW0) S.spos[ld] = ps[c];         // (the digit-pos word holds it)
           S.sdst[ld] = S.gbase[d] + (ld - S.tstart[d]);
         }
       }
@@ -885,8 +921,8 @@ k_v2_scatter(const uint8_t* __restrict__ seq, int64_t L, int k, int64_t Nw,
         wave_sync();
         if (act[c]) {
           const uint32_t ld = cur + (uint32_t)__popcll(grp & lanemask_lt());
-          if (BM != 2) S.skey[ld] = key[c];
-          S.spos[ld] = ps[c];
+          if (KEYOUT) S.skey[ld] = key[c];
+          if (!DPW0) S.spos[ld] = ps[c];
           S.sdst[ld] = S.gbase[dg[c]] + (ld - S.tstart[dg[c]]);
         }
       }
@@ -904,8 +940,8 @@ k_v2_scatter(const uint8_t* __restrict__ seq, int64_t L, int k, int64_t Nw,
         const uint64_t kk = S.skey[i];
         reinterpret_cast<uint3*>(kout)[dst] = make_uint3((uint32_t)kk, (uint32_t)(kk >> 32), S.spos[i]);
       } else {
-        if (BM != 2) koutT[dst] = S.skey[i];
-        if (!NOPOS && !P8OUT) pout[dst] = S.spos[i];
+        if (KEYOUT) koutT[dst] = S.skey[i];
+        if (POSOUT) pout[dst] = S.spos[i];
       }
       if constexpr (DS) {       // the next pass's digit, from the staged key (no more LDS)
         const uint64_t kk = P8OUT ? (uint64_t)S.skey[i] >> pk.sh : (uint64_t)S.skey[i];
@@ -954,6 +990,8 @@ __device__ __forceinline__ void bounds_lo_body(uint32_t lo, uint32_t* cnt,
       dg = digit_of(((uint64_t)w[1] << 32) | w[0], g, Dlast);
     } else if (bid == 3) {                 // packed 8-B elements: key << sh | window
       dg = digit_of(kprev[i] >> sh, g, Dlast);
+    } else if (bid == 4) {                 // digit-pos words: this pass's digit << 24 | pos
+      dg = reinterpret_cast<const uint32_t*>(kprev)[i] >> 24;
     } else {
       dg = digit_of(kprev[i], g, Dlast);
     }
@@ -1802,7 +1840,14 @@ void launch_scan_u32(uint32_t* a, uint64_t n, uint64_t* status, uint32_t* total,
 }
 void launch_v2_hist_bid(const uint32_t* bids, const uint32_t* n_ptr, Geom g, Digit D,
                         uint32_t* hist, uint32_t ntiles, uint64_t* scan_status, uint32_t n_status,
-                        hipStream_t s, uint32_t* save_col0) {
+                        hipStream_t s, uint32_t* save_col0, bool dpw) {
+  if (dpw) {                   // digit-pos words: the digit is w >> 24
+    static const unsigned cap = resident_blocks((const void*)k_v2_histp<6>);
+    hipLaunchKernelGGL(k_v2_histp<6>, dim3(std::min<unsigned>(ntiles, cap)), dim3(BLOCK), 0, s,
+                       reinterpret_cast<const uint64_t*>(bids), n_ptr, g, D, hist, ntiles,
+                       scan_status, n_status, save_col0, 0);
+    return;
+  }
   static const unsigned cap = resident_blocks((const void*)k_v2_histp<1>);
   hipLaunchKernelGGL(k_v2_histp<1>, dim3(std::min<unsigned>(ntiles, cap)), dim3(BLOCK), 0, s,
                      reinterpret_cast<const uint64_t*>(bids), n_ptr, g, D, hist, ntiles,
@@ -1857,10 +1902,11 @@ void launch_v2_hist(const uint64_t* keys, const uint32_t* n_ptr, Geom g, Digit D
 void launch_v2_bounds_lo(const uint64_t* kprev, const uint32_t* n_ptr, Geom g, Digit Dlast,
                          uint32_t div, const uint32_t* hist, uint32_t C, const uint32_t* lo_start,
                          uint32_t spread, uint32_t* start, uint32_t nlim, hipStream_t s,
-                         const uint32_t* bprev, bool aos, int sh8) {
+                         const uint32_t* bprev, bool aos, int sh8, bool dpw) {
   hipLaunchKernelGGL(k_v2_bounds_lo, dim3(div), dim3(BLOCK), 0, s,
                      bprev ? reinterpret_cast<const uint64_t*>(bprev) : kprev, n_ptr, g, Dlast,
-                     div, hist, C, lo_start, spread, start, bprev ? 1 : sh8 ? 3 : aos ? 2 : 0,
+                     div, hist, C, lo_start, spread, start,
+                     bprev ? (dpw ? 4 : 1) : sh8 ? 3 : aos ? 2 : 0,
                      nlim, sh8);
 }
 void launch_seg_bounds(const uint32_t* hist, uint32_t ntiles, uint32_t R, uint32_t nseg,
@@ -1904,11 +1950,14 @@ void launch_part_dense(const uint64_t* ck, const uint32_t* cp, const uint32_t* o
 }
 void launch_v2_scatter_bid0(const uint32_t* bids, int64_t Nw, Geom g, Digit D,
                             const uint32_t* hist, uint32_t ntiles, uint32_t* bout, uint32_t* pout,
-                            uint32_t pad, hipStream_t s, const DigitOut* ds) {
+                            uint32_t pad, hipStream_t s, const DigitOut* ds, bool dpw) {
   const uint64_t* ki = reinterpret_cast<const uint64_t*>(bids);
   uint64_t* ko = reinterpret_cast<uint64_t*>(bout);
   const DigitOut dso = ds ? *ds : kNoDigits;
-  if (bout)
+  if (dpw)                     // digit-pos words out (bout), pout unused
+    KMHG_SCATTER_BM(false, true, false, 8, nullptr, (int64_t)0, 0, Nw, ki, nullptr, nullptr, g,
+                    D, hist, ntiles, ko, nullptr, pad, 0, kNoFuse, kNoPack);
+  else if (bout)
     KMHG_SCATTER_BMD(false, true, false, 1, dso, nullptr, (int64_t)0, 0, Nw, ki, nullptr, nullptr,
                      g, D, hist, ntiles, ko, pout, pad, 0, kNoFuse, kNoPack);
   else
@@ -1918,12 +1967,15 @@ void launch_v2_scatter_bid0(const uint32_t* bids, int64_t Nw, Geom g, Digit D,
 void launch_v2_scatter_bid(const uint32_t* bin, const uint32_t* pin, const uint32_t* n_ptr,
                            Geom g, Digit D, const uint32_t* hist, uint32_t ntiles, uint32_t* bout,
                            uint32_t* pout, uint32_t pad, hipStream_t s, const BoundsFuse* bf,
-                           const DigitOut* ds) {
+                           const DigitOut* ds, bool dpw) {
   const uint64_t* ki = reinterpret_cast<const uint64_t*>(bin);
   uint64_t* ko = reinterpret_cast<uint64_t*>(bout);
   const BoundsFuse f = bf ? *bf : kNoFuse;
   const DigitOut dso = ds ? *ds : kNoDigits;
-  if (bout)
+  if (dpw)                     // digit-pos words in (bin; pin unused), positions out
+    KMHG_SCATTER_BM(false, false, false, 9, nullptr, (int64_t)0, 0, (int64_t)0, ki, nullptr,
+                    n_ptr, g, D, hist, ntiles, nullptr, pout, pad, 0, f, kNoPack);
+  else if (bout)
     KMHG_SCATTER_BMD(false, false, false, 1, dso, nullptr, (int64_t)0, 0, (int64_t)0, ki, pin,
                      n_ptr, g, D, hist, ntiles, ko, pout, pad, 0, f, kNoPack);
   else

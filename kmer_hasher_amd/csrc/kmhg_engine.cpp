@@ -43,7 +43,7 @@
 // KMHG_COUNT_TABLE, KMHG_COUNT_WALK, KMHG_CO_SPREAD, KMHG_CO_GLOBAL, KMHG_PART_COMPACT,
 // KMHG_ROW_ORDER_SORT, KMHG_PACK8, KMHG_NB_ROUND, KMHG_SLICE_POISON, KMHG_TEST_REPLICA,
 // KMHG_DIGIT_STREAM, KMHG_DS_BID, KMHG_DS_U8, KMHG_DS_PACK, KMHG_BUILD_TAGS,
-// KMHG_BUCKET_PLACE), which choose
+// KMHG_BUCKET_PLACE, KMHG_BID_PACK), which choose
 // between equivalent paths and change no result; fault injection (KMHG_TEST_DISORDER); and the
 // A/B-only switches (KMHG_D2H, KMHG_D2H_HUGE, KMHG_HOST_RUNS, KMHG_HOST_PAIRS, KMHG_HOST_POOL,
 // KMHG_COUNT_BID, KMHG_RK_CAP, KMHG_POOL_DEPTH, KMHG_POOL_BESTFIT, KMHG_POOL_TRACE).
@@ -1170,6 +1170,16 @@ uint32_t* bucket_place_counters() {
 uint32_t* bucket_place_counters() { return nullptr; }
 #endif
 
+// Which middle stream the bucket-id builds took (test build, kmhg_bid_pack_counters): [0] the
+// digit-pos words, [1] every other bucket-id build (the two arrays).  Host counters: the choice is
+// made here, not on the device.
+#ifdef KMHG_TEST_BUILD
+static std::atomic<uint64_t> g_bid_pack_ctr[2];
+void count_bid_pack(bool packed) { g_bid_pack_ctr[packed ? 0 : 1].fetch_add(1, std::memory_order_relaxed); }
+#else
+void count_bid_pack(bool) {}
+#endif
+
 kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t s,
                             const uint64_t* d_keys = nullptr, int64_t n_keys = 0,
                             bool count_only = false, int co_spread = 1, bool skip_empty = false,
@@ -1337,6 +1347,20 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
   const bool ds_bids = bid && passes >= 2 &&
                        (dse && dse[0] ? dse[0] == '1' : R <= 256 && dbe && dbe[0] == '1');
   const bool ds_on = ds_keys || ds_bids;
+  // Digit-pos words: a two-pass bucket-id build carries ONE u32 per window between its passes,
+  // (pass-1 digit << 24) | pos, instead of the (bucket id, pos) pair -- pass 1, its histogram
+  // and the bucket-start level need only that digit (the pass-0 digit is implied by where the
+  // element lies), the radix of a two-pass plan up to BID_MAX_WINDOWS is far below 256 (nb <=
+  // 13,824: R = 118) and the positions fit 24 bits.  Pass 0 writes and pass 1 reads 4 B per
+  // window less, and a tile's digit run is one piece instead of two.  Every other bucket-id
+  // build (one pass, 3+ passes under KMHG_MAXR, digit streams, KMHG_BUILD_BID=1 beyond 2^24
+  // windows) keeps the two arrays.  KMHG_BID_PACK=0 (test build) forces the two arrays.
+  static_assert(BID_MAX_WINDOWS < (int64_t(1) << BID_POS_BITS),
+                "a default bucket-id build's positions fit the digit-pos word");
+  const char* bpe = test_build_knob("KMHG_BID_PACK");
+  const bool bid_pack = bid && passes == 2 && R <= 256 && Nw < (int64_t(1) << BID_POS_BITS) &&
+                        !ds_bids && !(bpe && bpe[0] == '0');
+  if (bid) count_bid_pack(bid_pack);
   const char* dpe = test_build_knob("KMHG_DS_PACK");
   const bool ds_pack = ds_keys && !(dpe && dpe[0] == '0');
   auto packed = [&](int p) {
@@ -1357,7 +1381,8 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
   const bool no_pos = count_only;                        // keys only through the passes
   // (a part build's compacted windows land in kB / pB before they are packed: pB stays)
   const bool partc_pos = !from_keys && n_parts >= 2 && codes;
-  DBuf<uint32_t> pA(no_pos || !any_unpacked ? 1 : Nw + PTILE, s),
+  // (digit-pos words: pass 0 writes bA alone, pass 1 writes pB)
+  DBuf<uint32_t> pA(no_pos || !any_unpacked || bid_pack ? 1 : Nw + PTILE, s),
       pB(no_pos || (!any_unpacked && !partc_pos) ? 1 : Nw + PTILE, s);
   const uint32_t pad = (uint32_t)Nw;
   DBuf<uint32_t> hist(nhist, s);
@@ -1438,7 +1463,7 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
         LAUNCH("k_v2_scatter_seq", s,
                launch_v2_scatter_bid0(bB.p, Nw, g, make_digit(1, R), hist.p, ntiles,
                                       passes == 1 ? nullptr : bA.p, pA.p, pad, s,
-                                      ds_on ? &ds0 : nullptr));
+                                      ds_on ? &ds0 : nullptr, bid_pack));
         ds_ready = ds_on;
       } else {
         const DigitOut ds0{ds16p, make_digit(R, R), ds8p};
@@ -1500,7 +1525,7 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
     const bool p8 = pack8 && p == 1;                    // the input is the packed 8-B stream
     BoundsFuse f{reinterpret_cast<const uint64_t*>(kprev), lin, lout,
                  make_digit((uint32_t)dv, R), (uint32_t)dv, spread,
-                 is_bid ? 1 : p8 ? 3 : packed((int)p - 1) ? 2 : 0,
+                 is_bid ? (bid_pack ? 4 : 1) : p8 ? 3 : packed((int)p - 1) ? 2 : 0,
                  last ? g.nb : (uint32_t)(dv * R)};
     f.sh = p8 ? sh8 : 0;
     return f;
@@ -1511,7 +1536,7 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
     const uint32_t* bp = f.bid ? reinterpret_cast<const uint32_t*>(f.kprev) : nullptr;
     LAUNCH("k_v2_bounds", s, launch_v2_bounds_lo(kp, n_valid, g, f.Dlast, f.div, hp, C,
                                                  f.lo_start, f.spread, f.start, f.nlim, s, bp,
-                                                 f.bid == 2, f.bid == 3 ? f.sh : 0));
+                                                 f.bid == 2, f.bid == 3 ? f.sh : 0, f.bid == 4));
   };
   for (uint32_t p = 1; bid && p < passes; ++p) {
     const Digit Dp = make_digit(div, R);
@@ -1523,14 +1548,14 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
     else
       LAUNCH("k_v2_hist", s,
              launch_v2_hist_bid(bin, n_valid, g, Dp, hp, C, status, nst, s,
-                                p == 1 ? save1 : nullptr));
+                                p == 1 ? save1 : nullptr, bid_pack));
     LAUNCH("k_scan_u32", s, launch_scan_u32(hp, nh, status, n_valid, s));
     const BoundsFuse lv = level_of(p, bin, true, 1u);
     const DigitOut dsn{ds16p, make_digit(div * R, R), ds8p};
     LAUNCH("k_v2_scatter", s,
            launch_v2_scatter_bid(bin, pin, n_valid, g, Dp, hp, C, last ? nullptr : bout,
                                  pout, pad, s, fused(p) ? &lv : nullptr,
-                                 ds_on && !last ? &dsn : nullptr));
+                                 ds_on && !last ? &dsn : nullptr, bid_pack));
     ds_ready = ds_on && !last;
     if (!fused(p) && !last) launch_level(lv);
     std::swap(bin, bout);
@@ -4147,6 +4172,20 @@ int kmhg_bucket_place_counters(uint64_t out[3], int reset) {
     (void)hipSetDevice(dev);
     hip_check(e, "bucket placement counters");
     for (int i = 0; i < 3; ++i) out[i] = h[i];
+#else
+    (void)reset;
+#endif
+  });
+}
+
+int kmhg_bid_pack_counters(uint64_t out[2], int reset) {
+  return guarded([&] {
+    if (!out) fail(KMHG_EINVAL, "null result pointer");
+    out[0] = out[1] = 0;
+#ifdef KMHG_TEST_BUILD
+    for (int i = 0; i < 2; ++i)
+      out[i] = reset ? g_bid_pack_ctr[i].exchange(0, std::memory_order_relaxed)
+                     : g_bid_pack_ctr[i].load(std::memory_order_relaxed);
 #else
     (void)reset;
 #endif

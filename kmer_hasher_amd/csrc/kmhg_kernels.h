@@ -230,7 +230,8 @@ void launch_v2_hist(const uint64_t* keys, const uint32_t* n_ptr, Geom g, Digit D
 void launch_v2_bounds_lo(const uint64_t* kprev, const uint32_t* n_ptr, Geom g, Digit Dlast,
                          uint32_t div, const uint32_t* hist, uint32_t C, const uint32_t* lo_start,
                          uint32_t spread, uint32_t* start, uint32_t nlim, hipStream_t s,
-                         const uint32_t* bprev = nullptr, bool aos = false, int sh8 = 0);
+                         const uint32_t* bprev = nullptr, bool aos = false, int sh8 = 0,
+                         bool dpw = false);
 // segb (Pack8) from pass 0's scanned histogram: R x (nseg + 1) entries, tps = tiles per segment
 void launch_seg_bounds(const uint32_t* hist, uint32_t ntiles, uint32_t R, uint32_t nseg,
                        uint32_t tps, const uint32_t* n_valid, uint32_t* segb, hipStream_t s);
@@ -273,7 +274,7 @@ struct BoundsFuse {
   Digit Dlast;                 // the pass's own digit
   uint32_t div, spread;        // div = R^p lower-digit values
   int bid;                     // 0 u64 keys, 1 u32 bucket ids, 2 packed 12-B (key, pos) elements,
-                               // 3 packed 8-B (key << sh | window) elements
+                               // 3 packed 8-B (key << sh | window) elements, 4 digit-pos words
   uint32_t nlim;               // entries of S_p: nb for the last pass, R^(p+1) before
   int sh = 0;                  // bid 3: the element's key is e >> sh
 };
@@ -304,16 +305,23 @@ void launch_v2_scatter(const uint64_t* kin, const uint32_t* pin, const uint32_t*
 // every window's bucket id (`bids`, Nw u32, ~0 = not indexed), the radix passes carry (bucket
 // id u32, pos u32) and the last pass writes positions only (bout = nullptr); the bucket kernel
 // cuts the keys from the code words.  Histograms without hashing.
+// dpw (two passes, radix <= 256, Nw < 2^24 = 1 << BID_POS_BITS): the stream between the two
+// passes is one u32 per window, the digit-pos word (pass-1 digit << 24) | pos -- pass 0 writes
+// it to bout (pout unused), pass 1 and its histogram and bucket-start level read the digit as
+// w >> 24 (bin; pin unused) and pass 1 writes w & 0xFFFFFF to pout.
+constexpr int BID_POS_BITS = 24;
 void launch_v2_scatter_bid0(const uint32_t* bids, int64_t Nw, Geom g, Digit D,
                             const uint32_t* hist, uint32_t ntiles, uint32_t* bout, uint32_t* pout,
-                            uint32_t pad, hipStream_t s, const DigitOut* ds = nullptr);
+                            uint32_t pad, hipStream_t s, const DigitOut* ds = nullptr,
+                            bool dpw = false);
 void launch_v2_scatter_bid(const uint32_t* bin, const uint32_t* pin, const uint32_t* n_ptr,
                            Geom g, Digit D, const uint32_t* hist, uint32_t ntiles, uint32_t* bout,
                            uint32_t* pout, uint32_t pad, hipStream_t s,
-                           const BoundsFuse* bf = nullptr, const DigitOut* ds = nullptr);
+                           const BoundsFuse* bf = nullptr, const DigitOut* ds = nullptr,
+                           bool dpw = false);
 void launch_v2_hist_bid(const uint32_t* bids, const uint32_t* n_ptr, Geom g, Digit D,
                         uint32_t* hist, uint32_t ntiles, uint64_t* scan_status, uint32_t n_status,
-                        hipStream_t s, uint32_t* save_col0 = nullptr);
+                        hipStream_t s, uint32_t* save_col0 = nullptr, bool dpw = false);
 struct BucketStats {           // per-bucket partials of the build statistics
   uint32_t n_kmers, max_count;
   uint64_t n_pairs;
