@@ -98,6 +98,43 @@ __device__ __forceinline__ uint32_t digit_of_h(uint64_t h, const Geom& g, const 
 __device__ __forceinline__ uint32_t digit_of(uint64_t key, const Geom& g, const Digit& D) {
   return digit_of_h(mix64(key), g, D);
 }
+// The radix digit of ONE element of a stream of format F -- the only place that knows how a
+// format holds it.  w = the element's word already in registers: the u64 key (Keys, KeyPos,
+// Packed12), the packed 8-B element (Packed8: the key is w >> sh, sh = Pack8::sh), the u32 id
+// or digit-pos word (bucket-id formats), or the digit itself (Digits8 / Digits16).
+// In two steps, for a caller that takes two digits of one element (V_scatter reading Packed8):
+// digit_src is what every digit of the element is taken from -- the hash of its key, or the
+// word itself -- and digit_of_src one digit of that.
+template <StreamFmt F>
+__device__ __forceinline__ uint64_t digit_src(uint64_t w, int sh) {
+  if constexpr (fmt_bid(F) || F == StreamFmt::Digits8 || F == StreamFmt::Digits16) return w;
+  else return mix64(F == StreamFmt::Packed8 ? w >> sh : w);
+}
+template <StreamFmt F>
+__device__ __forceinline__ uint32_t digit_of_src(uint64_t x, const Geom& g, const Digit& D) {
+  if constexpr (F == StreamFmt::Digits8 || F == StreamFmt::Digits16) return (uint32_t)x;
+  else if constexpr (F == StreamFmt::DigitPos) return (uint32_t)x >> BID_POS_BITS;
+  else if constexpr (fmt_bid(F)) return digit_of_b((uint32_t)x, D);
+  else return digit_of_h(x, g, D);
+}
+template <StreamFmt F>
+__device__ __forceinline__ uint32_t digit_of_elem(uint64_t w, const Geom& g, const Digit& D,
+                                                  int sh) {
+  return digit_of_src<F>(digit_src<F>(w, sh), g, D);
+}
+// ... of element i of the stream's first array `in`
+template <StreamFmt F>
+__device__ __forceinline__ uint32_t digit_of_elem(const void* __restrict__ in, uint64_t i,
+                                                  const Geom& g, const Digit& D, int sh) {
+  if constexpr (fmt_bid(F)) {
+    return digit_of_elem<F>(reinterpret_cast<const uint32_t*>(in)[i], g, D, sh);
+  } else if constexpr (F == StreamFmt::Packed12) {
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(in) + 3 * i;
+    return digit_of_elem<F>(((uint64_t)w[1] << 32) | w[0], g, D, sh);
+  } else {
+    return digit_of_elem<F>(reinterpret_cast<const uint64_t*>(in)[i], g, D, sh);
+  }
+}
 
 // Lanes of the wave holding the same `v` (nbits wide) among active lanes: one ballot per bit.
 __device__ __forceinline__ uint64_t match_bits(uint32_t v, int nbits, bool act) {
@@ -303,8 +340,9 @@ constexpr uint32_t HLL_SAMPLE_BITS = 6;
 constexpr uint32_t HLL_PART_ROWS = 256;        // V_hll workgroups (partial rows) at most
 static_assert(HLL_PART_WORDS == HLL_PART_ROWS * 64 + 1, "V_hll partial rows + ticket");
 
-// BID: the stream holds u32 bucket ids (BM scatter passes), digits without hashing.
-template <bool HLL, bool BID = false>
+// The first pass over a caller's key stream (format Keys: exactly n keys, no pad), one workgroup
+// per tile; every later pass takes the persistent k_v2_histp.
+template <bool HLL>
 __global__ void __launch_bounds__(BLOCK)
 k_v2_hist(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ n_ptr, Geom g,
           Digit D, uint32_t* __restrict__ hist, uint32_t ntiles,
@@ -328,20 +366,12 @@ k_v2_hist(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ n_ptr,
   const uint32_t R = D.R;
   for (uint32_t d = threadIdx.x; d < R; d += BLOCK) lh[d] = 0;
   __syncthreads();
-  constexpr int NL = BID ? 8 : 4;                 // loads in flight per lane
-  const uint32_t* __restrict__ bids = reinterpret_cast<const uint32_t*>(keys);
+  constexpr int NL = 4;                           // loads in flight per lane
   for (uint64_t e = e0 + threadIdx.x; e < e1; e += NL * BLOCK) {
     uint32_t dg[NL];
     bool in[NL];
-    if (BID) {
 #pragma unroll
-      for (int j = 0; j < NL; ++j) {
-        in[j] = e + j * BLOCK < e1;
-        dg[j] = in[j] ? digit_of_b(bids[e + j * BLOCK], D) : 0u;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < NL && !BID; ++j) {
+    for (int j = 0; j < NL; ++j) {
       in[j] = e + j * BLOCK < e1;
       const uint64_t key = in[j] ? keys[e + j * BLOCK] : 0ull;
       if (skip_empty && key == EMPTY_KEY) in[j] = false;      // a padded read's unused slot
@@ -370,15 +400,20 @@ k_v2_hist(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ n_ptr,
 // while this one is counted -- the one-tile-per-workgroup form exposed every workgroup's load
 // latency (config 2: 14.5 us for 40 MB).  `in` holds n + PTILE elements (the passes' padded
 // streams), so whole-tile loads stay inside it.
-// MODE: 0 = u64 keys, 1 = u32 bucket ids, 2 = packed 12-B {key lo, key hi, pos} elements (the
-// position builds' key streams), 3 = packed 8-B elements (Pack8: the key is e >> sh), 4 = the
-// previous pass's digit stream (u16 digits, DS in V_scatter), 5 = the same in u8 digits, 6 =
-// digit-pos words (the packed bucket-id stream, V_scatter BM 8): the digit is w >> 24.
-template <int MODE>
+// IN = the format of `in`.  KeyPos reads the u64 key array (a Keys stream takes the same
+// instance); BidPos the u32 bucket ids; Packed12 the position builds' packed key streams;
+// Packed8 the 8-B elements whose key is e >> sh; Digits16 / Digits8 the previous pass's digit
+// stream (DS in V_scatter) instead of its elements; DigitPos the packed bucket-id stream, whose
+// digit is w >> 24.  What differs per format here is the load shape only (16-B loads; one
+// dwordx3 element per lane for Packed12; one 8-B load for Digits8) -- the digit of an element is
+// digit_of_elem's.
+template <StreamFmt IN>
 __global__ void __launch_bounds__(BLOCK)
 k_v2_histp(const uint64_t* __restrict__ in, const uint32_t* __restrict__ n_ptr, Geom g, Digit D,
            uint32_t* __restrict__ hist, uint32_t ntiles, uint64_t* __restrict__ scan_status,
            uint32_t n_status, uint32_t* __restrict__ save_col0, int sh) {
+  static_assert(IN != StreamFmt::Keys && IN != StreamFmt::Bids && IN != StreamFmt::Pos,
+                "Keys streams take the KeyPos instance; Bids and Pos streams are never counted");
   __shared__ uint32_t lh[V2_MAXR];
   for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n_status; i += gridDim.x * BLOCK)
     scan_status[i] = 0;
@@ -391,8 +426,7 @@ k_v2_histp(const uint64_t* __restrict__ in, const uint32_t* __restrict__ n_ptr, 
   if (save_col0 && tile_at(0) == 0)
     for (uint32_t d = threadIdx.x; d < R; d += BLOCK) save_col0[d] = hist[(size_t)d * ntiles];
   for (uint32_t d = threadIdx.x; d < R; d += BLOCK) lh[d] = 0;
-  constexpr bool BID = MODE == 1 || MODE == 6;
-  if constexpr (MODE == 2) {
+  if constexpr (IN == StreamFmt::Packed12) {
     // packed 12-B elements: thread t takes elements t + 256 j of the tile (j < 8), so every
     // load instruction reads 768 contiguous bytes per wave (one element per lane, dwordx3); a
     // thread's 96 consecutive bytes would spread each instruction over 48 lines
@@ -413,10 +447,8 @@ k_v2_histp(const uint64_t* __restrict__ in, const uint32_t* __restrict__ n_ptr, 
       const uint64_t e0 = (uint64_t)tile * PTILE + threadIdx.x;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        if (e0 + (uint64_t)j * BLOCK < n) {
-          const uint64_t key = ((uint64_t)cur[j].y << 32) | cur[j].x;
-          atomicAdd(&lh[digit_of_h(mix64(key), g, D)], 1u);
-        }
+        if (e0 + (uint64_t)j * BLOCK < n)
+          atomicAdd(&lh[digit_of_elem<IN>(((uint64_t)cur[j].y << 32) | cur[j].x, g, D, sh)], 1u);
       }
       __syncthreads();
       for (uint32_t d = threadIdx.x; d < R; d += BLOCK) {
@@ -426,17 +458,18 @@ k_v2_histp(const uint64_t* __restrict__ in, const uint32_t* __restrict__ n_ptr, 
     }
     return;
   }
-  constexpr bool DIG = MODE == 4, DIG8 = MODE == 5;
-  constexpr int NV = DIG || DIG8 ? 1 : BID ? 2 : 4;   // 16-B loads per thread per tile
+  // thread t's 8 consecutive elements of a tile, EB bytes each, as NV 16-B words
+  constexpr int EB = (int)fmt_key_bytes(IN);
+  constexpr int NV = EB == 1 ? 1 : EB / 2;
   uint4 nx[NV];
   auto prefetch = [&](uint32_t tile) {
-    if constexpr (DIG8) {                              // 8 u8 digits: one 8-B load
+    if constexpr (EB == 1) {                           // 8 u8 digits: one 8-B load
       const uint2 v = reinterpret_cast<const uint2*>(in)[(uint64_t)tile * (PTILE / 8) + threadIdx.x];
       nx[0] = make_uint4(v.x, v.y, 0u, 0u);
       return;
     }
     const uint4* src = reinterpret_cast<const uint4*>(in) +
-                       ((uint64_t)tile * PTILE + 8u * threadIdx.x) / (DIG ? 8 : BID ? 4 : 2);
+                       ((uint64_t)tile * PTILE + 8u * threadIdx.x) / (16 / EB);
 #pragma unroll
     for (int v = 0; v < NV; ++v) nx[v] = src[v];
   };
@@ -452,24 +485,15 @@ k_v2_histp(const uint64_t* __restrict__ in, const uint32_t* __restrict__ n_ptr, 
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       if (e0 + j < n) {
-        uint32_t dg;
-        if (DIG8) {
-          const uint32_t wj = (j >> 2) == 0 ? cur[0].x : cur[0].y;
-          dg = (wj >> (8 * (j & 3))) & 0xFFu;
-        } else if (DIG) {
-          const uint4 w = cur[0];
-          const uint32_t wj = (j >> 1) == 0 ? w.x : (j >> 1) == 1 ? w.y : (j >> 1) == 2 ? w.z : w.w;
-          dg = (j & 1) ? wj >> 16 : wj & 0xFFFFu;
-        } else if (BID) {
-          const uint4 w = cur[j >> 2];
-          const uint32_t id = (j & 3) == 0 ? w.x : (j & 3) == 1 ? w.y : (j & 3) == 2 ? w.z : w.w;
-          dg = MODE == 6 ? id >> 24 : digit_of_b(id, D);
-        } else {
-          const uint4 w = cur[j >> 1];
-          const uint64_t e = (j & 1) ? (((uint64_t)w.w << 32) | w.z) : (((uint64_t)w.y << 32) | w.x);
-          dg = digit_of_h(mix64(MODE == 3 ? e >> sh : e), g, D);
-        }
-        atomicAdd(&lh[dg], 1u);
+        // element j out of the loaded words: u32 word jw of them, or the u64 at words jw, jw + 1
+        constexpr int PW = 4 / (EB < 4 ? EB : 4);      // elements per u32 word
+        const int jw = EB == 8 ? 2 * j : j / PW;
+        const uint4 w = cur[jw >> 2];
+        auto word = [&](int i) { return i == 0 ? w.x : i == 1 ? w.y : i == 2 ? w.z : w.w; };
+        uint64_t e = word(jw & 3);
+        if constexpr (EB == 8) e |= (uint64_t)word((jw & 3) + 1) << 32;
+        if constexpr (EB < 4) e = (e >> (8 * EB * (j % PW))) & ((1u << (8 * EB)) - 1u);
+        atomicAdd(&lh[digit_of_elem<IN>(e, g, D, sh)], 1u);
       }
     }
     __syncthreads();
@@ -562,6 +586,75 @@ k_v2_hll_final(const uint32_t* __restrict__ part, uint32_t n_part, double* __res
   }
 }
 
+// ---------------------------------------------------------------- V_bounds_lo
+// Bucket starts from the radix histograms instead of a pass over the sorted keys.  With LSD
+// passes, pass p's input is sorted by lo = c mod div (c = the element's digits 0 .. p combined,
+// div = R^p) and the pass places elements by its own digit hi, stably, so
+//   S_p[hi * div + lo] = #(digit < hi) + #(digit == hi and lo' < lo)
+//                      = hist_p[hi][t] + #(digit hi among the pass's input [t * PTILE, P_lo))
+// where P_lo = S_(p-1)[lo] = #(lo' < lo) is the start of lo in that input (for p = 1 pass 0's
+// scanned column 0, saved by V_hist) and t = P_lo / PTILE: one workgroup per lo value counts at
+// most one partial tile.  S_p of the last pass are the bucket starts; the earlier levels (3+
+// passes) keep S_p (R^(p+1) entries, `nlim`) for the next.  Each level rides in its pass's
+// scatter (BoundsFuse) -- it needs that pass's scanned histogram and its input, both live
+// there -- so no key pass and no launch of its own.  Interleaved schedule only (one histogram
+// column per tile).  `spread` (count-only builds): start[b / spread] for the buckets b that are
+// multiples of spread.
+// IN = the format of the pass's input `in` (sh: Pack8::sh of a Packed8 stream).
+template <StreamFmt IN>
+__device__ __forceinline__ void bounds_lo_body(uint32_t lo, uint32_t* cnt,
+                                               const void* __restrict__ in, int sh, uint32_t n,
+                                               Geom g, Digit Dlast, uint32_t div,
+                                               const uint32_t* __restrict__ hist, uint32_t C,
+                                               const uint32_t* __restrict__ lo_start,
+                                               uint32_t spread, uint32_t* __restrict__ start,
+                                               int tb, uint32_t nlim) {
+  const uint32_t R = Dlast.R;
+  const uint32_t P = lo_start ? lo_start[lo] : 0u;
+  for (uint32_t d = threadIdx.x; d < R; d += tb) cnt[d] = 0;
+  __syncthreads();
+  const uint32_t tile = P / PTILE;
+  for (uint32_t i = tile * PTILE + threadIdx.x; i < P; i += tb)
+    atomicAdd(&cnt[digit_of_elem<IN>(in, i, g, Dlast, sh)], 1u);
+  __syncthreads();
+  for (uint32_t hi = threadIdx.x; hi < R; hi += tb) {
+    const uint64_t b = (uint64_t)hi * div + lo;
+    if (b >= nlim || b % spread) continue;
+    // P == n on a tile boundary past the last column: the end of digit hi
+    const uint32_t base = tile < C ? hist[(size_t)hi * C + tile]
+                                   : (hi + 1 < R ? hist[(size_t)(hi + 1) * C] : n);
+    start[b / spread] = base + cnt[hi];
+  }
+  if (lo == 0 && threadIdx.x == 0) start[nlim / spread] = n;
+  __syncthreads();                         // cnt is the caller's LDS: free again
+}
+
+// The unfused level (KMHG_FUSE_BOUNDS=0, the last level of a count-only build that picks its
+// spread after the passes, one-pass builds): the cold path, so one kernel that switches over the
+// format at run time.
+__global__ void __launch_bounds__(BLOCK)
+k_v2_bounds_lo(StreamFmt fmt, const void* __restrict__ in, int sh,
+               const uint32_t* __restrict__ n_ptr, Geom g, Digit Dlast, uint32_t div,
+               const uint32_t* __restrict__ hist, uint32_t C,
+               const uint32_t* __restrict__ lo_start, uint32_t spread,
+               uint32_t* __restrict__ start, uint32_t nlim) {
+  __shared__ uint32_t cnt[V2_MAXR];
+#define KMHG_LEVEL(F)                                                                          \
+  case StreamFmt::F:                                                                           \
+    bounds_lo_body<StreamFmt::F>(blockIdx.x, cnt, in, sh, *n_ptr, g, Dlast, div, hist, C,       \
+                                 lo_start, spread, start, BLOCK, nlim);                         \
+    break
+  switch (fmt) {
+    KMHG_LEVEL(KeyPos);
+    KMHG_LEVEL(Packed12);
+    KMHG_LEVEL(Packed8);
+    KMHG_LEVEL(BidPos);
+    KMHG_LEVEL(DigitPos);
+    default: break;            // (Keys arrives as KeyPos; nothing else is a pass's input)
+  }
+#undef KMHG_LEVEL
+}
+
 // ---------------------------------------------------------------- V_scatter (stable)
 // Tile t = elements [t*PTILE, (t+1)*PTILE); wave w of the NWV waves owns the contiguous
 // PTILE/NWV elements [t*PTILE + w*PTILE/NWV, ...), lane l holds element 64c + l of them.
@@ -578,8 +671,9 @@ k_v2_hll_final(const uint32_t* __restrict__ part, uint32_t n_part, double* __res
 // schedule with per-chunk histograms, -10 %: each workgroup's open digit-run heads overflow the
 // L2.)
 constexpr int SC_NWV = 4;                       // waves per scatter workgroup
-// KEY / POS / STG: the mode stages keys / positions / the tile's chars (the digit-pos modes, BM 8
-// and 9, drop what they never touch: 33.4 -> 24.1 KB per workgroup)
+// KEY / POS / STG: the pass stages keys / positions / the tile's chars (the two DigitPos passes,
+// Bids -> DigitPos and DigitPos -> Pos, drop what they never touch: 33.4 -> 24.1 KB per
+// workgroup)
 template <class KT, bool KEY = true, bool POS = true, bool STG = true>
 struct ScatterLDS {
   static constexpr uint32_t MAXR = V2_MAXR_IL;
@@ -632,35 +726,51 @@ __device__ __forceinline__ uint32_t block_excl_scan_n32(uint32_t v, uint64_t* ld
 
 // KEYS0: the first pass over a caller's key stream (a table rebuilt from keys): `kin` holds
 // exactly n keys (loads clamped, no pad) and positions are implicit (e + 1), so the stream is
-// neither copied nor paired with an iota array first.  NOPOS: keys only (count-only builds:
-// nobody reads the positions), 8 B per element in and out instead of 12.
-// BM (bucket-id streams, position builds that keep code words): 0 = (key u64, pos) elements;
-// 1 = (bucket id u32, pos) in and out -- the digit needs no hash, and the key is cut from the
-// code words by the bucket kernel; 2 = the last pass: (bucket id, pos) in, positions only out.
-// kin / kout then point at u32 arrays.  8 B per element instead of 12 through the middle passes,
-// 4 B out of the last.
-// 8 / 9 = the two passes of a two-pass bucket-id build at a radix <= 256 and < 2^24 windows with
-// ONE u32 per window between them, the digit-pos word (pass-1 digit << 24) | pos: 8 = pass 0
-// (KEYS0: V_hist0's ids in, positions implicit) writes the words to kout, nothing to pout; 9 =
-// the last pass reads them (digit = w >> 24, no division) and writes w & 0xFFFFFF to pout.  The
-// pass-0 digit is implied by where the word lies, and the fused bucket-start level reads only
-// this pass's digit too.  4 B per window through the middle instead of 8, one run per tile and
-// digit instead of two.
-// 3 = packed (key, pos) elements, 12 B each in kin / kout ({key lo, key hi, pos}; pin / pout
+// neither copied nor paired with an iota array first.
+// IN / OUT: the formats of the pass's input and output (StreamFmt; the sequence and a first
+// pass over keys are Keys in: positions implicit).
+// Keys out (count-only builds: nobody reads the positions): 8 B per element in and out instead
+// of 12.  KeyPos: (key u64, pos) in two arrays.
+// BidPos (bucket-id streams, position builds that keep code words): (bucket id u32, pos) -- the
+// digit needs no hash, and the key is cut from the code words by the bucket kernel; the last
+// pass writes Pos, positions only.  kin / kout then point at u32 arrays.  8 B per element
+// instead of 12 through the middle passes, 4 B out of the last.
+// DigitPos: the two passes of a two-pass bucket-id build at a radix <= 256 and < 2^24 windows
+// carry ONE u32 per window between them, the digit-pos word (pass-1 digit << 24) | pos: Bids ->
+// DigitPos (pass 0: V_hist0's ids in, positions implicit) writes the words to kout, nothing to
+// pout; DigitPos -> Pos, the last pass, reads them (digit = w >> 24, no division) and writes
+// w & 0xFFFFFF to pout.  The pass-0 digit is implied by where the word lies, and the fused
+// bucket-start level reads only this pass's digit too.  4 B per window through the middle
+// instead of 8, one run per tile and digit instead of two.
+// Packed12: (key, pos) elements, 12 B each in kin / kout ({key lo, key hi, pos}; pin / pout
 // unused): a tile's digit run leaves as ONE contiguous piece instead of an 8 c-byte piece of
-// keys and a 4 c-byte piece of positions in two arrays; 4 = (key, pos) arrays in, packed out
-// (the last pass of a build whose earlier streams stay unpacked for their histogram passes);
-// 6 = the first pass from the sequence writing packed 8-B elements (Pack8, small k), 7 = the
-// second pass reading them (each element's position restored from its segment, found in
-// pk.segb by its place in the stream) and writing packed 12-B elements.  Write-pattern probe
+// keys and a 4 c-byte piece of positions in two arrays; KeyPos -> Packed12 is the last pass of a
+// build whose earlier streams stay unpacked for their histogram passes.
+// Packed8 (Pack8, small k): the first pass from the sequence writes packed 8-B elements, and
+// Packed8 -> Packed12, the second pass, reads them (each element's position restored from its
+// segment, found in pk.segb by its place in the stream).  Write-pattern probe
 // (tools/scatter_pattern.hip layout, profiles/r5a_scatter_layout.txt, 100 M elements): radix 313
 // 1.09 -> 0.87 ms, radix 79 0.72 -> 0.61 ms.
 // BALLOT: stable ranks from one ballot per digit bit instead of the count atomics' lane-ordered
 // returns -- chosen at run time where the device self-check finds that order violated.
 // DS (digit stream): the pass also writes every element's digit of the NEXT pass (u16, at the
 // element's place in the output), which that pass's histogram reads instead of the keys.
-template <bool FROM_SEQ, bool KEYS0 = false, bool NOPOS = false, int BM = 0, bool BALLOT = false,
-          bool DS = false>
+// the (IN, OUT) pairs a pass may be built for (launch_v2_scatter lists the same ones)
+constexpr bool scatter_pair_ok(bool from_seq, bool keys0, StreamFmt in, StreamFmt out) {
+  using F = StreamFmt;
+  if (from_seq)                // the windows: keys with implicit positions
+    return !keys0 && in == F::Keys && (out == F::KeyPos || out == F::Packed12 || out == F::Packed8);
+  if (keys0)                   // a caller's keys, or V_hist0's ids
+    return in == F::Keys ? out == F::Keys || out == F::KeyPos
+                         : in == F::Bids &&
+                               (out == F::BidPos || out == F::DigitPos || out == F::Pos);
+  return (in == F::Keys && out == F::Keys) ||
+         (in == F::KeyPos && (out == F::KeyPos || out == F::Packed12)) ||
+         ((in == F::Packed12 || in == F::Packed8) && out == F::Packed12) ||
+         (in == F::BidPos && (out == F::BidPos || out == F::Pos)) ||
+         (in == F::DigitPos && out == F::Pos);
+}
+template <bool FROM_SEQ, bool KEYS0, StreamFmt IN, StreamFmt OUT, bool BALLOT, bool DS>
 __global__ void __launch_bounds__(SC_NWV * 64)
 k_v2_scatter(const uint8_t* __restrict__ seq, int64_t L, int k, int64_t Nw,
              const uint64_t* __restrict__ kin, const uint32_t* __restrict__ pin,
@@ -668,22 +778,20 @@ k_v2_scatter(const uint8_t* __restrict__ seq, int64_t L, int k, int64_t Nw,
              const uint32_t* __restrict__ hist, uint32_t ntiles,
              uint64_t* __restrict__ kout, uint32_t* __restrict__ pout, uint32_t pad,
              int skip_empty, BoundsFuse bf, Pack8 pk, DigitOut dso) {
-  constexpr bool DPW0 = BM == 8, DPW1 = BM == 9;  // digit-pos words out / in
-  constexpr bool BIDS = BM == 1 || BM == 2 || DPW0 || DPW1;      // bucket-id streams
-  constexpr bool KEYOUT = BM != 2 && !DPW1;       // the pass writes kout
-  constexpr bool POSOUT = !NOPOS && BM != 6 && !DPW0;   // ... pout (packed streams: see AOS)
-  constexpr bool AOS = BM == 3 || BM == 4 || BM == 7;   // packed 12-B (key, pos) elements out
-  constexpr bool AIN = BM == 3;                   // ... and in
-  constexpr bool P8OUT = BM == 6;                 // packed 8-B (key << sh | window) out
-  constexpr bool P8IN = BM == 7;                  // ... in
+  static_assert(scatter_pair_ok(FROM_SEQ, KEYS0, IN, OUT), "not a pair of formats a pass converts");
+  static_assert(!DS || (OUT != StreamFmt::Pos && OUT != StreamFmt::DigitPos &&
+                        OUT != StreamFmt::Keys), "no digit stream out of these passes");
+  constexpr bool DPW0 = OUT == StreamFmt::DigitPos, DPW1 = IN == StreamFmt::DigitPos;
+  constexpr bool BIDS = fmt_bid(IN);              // bucket-id streams: u32 words in and out
+  constexpr bool KEYOUT = fmt_key_bytes(OUT) != 0;   // the pass writes kout
+  constexpr bool POSOUT = fmt_pos_array(OUT);     // ... pout
+  constexpr bool POSIN = fmt_pos_array(IN);       // ... reads pin
+  constexpr bool AOS = OUT == StreamFmt::Packed12, AIN = IN == StreamFmt::Packed12;
+  constexpr bool P8OUT = OUT == StreamFmt::Packed8, P8IN = IN == StreamFmt::Packed8;
   using KT = typename std::conditional<BIDS, uint32_t, uint64_t>::type;
+  // staged in LDS: the key unless the pass reads digit-pos words, the position unless it writes
+  // them, the chars in neither of the two
   using SL = ScatterLDS<KT, !DPW1, !DPW0, !(DPW0 || DPW1)>;
-  static_assert(!DS || (BM != 2 && !DPW0 && !DPW1), "no digit stream out of these passes");
-  static_assert(!DPW0 || (KEYS0 && !FROM_SEQ), "the digit-pos words start from V_hist0's ids");
-  static_assert(!DPW1 || (!KEYS0 && !FROM_SEQ), "the digit-pos words' second pass");
-  static_assert(BM == 0 || !NOPOS, "bucket-id and packed streams carry positions");
-  static_assert(!(AOS && KEYS0), "packed streams start from the sequence");
-  // KEYS0 with BM: the first pass over V_hist0's per-window bucket ids (~0: not indexed)
   const KT* __restrict__ kinT = reinterpret_cast<const KT*>(kin);
   KT* __restrict__ koutT = reinterpret_cast<KT*>(kout);
   constexpr int NWV = SC_NWV;
@@ -719,11 +827,12 @@ k_v2_scatter(const uint8_t* __restrict__ seq, int64_t L, int k, int64_t Nw,
       ngb[q] = hist[(size_t)d * ntiles + tv];
     }
   };
-  // the folded bucket-start work (last pass only), before any tile's loads are issued
+  // the folded bucket-start level, over this pass's own input, before any tile's loads are
+  // issued
   if (bf.start)
     for (uint32_t lo = blockIdx.x; lo < bf.div; lo += gridDim.x)
-      bounds_lo_body(lo, &S.wc[0][0], bf.kprev, *n_ptr, g, bf.Dlast, bf.div, hist, ntiles,
-                     bf.lo_start, bf.spread, bf.start, bf.bid, TB, bf.nlim, bf.sh);
+      bounds_lo_body<IN>(lo, &S.wc[0][0], kin, pk.sh, *n_ptr, g, bf.Dlast, bf.div, hist, ntiles,
+                         bf.lo_start, bf.spread, bf.start, TB, bf.nlim);
   // the next tile's inputs are in flight while this one is processed
   KT nkey[PER];
   uint32_t npos[PER];
@@ -743,12 +852,9 @@ k_v2_scatter(const uint8_t* __restrict__ seq, int64_t L, int k, int64_t Nw,
           const uint3 v = reinterpret_cast<const uint3*>(kin)[e];
           nkey[cc] = ((uint64_t)v.y << 32) | v.x;
           npos[cc] = v.z;
-        } else if (P8IN) {
-          nkey[cc] = kinT[e];                  // position restored from the segment table
-          npos[cc] = 0u;
-        } else {
-          nkey[cc] = kinT[e];
-          npos[cc] = NOPOS || DPW1 ? 0u : pin[e];
+        } else {                               // (Packed8: the position is restored from the
+          nkey[cc] = kinT[e];                  // segment table, DigitPos: cut from the word)
+          npos[cc] = POSIN ? pin[e] : 0u;
         }
       }
     }
@@ -802,45 +908,39 @@ k_v2_scatter(const uint8_t* __restrict__ seq, int64_t L, int k, int64_t Nw,
         const uint64_t h = mix64(kk);
         const uint32_t bl = bucket_local(h, g);
         act[c] = act[c] && bl < g.nb;                        // a part build keeps its buckets
-        key[c] = BIDS ? (KT)bl
-                      : P8OUT ? (KT)((kk << pk.sh) | (e & ((1ull << pk.sh) - 1ull))) : (KT)kk;
+        key[c] = P8OUT ? (KT)((kk << pk.sh) | (e & ((1ull << pk.sh) - 1ull))) : (KT)kk;
         dg[c] = act[c] ? digit_of_b(bl, D) : 0;
-      } else if (P8IN) {
-        // key and window index from the packed element; the segment from the element's place
-        // in its pass-0 digit run (segb row of that digit: the largest s with segb[s] <= e)
-        act[c] = e < n;
-        const uint64_t kk = (uint64_t)key[c] >> pk.sh;
-        const uint64_t h = mix64(kk);
-        dg[c] = act[c] ? digit_of_h(h, g, D) : 0;
-        const uint32_t* row = pk.segb + (uint64_t)digit_of_h(h, g, pk.d0) * (pk.nseg + 1);
-        uint32_t lo = 0, hi = pk.nseg;                       // row[0] <= e < row[nseg]
-        while (hi - lo > 1) {
-          const uint32_t mid = (lo + hi) >> 1;
-          if ((uint64_t)row[mid] <= e) lo = mid; else hi = mid;
-        }
-        ps[c] = (uint32_t)((((uint64_t)lo << pk.sh) | ((uint64_t)key[c] & ((1ull << pk.sh) - 1ull))) + 1);
-        key[c] = (KT)kk;
-      } else if (DPW0) {
-        // both digits from one division: this pass's, and the quotient (< R <= 256: two passes)
-        // that is the next pass's, packed over the position (< 2^24)
-        const uint32_t id = (uint32_t)key[c];
-        uint32_t hi;
-        const uint32_t lo = digit_of_b_hi(id, D, hi);
-        act[c] = e < n && id != ~0u;
-        dg[c] = act[c] ? lo : 0;
-        key[c] = (KT)((hi << 24) | ps[c]);
-      } else if (DPW1) {
-        const uint32_t w = (uint32_t)key[c];
-        act[c] = e < n;
-        dg[c] = act[c] ? w >> 24 : 0;
-        ps[c] = w & 0xFFFFFFu;
-      } else if (BIDS) {
-        act[c] = e < n && !(KEYS0 && (uint32_t)key[c] == ~0u);
-        dg[c] = act[c] ? digit_of_b((uint32_t)key[c], D) : 0;
       } else {
-        act[c] = e < n && !(KEYS0 && skip_empty && key[c] == EMPTY_KEY);
-        const uint64_t hk = mix64((uint64_t)key[c]);
-        dg[c] = act[c] ? digit_of_h(hk, g, D) : 0;
+        // a first pass drops what is no element: V_hist0's ~0 ids, a padded stream's empty keys
+        act[c] = e < n && !(KEYS0 && (BIDS ? (uint32_t)key[c] == ~0u
+                                           : skip_empty && (uint64_t)key[c] == EMPTY_KEY));
+        [[maybe_unused]] const uint64_t src = digit_src<IN>(key[c], pk.sh);
+        if constexpr (DPW0) {
+          // both digits from one division: this pass's, and the quotient (< R <= 256: two
+          // passes) that is the next pass's, packed over the position (< 2^24)
+          uint32_t hi;
+          const uint32_t lo = digit_of_b_hi((uint32_t)key[c], D, hi);
+          dg[c] = act[c] ? lo : 0;
+          key[c] = (KT)((hi << BID_POS_BITS) | ps[c]);
+        } else {
+          dg[c] = act[c] ? digit_of_src<IN>(src, g, D) : 0;
+        }
+        if constexpr (P8IN) {
+          // key and window index from the packed element; the segment from the element's place
+          // in its pass-0 digit run (segb row of that digit: the largest s with segb[s] <= e)
+          const uint64_t kk = (uint64_t)key[c] >> pk.sh;
+          const uint32_t d0 = digit_of_src<IN>(src, g, pk.d0);   // the same hash's pass-0 digit
+          const uint32_t* row = pk.segb + (uint64_t)d0 * (pk.nseg + 1);
+          uint32_t lo = 0, hi = pk.nseg;                     // row[0] <= e < row[nseg]
+          while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if ((uint64_t)row[mid] <= e) lo = mid; else hi = mid;
+          }
+          ps[c] = (uint32_t)((((uint64_t)lo << pk.sh) |
+                              ((uint64_t)key[c] & ((1ull << pk.sh) - 1ull))) + 1);
+          key[c] = (KT)kk;
+        }
+        if constexpr (DPW1) ps[c] = (uint32_t)key[c] & ((1u << BID_POS_BITS) - 1u);
       }
     }
     if (!BALLOT) {
@@ -944,8 +1044,7 @@ k_v2_scatter(const uint8_t* __restrict__ seq, int64_t L, int k, int64_t Nw,
         if (POSOUT) pout[dst] = S.spos[i];
       }
       if constexpr (DS) {       // the next pass's digit, from the staged key (no more LDS)
-        const uint64_t kk = P8OUT ? (uint64_t)S.skey[i] >> pk.sh : (uint64_t)S.skey[i];
-        const uint32_t dnx = BIDS ? digit_of_b((uint32_t)kk, dso.Dn) : digit_of(kk, g, dso.Dn);
+        const uint32_t dnx = digit_of_elem<OUT>(S.skey[i], g, dso.Dn, pk.sh);
         // (plain stores: the partial lines merge in the XCD's L2; nontemporal digit stores cost
         // the 500 Mbp build 16.86 -> 19.04 ms, profiles/r5y_variants_large_build_only.txt)
         if (dso.out8) dso.out8[dst] = (uint8_t)dnx;
@@ -953,71 +1052,6 @@ k_v2_scatter(const uint8_t* __restrict__ seq, int64_t L, int k, int64_t Nw,
       }
     }
   }
-}
-
-// ---------------------------------------------------------------- V_bounds_lo
-// Bucket starts from the radix histograms instead of a pass over the sorted keys.  With LSD
-// passes, pass p's input is sorted by lo = c mod div (c = the element's digits 0 .. p combined,
-// div = R^p) and the pass places elements by its own digit hi, stably, so
-//   S_p[hi * div + lo] = #(digit < hi) + #(digit == hi and lo' < lo)
-//                      = hist_p[hi][t] + #(digit hi among the pass's input [t * PTILE, P_lo))
-// where P_lo = S_(p-1)[lo] = #(lo' < lo) is the start of lo in that input (for p = 1 pass 0's
-// scanned column 0, saved by V_hist) and t = P_lo / PTILE: one workgroup per lo value counts at
-// most one partial tile.  S_p of the last pass are the bucket starts; the earlier levels (3+
-// passes) keep S_p (R^(p+1) entries, `nlim`) for the next.  Each level rides in its pass's
-// scatter (BoundsFuse) -- it needs that pass's scanned histogram and its input, both live
-// there -- so no key pass and no launch of its own.  Interleaved schedule only (one histogram
-// column per tile).  `spread` (count-only builds): start[b / spread] for the buckets b that are
-// multiples of spread.
-__device__ __forceinline__ void bounds_lo_body(uint32_t lo, uint32_t* cnt,
-                                               const uint64_t* __restrict__ kprev, uint32_t n,
-                                               Geom g, Digit Dlast, uint32_t div,
-                                               const uint32_t* __restrict__ hist, uint32_t C,
-                                               const uint32_t* __restrict__ lo_start,
-                                               uint32_t spread, uint32_t* __restrict__ start,
-                                               int bid, int tb, uint32_t nlim, int sh = 0) {
-  const uint32_t R = Dlast.R;
-  const uint32_t P = lo_start ? lo_start[lo] : 0u;
-  for (uint32_t d = threadIdx.x; d < R; d += tb) cnt[d] = 0;
-  __syncthreads();
-  const uint32_t tile = P / PTILE;
-  for (uint32_t i = tile * PTILE + threadIdx.x; i < P; i += tb) {
-    uint32_t dg;
-    if (bid == 1) {                        // bucket ids
-      dg = digit_of_b(reinterpret_cast<const uint32_t*>(kprev)[i], Dlast);
-    } else if (bid == 2) {                 // packed (key, pos) elements
-      const uint32_t* w = reinterpret_cast<const uint32_t*>(kprev) + 3 * (uint64_t)i;
-      dg = digit_of(((uint64_t)w[1] << 32) | w[0], g, Dlast);
-    } else if (bid == 3) {                 // packed 8-B elements: key << sh | window
-      dg = digit_of(kprev[i] >> sh, g, Dlast);
-    } else if (bid == 4) {                 // digit-pos words: this pass's digit << 24 | pos
-      dg = reinterpret_cast<const uint32_t*>(kprev)[i] >> 24;
-    } else {
-      dg = digit_of(kprev[i], g, Dlast);
-    }
-    atomicAdd(&cnt[dg], 1u);
-  }
-  __syncthreads();
-  for (uint32_t hi = threadIdx.x; hi < R; hi += tb) {
-    const uint64_t b = (uint64_t)hi * div + lo;
-    if (b >= nlim || b % spread) continue;
-    // P == n on a tile boundary past the last column: the end of digit hi
-    const uint32_t base = tile < C ? hist[(size_t)hi * C + tile]
-                                   : (hi + 1 < R ? hist[(size_t)(hi + 1) * C] : n);
-    start[b / spread] = base + cnt[hi];
-  }
-  if (lo == 0 && threadIdx.x == 0) start[nlim / spread] = n;
-  __syncthreads();                         // cnt is the caller's LDS: free again
-}
-
-__global__ void __launch_bounds__(BLOCK)
-k_v2_bounds_lo(const uint64_t* __restrict__ kprev, const uint32_t* __restrict__ n_ptr, Geom g,
-               Digit Dlast, uint32_t div, const uint32_t* __restrict__ hist, uint32_t C,
-               const uint32_t* __restrict__ lo_start, uint32_t spread,
-               uint32_t* __restrict__ start, int bid, uint32_t nlim, int sh) {
-  __shared__ uint32_t cnt[V2_MAXR];
-  bounds_lo_body(blockIdx.x, cnt, kprev, *n_ptr, g, Dlast, div, hist, C, lo_start, spread, start,
-                 bid, BLOCK, nlim, sh);
 }
 
 // Pack8's segment table: segb[d * (nseg + 1) + s] = where segment s (tiles [s tps, (s + 1) tps))
@@ -1766,29 +1800,6 @@ static inline unsigned grid_of(uint64_t n, unsigned per) {
 // kernels.  KMHG_TEST_BALLOT=1 (tests) forces them.
 bool ballot_ranks();
 
-#define KMHG_SCATTER_X(FS, K0, NP, BM, DSF, DSO, ...)                                         \
-  do {                                                                                       \
-    if (ballot_ranks()) {                                                                    \
-      static const unsigned cap_ =                                                           \
-          resident_blocks((const void*)k_v2_scatter<FS, K0, NP, BM, true, DSF>, SC_NWV * 64); \
-      hipLaunchKernelGGL((k_v2_scatter<FS, K0, NP, BM, true, DSF>), dim3(std::min(ntiles, cap_)), \
-                         dim3(SC_NWV * 64), 0, s, __VA_ARGS__, DSO);                         \
-    } else {                                                                                 \
-      static const unsigned cap_ =                                                           \
-          resident_blocks((const void*)k_v2_scatter<FS, K0, NP, BM, false, DSF>, SC_NWV * 64); \
-      hipLaunchKernelGGL((k_v2_scatter<FS, K0, NP, BM, false, DSF>), dim3(std::min(ntiles, cap_)), \
-                         dim3(SC_NWV * 64), 0, s, __VA_ARGS__, DSO);                         \
-    }                                                                                        \
-  } while (0)
-#define KMHG_SCATTER_BM(FS, K0, NP, BM, ...) KMHG_SCATTER_X(FS, K0, NP, BM, false, kNoDigits, __VA_ARGS__)
-// the same pass also writing the next pass's digits (dso)
-#define KMHG_SCATTER_BMD(FS, K0, NP, BM, DSO, ...)                                            \
-  do {                                                                                       \
-    if (DSO.out || DSO.out8) KMHG_SCATTER_X(FS, K0, NP, BM, true, DSO, __VA_ARGS__);                      \
-    else KMHG_SCATTER_X(FS, K0, NP, BM, false, kNoDigits, __VA_ARGS__);                       \
-  } while (0)
-#define KMHG_SCATTER(FS, K0, NP, ...) KMHG_SCATTER_BM(FS, K0, NP, 0, __VA_ARGS__)
-
 void launch_v2_hist0(const uint8_t* seq, int64_t L, int k, int64_t Nw, Geom g, Digit D,
                      uint32_t* hist, uint32_t ntiles, uint64_t* scan_status, uint32_t n_status,
                      BuildMeta* meta, hipStream_t s, uint32_t* code, uint16_t* nbit,
@@ -1838,76 +1849,54 @@ void launch_scan_u32(uint32_t* a, uint64_t n, uint64_t* status, uint32_t* total,
     hipLaunchKernelGGL(k_scan_lb_u32<WPT>, dim3(nt), dim3(BLOCK), 0, s, a, n, status, nt, total);
   }
 }
-void launch_v2_hist_bid(const uint32_t* bids, const uint32_t* n_ptr, Geom g, Digit D,
-                        uint32_t* hist, uint32_t ntiles, uint64_t* scan_status, uint32_t n_status,
-                        hipStream_t s, uint32_t* save_col0, bool dpw) {
-  if (dpw) {                   // digit-pos words: the digit is w >> 24
-    static const unsigned cap = resident_blocks((const void*)k_v2_histp<6>);
-    hipLaunchKernelGGL(k_v2_histp<6>, dim3(std::min<unsigned>(ntiles, cap)), dim3(BLOCK), 0, s,
-                       reinterpret_cast<const uint64_t*>(bids), n_ptr, g, D, hist, ntiles,
-                       scan_status, n_status, save_col0, 0);
-    return;
-  }
-  static const unsigned cap = resident_blocks((const void*)k_v2_histp<1>);
-  hipLaunchKernelGGL(k_v2_histp<1>, dim3(std::min<unsigned>(ntiles, cap)), dim3(BLOCK), 0, s,
-                     reinterpret_cast<const uint64_t*>(bids), n_ptr, g, D, hist, ntiles,
-                     scan_status, n_status, save_col0, 0);
+template <StreamFmt IN>
+static void histp_launch(const void* in, const uint32_t* n_ptr, Geom g, Digit D, uint32_t* hist,
+                         uint32_t ntiles, uint64_t* scan_status, uint32_t n_status, hipStream_t s,
+                         uint32_t* save_col0, int sh) {
+  static const unsigned cap = resident_blocks((const void*)k_v2_histp<IN>);
+  hipLaunchKernelGGL(k_v2_histp<IN>, dim3(std::min<unsigned>(ntiles, cap)), dim3(BLOCK), 0, s,
+                     reinterpret_cast<const uint64_t*>(in), n_ptr, g, D, hist, ntiles,
+                     scan_status, n_status, save_col0, sh);
 }
-void launch_v2_hist_digits(const void* digits, bool u8, const uint32_t* n_ptr, Geom g, Digit D,
-                           uint32_t* hist, uint32_t ntiles, uint64_t* scan_status,
-                           uint32_t n_status, hipStream_t s, uint32_t* save_col0) {
-  if (u8) {
-    static const unsigned cap = resident_blocks((const void*)k_v2_histp<5>);
-    hipLaunchKernelGGL(k_v2_histp<5>, dim3(std::min<unsigned>(ntiles, cap)), dim3(BLOCK), 0, s,
-                       reinterpret_cast<const uint64_t*>(digits), n_ptr, g, D, hist, ntiles,
-                       scan_status, n_status, save_col0, 0);
-    return;
+void launch_v2_hist(StreamFmt fmt, const void* in, const uint32_t* n_ptr, Geom g, Digit D,
+                    uint32_t* hist, uint32_t ntiles, uint64_t* scan_status, uint32_t n_status,
+                    hipStream_t s, uint32_t* save_col0, int sh) {
+#define KMHG_HISTP(F)                                                                          \
+  case StreamFmt::F:                                                                           \
+    return histp_launch<StreamFmt::F>(in, n_ptr, g, D, hist, ntiles, scan_status, n_status, s,  \
+                                      save_col0, sh)
+  switch (fmt == StreamFmt::Keys ? StreamFmt::KeyPos : fmt) {   // the key array alone is read
+    KMHG_HISTP(KeyPos);
+    KMHG_HISTP(Packed12);
+    KMHG_HISTP(Packed8);
+    KMHG_HISTP(BidPos);
+    KMHG_HISTP(DigitPos);
+    KMHG_HISTP(Digits8);
+    KMHG_HISTP(Digits16);
+    default: std::abort();     // Bids and Pos streams are no pass's histogram input
   }
-  static const unsigned cap = resident_blocks((const void*)k_v2_histp<4>);
-  hipLaunchKernelGGL(k_v2_histp<4>, dim3(std::min<unsigned>(ntiles, cap)), dim3(BLOCK), 0, s,
-                     reinterpret_cast<const uint64_t*>(digits), n_ptr, g, D, hist, ntiles,
-                     scan_status, n_status, save_col0, 0);
+#undef KMHG_HISTP
 }
-void launch_v2_hist(const uint64_t* keys, const uint32_t* n_ptr, Geom g, Digit D, uint32_t* hist,
-                    uint32_t ntiles, uint64_t* scan_status, uint32_t n_status, hipStream_t s,
-                    uint32_t* hll_rows, uint32_t* hll_regs, uint32_t* save_col0, bool skip_empty,
-                    bool padded, bool aos, int sh8) {
-  if (sh8) {                   // packed 8-B (key << sh | window) stream
-    static const unsigned cap = resident_blocks((const void*)k_v2_histp<3>);
-    hipLaunchKernelGGL(k_v2_histp<3>, dim3(std::min<unsigned>(ntiles, cap)), dim3(BLOCK), 0,
-                       s, keys, n_ptr, g, D, hist, ntiles, scan_status, n_status, save_col0, sh8);
-    return;
-  }
-  if (aos) {                   // packed (key, pos) stream (padded by construction)
-    static const unsigned cap = resident_blocks((const void*)k_v2_histp<2>);
-    hipLaunchKernelGGL(k_v2_histp<2>, dim3(std::min<unsigned>(ntiles, cap)), dim3(BLOCK), 0,
-                       s, keys, n_ptr, g, D, hist, ntiles, scan_status, n_status, save_col0, 0);
-    return;
-  }
-  if (padded && !hll_rows && !skip_empty) {
-    static const unsigned cap = resident_blocks((const void*)k_v2_histp<0>);
-    hipLaunchKernelGGL(k_v2_histp<0>, dim3(std::min<unsigned>(ntiles, cap)), dim3(BLOCK), 0,
-                       s, keys, n_ptr, g, D, hist, ntiles, scan_status, n_status, save_col0, 0);
-    return;
-  }
+void launch_v2_hist_keys0(const uint64_t* keys, const uint32_t* n_ptr, Geom g, Digit D,
+                          uint32_t* hist, uint32_t ntiles, uint64_t* scan_status,
+                          uint32_t n_status, hipStream_t s, uint32_t* hll_rows,
+                          uint32_t* hll_regs, bool skip_empty) {
   if (hll_rows)
     hipLaunchKernelGGL(k_v2_hist<true>, dim3(ntiles), dim3(BLOCK), 0, s, keys, n_ptr, g, D, hist,
-                       ntiles, scan_status, n_status, hll_rows, hll_regs, save_col0,
+                       ntiles, scan_status, n_status, hll_rows, hll_regs, nullptr,
                        skip_empty ? 1 : 0);
   else
     hipLaunchKernelGGL(k_v2_hist<false>, dim3(ntiles), dim3(BLOCK), 0, s, keys, n_ptr, g, D, hist,
-                       ntiles, scan_status, n_status, nullptr, nullptr, save_col0,
+                       ntiles, scan_status, n_status, nullptr, nullptr, nullptr,
                        skip_empty ? 1 : 0);
 }
-void launch_v2_bounds_lo(const uint64_t* kprev, const uint32_t* n_ptr, Geom g, Digit Dlast,
-                         uint32_t div, const uint32_t* hist, uint32_t C, const uint32_t* lo_start,
-                         uint32_t spread, uint32_t* start, uint32_t nlim, hipStream_t s,
-                         const uint32_t* bprev, bool aos, int sh8, bool dpw) {
+void launch_v2_bounds_lo(StreamFmt fmt, const void* in, const uint32_t* n_ptr, Geom g,
+                         Digit Dlast, uint32_t div, const uint32_t* hist, uint32_t C,
+                         const uint32_t* lo_start, uint32_t spread, uint32_t* start,
+                         uint32_t nlim, hipStream_t s, int sh) {
   hipLaunchKernelGGL(k_v2_bounds_lo, dim3(div), dim3(BLOCK), 0, s,
-                     bprev ? reinterpret_cast<const uint64_t*>(bprev) : kprev, n_ptr, g, Dlast,
-                     div, hist, C, lo_start, spread, start,
-                     bprev ? (dpw ? 4 : 1) : sh8 ? 3 : aos ? 2 : 0,
-                     nlim, sh8);
+                     fmt == StreamFmt::Keys ? StreamFmt::KeyPos : fmt, in, sh, n_ptr, g, Dlast,
+                     div, hist, C, lo_start, spread, start, nlim);
 }
 void launch_seg_bounds(const uint32_t* hist, uint32_t ntiles, uint32_t R, uint32_t nseg,
                        uint32_t tps, const uint32_t* n_valid, uint32_t* segb, hipStream_t s) {
@@ -1921,109 +1910,100 @@ void launch_v2_hll(const uint32_t* hll_rows, uint32_t n_rows, uint32_t* hll_regs
   hipLaunchKernelGGL(k_v2_hll_final, dim3(1), dim3(HLL_T), 0, s, hll_regs, g, host_est, n_valid,
                      host_n);
 }
-static const BoundsFuse kNoFuse{nullptr, nullptr, nullptr, Digit{}, 0u, 1u, 0, 0u};
-static const Pack8 kNoPack{0, nullptr, 0u, Digit{}};
-void launch_v2_scatter_seq(const uint8_t* seq, int64_t L, int k, int64_t Nw, Geom g, Digit D,
-                           const uint32_t* hist, uint32_t ntiles, uint64_t* kout, uint32_t* pout,
-                           uint32_t pad, hipStream_t s, bool aos, const Pack8* pk,
-                           const DigitOut* ds) {
-  const DigitOut dso = ds ? *ds : kNoDigits;
-  if (pk && pk->sh)
-    KMHG_SCATTER_BMD(true, false, false, 6, dso, seq, L, k, Nw, nullptr, nullptr, nullptr, g, D,
-                     hist, ntiles, kout, nullptr, pad, 0, kNoFuse, *pk);
-  else if (aos)
-    KMHG_SCATTER_BMD(true, false, false, 3, dso, seq, L, k, Nw, nullptr, nullptr, nullptr, g, D,
-                     hist, ntiles, kout, nullptr, pad, 0, kNoFuse, kNoPack);
-  else
-    KMHG_SCATTER_BMD(true, false, false, 0, dso, seq, L, k, Nw, nullptr, nullptr, nullptr, g, D,
-                     hist, ntiles, kout, pout, pad, 0, kNoFuse, kNoPack);
-}
 void launch_part_dense(const uint64_t* ck, const uint32_t* cp, const uint32_t* off,
-                       uint32_t ntiles, const uint32_t* n_total, uint64_t* dk, uint32_t* dp,
-                       hipStream_t s, bool aos) {
-  if (aos)
-    hipLaunchKernelGGL(k_part_dense<true>, dim3(std::min<uint32_t>(ntiles, 8192u)), dim3(BLOCK), 0,
-                       s, ck, cp, off, ntiles, n_total, dk, dp);
+                       uint32_t ntiles, const uint32_t* n_total, void* dk, uint32_t* dp,
+                       StreamFmt out, hipStream_t s) {
+  const dim3 gr(std::min<uint32_t>(ntiles, 8192u)), bl(BLOCK);
+  uint64_t* dk64 = reinterpret_cast<uint64_t*>(dk);
+  if (out == StreamFmt::Packed12)
+    hipLaunchKernelGGL(k_part_dense<true>, gr, bl, 0, s, ck, cp, off, ntiles, n_total, dk64, dp);
   else
-    hipLaunchKernelGGL(k_part_dense<false>, dim3(std::min<uint32_t>(ntiles, 8192u)), dim3(BLOCK), 0,
-                       s, ck, cp, off, ntiles, n_total, dk, dp);
+    hipLaunchKernelGGL(k_part_dense<false>, gr, bl, 0, s, ck, cp, off, ntiles, n_total, dk64, dp);
 }
-void launch_v2_scatter_bid0(const uint32_t* bids, int64_t Nw, Geom g, Digit D,
-                            const uint32_t* hist, uint32_t ntiles, uint32_t* bout, uint32_t* pout,
-                            uint32_t pad, hipStream_t s, const DigitOut* ds, bool dpw) {
-  const uint64_t* ki = reinterpret_cast<const uint64_t*>(bids);
-  uint64_t* ko = reinterpret_cast<uint64_t*>(bout);
-  const DigitOut dso = ds ? *ds : kNoDigits;
-  if (dpw)                     // digit-pos words out (bout), pout unused
-    KMHG_SCATTER_BM(false, true, false, 8, nullptr, (int64_t)0, 0, Nw, ki, nullptr, nullptr, g,
-                    D, hist, ntiles, ko, nullptr, pad, 0, kNoFuse, kNoPack);
-  else if (bout)
-    KMHG_SCATTER_BMD(false, true, false, 1, dso, nullptr, (int64_t)0, 0, Nw, ki, nullptr, nullptr,
-                     g, D, hist, ntiles, ko, pout, pad, 0, kNoFuse, kNoPack);
-  else
-    KMHG_SCATTER_BM(false, true, false, 2, nullptr, (int64_t)0, 0, Nw, ki, nullptr, nullptr, g,
-                    D, hist, ntiles, ko, pout, pad, 0, kNoFuse, kNoPack);
+
+// One (FROM_SEQ, KEYS0, IN, OUT) pass: the lane-order or the ballot-rank instance, each on its
+// own persistent grid; scatter_launch_ds: the pass may also write the next pass's digits.
+struct ScatterArgs {
+  ScatterIn in;
+  uint64_t* kout;
+  uint32_t* pout;
+  uint32_t pad;
+  const uint32_t* n_ptr;
+  Geom g;
+  Digit D;
+  const uint32_t* hist;
+  uint32_t ntiles;
+  hipStream_t s;
+  BoundsFuse bf;
+  Pack8 pk;
+  DigitOut dso;
+};
+template <bool FS, bool K0, StreamFmt IN, StreamFmt OUT, bool BAL, bool DS>
+static void scatter_launch1(const ScatterArgs& a) {
+  static const unsigned cap =
+      resident_blocks((const void*)k_v2_scatter<FS, K0, IN, OUT, BAL, DS>, SC_NWV * 64);
+  hipLaunchKernelGGL((k_v2_scatter<FS, K0, IN, OUT, BAL, DS>), dim3(std::min(a.ntiles, cap)),
+                     dim3(SC_NWV * 64), 0, a.s, a.in.seq, a.in.L, a.in.k, a.in.n0,
+                     reinterpret_cast<const uint64_t*>(a.in.kin), a.in.pin, a.n_ptr, a.g, a.D,
+                     a.hist, a.ntiles, a.kout, a.pout, a.pad, a.in.skip_empty ? 1 : 0, a.bf, a.pk,
+                     a.dso);
 }
-void launch_v2_scatter_bid(const uint32_t* bin, const uint32_t* pin, const uint32_t* n_ptr,
-                           Geom g, Digit D, const uint32_t* hist, uint32_t ntiles, uint32_t* bout,
-                           uint32_t* pout, uint32_t pad, hipStream_t s, const BoundsFuse* bf,
-                           const DigitOut* ds, bool dpw) {
-  const uint64_t* ki = reinterpret_cast<const uint64_t*>(bin);
-  uint64_t* ko = reinterpret_cast<uint64_t*>(bout);
-  const BoundsFuse f = bf ? *bf : kNoFuse;
-  const DigitOut dso = ds ? *ds : kNoDigits;
-  if (dpw)                     // digit-pos words in (bin; pin unused), positions out
-    KMHG_SCATTER_BM(false, false, false, 9, nullptr, (int64_t)0, 0, (int64_t)0, ki, nullptr,
-                    n_ptr, g, D, hist, ntiles, nullptr, pout, pad, 0, f, kNoPack);
-  else if (bout)
-    KMHG_SCATTER_BMD(false, false, false, 1, dso, nullptr, (int64_t)0, 0, (int64_t)0, ki, pin,
-                     n_ptr, g, D, hist, ntiles, ko, pout, pad, 0, f, kNoPack);
-  else
-    KMHG_SCATTER_BM(false, false, false, 2, nullptr, (int64_t)0, 0, (int64_t)0, ki, pin, n_ptr,
-                    g, D, hist, ntiles, ko, pout, pad, 0, f, kNoPack);
+template <bool FS, bool K0, StreamFmt IN, StreamFmt OUT, bool DS = false>
+static void scatter_launch(const ScatterArgs& a) {
+  if (ballot_ranks()) scatter_launch1<FS, K0, IN, OUT, true, DS>(a);
+  else scatter_launch1<FS, K0, IN, OUT, false, DS>(a);
 }
-void launch_v2_scatter(const uint64_t* kin, const uint32_t* pin, const uint32_t* n_ptr, Geom g,
-                       Digit D, const uint32_t* hist, uint32_t ntiles, uint64_t* kout,
-                       uint32_t* pout, uint32_t pad, hipStream_t s, const BoundsFuse* bf,
-                       bool aos, bool aos_in, const Pack8* pk, const DigitOut* ds) {
-  const DigitOut dso = ds ? *ds : kNoDigits;
-  if (pk && pk->sh)            // packed 8-B elements in, packed 12-B out (a last pass)
-    KMHG_SCATTER_BM(false, false, false, 7, nullptr, (int64_t)0, 0, (int64_t)0, kin, nullptr,
-                    n_ptr, g, D, hist, ntiles, kout, nullptr, pad, 0, bf ? *bf : kNoFuse, *pk);
-  else if (aos && aos_in)
-    KMHG_SCATTER_BMD(false, false, false, 3, dso, nullptr, (int64_t)0, 0, (int64_t)0, kin,
-                     nullptr, n_ptr, g, D, hist, ntiles, kout, nullptr, pad, 0,
-                     bf ? *bf : kNoFuse, kNoPack);
-  else if (aos)
-    KMHG_SCATTER_BMD(false, false, false, 4, dso, nullptr, (int64_t)0, 0, (int64_t)0, kin, pin,
-                     n_ptr, g, D, hist, ntiles, kout, nullptr, pad, 0, bf ? *bf : kNoFuse,
-                     kNoPack);
-  else
-    KMHG_SCATTER_BMD(false, false, false, 0, dso, nullptr, (int64_t)0, 0, (int64_t)0, kin, pin,
-                     n_ptr, g, D, hist, ntiles, kout, pout, pad, 0, bf ? *bf : kNoFuse, kNoPack);
+template <bool FS, bool K0, StreamFmt IN, StreamFmt OUT>
+static void scatter_launch_ds(const ScatterArgs& a) {
+  if (a.dso.out || a.dso.out8) scatter_launch<FS, K0, IN, OUT, true>(a);
+  else scatter_launch<FS, K0, IN, OUT, false>(a);
 }
-void launch_v2_scatter_keys0(const uint64_t* kin, uint64_t n_keys, const uint32_t* n_ptr, Geom g,
-                             Digit D, const uint32_t* hist, uint32_t ntiles, uint64_t* kout,
-                             uint32_t* pout, uint32_t pad, bool nopos, bool skip_empty,
-                             hipStream_t s) {
-  if (nopos)
-    KMHG_SCATTER(false, true, true, nullptr, (int64_t)0, 0, (int64_t)n_keys, kin, nullptr, n_ptr,
-                 g, D, hist, ntiles, kout, nullptr, pad, skip_empty ? 1 : 0, kNoFuse, kNoPack);
-  else
-    KMHG_SCATTER(false, true, false, nullptr, (int64_t)0, 0, (int64_t)n_keys, kin, nullptr,
-                 n_ptr, g, D, hist, ntiles, kout, pout, pad, skip_empty ? 1 : 0, kNoFuse, kNoPack);
+constexpr int pass_id(int src, StreamFmt i, StreamFmt o) {
+  return (src * 16 + (int)i) * 16 + (int)o;
 }
-void launch_v2_scatter_nopos(const uint64_t* kin, const uint32_t* n_ptr, Geom g, Digit D,
-                             const uint32_t* hist, uint32_t ntiles, uint64_t* kout, uint32_t pad,
-                             hipStream_t s, const BoundsFuse* bf) {
-  KMHG_SCATTER(false, false, true, nullptr, (int64_t)0, 0, (int64_t)0, kin, nullptr, n_ptr, g, D,
-               hist, ntiles, kout, nullptr, pad, 0, bf ? *bf : kNoFuse, kNoPack);
+void launch_v2_scatter(const ScatterIn& in, StreamFmt fin, StreamFmt fout, void* kout,
+                       uint32_t* pout, uint32_t pad, const uint32_t* n_ptr, Geom g, Digit D,
+                       const uint32_t* hist, uint32_t ntiles, hipStream_t s, const BoundsFuse* bf,
+                       const Pack8* pk, const DigitOut* ds) {
+  using F = StreamFmt;
+  const ScatterArgs a{in, reinterpret_cast<uint64_t*>(kout), pout, pad, n_ptr, g, D, hist, ntiles,
+                      s, bf ? *bf : BoundsFuse{nullptr, nullptr, Digit{}, 0u, 1u, 0u},
+                      pk ? *pk : Pack8{0, nullptr, 0u, Digit{}}, ds ? *ds : kNoDigits};
+  // every pass there is: its source (SEQ the sequence, FIRST a first pass with implicit
+  // positions, 0 a stream), IN -> OUT, and whether it may also write digits (_ds)
+  enum { SEQ = 2, FIRST = 1 };
+#define KMHG_PASS(SRC, I, O, LAUNCH)                                                           \
+  case pass_id(SRC, F::I, F::O):                                                               \
+    return LAUNCH<SRC == SEQ, SRC == FIRST, F::I, F::O>(a)
+  switch (pass_id(in.seq ? SEQ : in.first ? FIRST : 0, fin, fout)) {
+    KMHG_PASS(SEQ, Keys, KeyPos, scatter_launch_ds);
+    KMHG_PASS(SEQ, Keys, Packed12, scatter_launch_ds);
+    KMHG_PASS(SEQ, Keys, Packed8, scatter_launch_ds);
+    KMHG_PASS(FIRST, Keys, Keys, scatter_launch);
+    KMHG_PASS(FIRST, Keys, KeyPos, scatter_launch);
+    KMHG_PASS(FIRST, Bids, BidPos, scatter_launch_ds);
+    KMHG_PASS(FIRST, Bids, DigitPos, scatter_launch);
+    KMHG_PASS(FIRST, Bids, Pos, scatter_launch);
+    KMHG_PASS(0, Keys, Keys, scatter_launch);
+    KMHG_PASS(0, KeyPos, KeyPos, scatter_launch_ds);
+    KMHG_PASS(0, KeyPos, Packed12, scatter_launch_ds);
+    KMHG_PASS(0, Packed12, Packed12, scatter_launch_ds);
+    KMHG_PASS(0, Packed8, Packed12, scatter_launch);
+    KMHG_PASS(0, BidPos, BidPos, scatter_launch_ds);
+    KMHG_PASS(0, BidPos, Pos, scatter_launch);
+    KMHG_PASS(0, DigitPos, Pos, scatter_launch);
+    default: std::abort();     // not a pair of formats a pass converts (scatter_pair_ok)
+  }
+#undef KMHG_PASS
 }
-void launch_v2_bucket_wg(const uint64_t* keys, const uint32_t* pos, const uint32_t* start, Geom g,
-                         Slot* T, int32_t* positions, BucketStats* bstats, BuildMeta* meta,
-                         bool count_only, hipStream_t s, const uint32_t* n_ptr, uint32_t nw,
-                         const uint32_t* code, int k, bool aos, uint8_t* TG, uint32_t* rep,
-                         bool place, uint32_t* place_ctr) {
+void launch_v2_bucket_wg(StreamFmt fmt, const void* keys_, const uint32_t* pos,
+                         const uint32_t* start, Geom g, Slot* T, int32_t* positions,
+                         BucketStats* bstats, BuildMeta* meta, hipStream_t s,
+                         const uint32_t* n_ptr, uint32_t nw, const uint32_t* code, int k,
+                         uint8_t* TG, uint32_t* rep, bool place, uint32_t* place_ctr) {
+  const uint64_t* keys = reinterpret_cast<const uint64_t*>(keys_);
+  const bool count_only = fmt == StreamFmt::Keys, aos = fmt == StreamFmt::Packed12;
+  if (fmt != StreamFmt::Pos) code = nullptr;     // only bucket-id builds cut keys from the code
   const bool ballot = ballot_ranks();
   const bool tags = TG != nullptr && !count_only && !code;
   const dim3 gr(g.nb), bl(BLOCK);
@@ -2101,9 +2081,11 @@ __global__ void k_v2_test_disorder(uint32_t* __restrict__ pos, uint32_t* __restr
     }
   }
 }
-void launch_v2_test_disorder(uint32_t* pos, uint32_t* start, const uint32_t* n_ptr, int mode,
-                             hipStream_t s, uint32_t stride) {
-  hipLaunchKernelGGL(k_v2_test_disorder, dim3(1), dim3(64), 0, s, pos, start, n_ptr, mode, stride);
+void launch_v2_test_disorder(StreamFmt fmt, void* keys, uint32_t* pos, uint32_t* start,
+                             const uint32_t* n_ptr, int mode, hipStream_t s) {
+  uint32_t* words = fmt_pos_array(fmt) ? pos : reinterpret_cast<uint32_t*>(keys);
+  hipLaunchKernelGGL(k_v2_test_disorder, dim3(1), dim3(64), 0, s, words + fmt_pos_word(fmt), start,
+                     n_ptr, mode, fmt_pos_stride(fmt));
 }
 void launch_v2_stats(const BucketStats* bstats, uint32_t nb, const uint32_t* n_valid,
                      BuildMeta* meta, BuildMeta* host_meta, hipStream_t s) {

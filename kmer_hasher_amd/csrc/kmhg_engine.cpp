@@ -1366,24 +1366,61 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
   auto packed = [&](int p) {
     return aos && (p + 1 == (int)passes || R >= AOS_MIN_RADIX || ds_pack);
   };
-  bool any_unpacked = !aos;
-  for (int p = -1; p + 1 < (int)passes; ++p) any_unpacked |= !packed(p) && !(pack8 && p == 0);
-  const uint64_t kwords = bid ? 1 : aos ? ((uint64_t)(Nw + PTILE) * 3 + 1) / 2 : (uint64_t)(Nw + PTILE);
-  DBuf<uint64_t> kA(kwords, s), kB(kwords, s);   // + pad
+  const bool no_pos = count_only;                        // keys only through the passes
+  // a part of 4+ (key streams): V_hist0 also writes the part's windows compacted per tile into
+  // side 1's arrays (free until then) with their counts; a scan of the counts and one copy make
+  // them a dense (key, position) stream of ~1/n_parts of the windows, and every radix pass runs
+  // over that alone -- instead of encoding and hashing every window again in a first pass over
+  // all of them.  It costs a copy and one more pass over the part's windows, so it pays from 4
+  // parts on (one-GPU rehearsal, tools/part_step.py, per-rank step of 10 Mbp per part: 2 parts
+  // 0.397 -> 0.467 ms, 4 parts 0.504 -> 0.495, 8 parts 0.749 -> 0.581).  KMHG_PART_COMPACT=0 / 1
+  // forces the first pass over every window / the compaction (tests).
+  const char* pce = test_build_knob("KMHG_PART_COMPACT");
+  const bool partc = !from_keys && n_parts >= 2 && !bid && codes &&
+                     (pce ? pce[0] == '1' : n_parts >= 4);
+  // The plan's outcome, once: F(p) = the format of the stream pass p writes, F(-1) = what the
+  // first radix pass reads (the windows of the sequence and a caller's key stream are Keys,
+  // positions implicit).  Everything below -- buffer sizes, which kernel instance a pass, its
+  // histogram, its bucket-start level and the bucket kernel take -- reads this table.
+  std::vector<StreamFmt> fmt(passes + 1);
+  auto F = [&](int p) -> StreamFmt& { return fmt[(size_t)(p + 1)]; };
+  F(-1) = bid ? StreamFmt::Bids : partc && packed(-1) ? StreamFmt::Packed12
+          : partc ? StreamFmt::KeyPos : StreamFmt::Keys;
+  for (int p = 0; p < (int)passes; ++p) {
+    const bool last = p + 1 == (int)passes;
+    F(p) = no_pos ? StreamFmt::Keys
+           : bid  ? (last ? StreamFmt::Pos : bid_pack ? StreamFmt::DigitPos : StreamFmt::BidPos)
+           : pack8 && p == 0 ? StreamFmt::Packed8
+           : packed(p)       ? StreamFmt::Packed12
+                             : StreamFmt::KeyPos;
+  }
+  // pass p also writes the next pass's digits, which that pass's histogram reads instead of F(p)
+  auto ds_out = [&](int p) { return ds_on && p >= 0 && p + 1 < (int)passes; };
+  // Stream p lives on side p mod 2 of two (first array, position array) buffer pairs -- flipped
+  // where the radix passes start at pass 0 in the loop below, so that their first output lands
+  // on side 1 -- each side sized for the widest stream it holds (+ pad).  F(-1) is stored here
+  // only where V_hist0 / V_part_dense wrote it (ids, a part's dense stream).
   // (Removed in round 4 after measurement, DESIGN.md §5: radix passes writing whole 128-B lines
   // through LDS write-combining buffers -- config 3 29.2 -> 25.0-28.7 Gbp/s, the 500 Mbp build
   // 18.1 -> 18.9-22.7 ms.)
-  // bucket ids: pass p writes bA / bB alternately; the last pass writes none (the bucket starts
-  // come from the histograms)
-  // (bB first holds V_hist0's per-window ids, the first pass's input)
-  DBuf<uint32_t> bA(bid && passes > 1 ? Nw + PTILE : 1, s);
-  DBuf<uint32_t> bB(bid ? Nw + PTILE : 1, s);
-  const bool no_pos = count_only;                        // keys only through the passes
-  // (a part build's compacted windows land in kB / pB before they are packed: pB stays)
-  const bool partc_pos = !from_keys && n_parts >= 2 && codes;
-  // (digit-pos words: pass 0 writes bA alone, pass 1 writes pB)
-  DBuf<uint32_t> pA(no_pos || !any_unpacked || bid_pack ? 1 : Nw + PTILE, s),
-      pB(no_pos || (!any_unpacked && !partc_pos) ? 1 : Nw + PTILE, s);
+  auto side = [&](int p) { return (p & 1) ^ (from_keys || partc ? 1 : 0); };
+  uint32_t key_bytes[2] = {0, 0};
+  bool pos_array[2] = {false, false};
+  for (int p = bid || partc ? -1 : 0; p < (int)passes; ++p) {
+    key_bytes[side(p)] = std::max(key_bytes[side(p)], fmt_key_bytes(F(p)));
+    pos_array[side(p)] |= fmt_pos_array(F(p));
+  }
+  if (partc) {                 // the compacted tiles: u64 keys and positions on side 1
+    key_bytes[1] = std::max(key_bytes[1], 8u);
+    pos_array[1] = true;
+  }
+  auto kwords = [&](int sd) { return ((uint64_t)(Nw + PTILE) * key_bytes[sd] + 7) / 8; };
+  DBuf<uint64_t> kA(kwords(0), s), kB(kwords(1), s);
+  DBuf<uint32_t> pA(pos_array[0] ? Nw + PTILE : 1, s), pB(pos_array[1] ? Nw + PTILE : 1, s);
+  auto kptr = [&](int p) -> void* {
+    return p < 0 && from_keys ? const_cast<uint64_t*>(d_keys) : side(p) ? kB.p : kA.p;
+  };
+  auto pptr = [&](int p) { return side(p) ? pB.p : pA.p; };
   const uint32_t pad = (uint32_t)Nw;
   DBuf<uint32_t> hist(nhist, s);
   DBuf<uint32_t> start((uint64_t)nb + 1, s);
@@ -1395,7 +1432,6 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
   DBuf<uint16_t> dsb(ds_on ? ((uint64_t)Nw + PTILE + 8) / (ds8 ? 2 : 1) + 8 : 1, s);
   uint8_t* ds8p = ds8 ? reinterpret_cast<uint8_t*>(dsb.p) : nullptr;
   uint16_t* ds16p = ds8 ? nullptr : dsb.p;
-  bool ds_ready = false;                                  // dsb holds the next pass's digits
   const Pack8 pk8{pack8 ? sh8 : 0, segb.p, nseg8, make_digit(1, R)};
   // scratch (zeroed in-kernel by V_hist0 / V_hist, no memset): [n_valid][meta][scan status]
   const size_t off_meta = 64, off_status = 128;
@@ -1423,21 +1459,8 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
   uint64_t r_top = 1;                                   // R^(passes - 1)
   for (uint32_t i = 1; i < passes; ++i) r_top *= R;
   DBuf<uint32_t> lvA(passes >= 3 ? r_top + 1 : 1, s), lvB(passes >= 4 ? r_top + 1 : 1, s);
-  uint64_t *kin = kA.p, *kout = kB.p;
-  uint32_t *pin = pA.p, *pout = pB.p;
   uint32_t div = 1;
   DiagBlock db{nullptr, nullptr, nullptr};
-  // a part of 4+ (key streams): V_hist0 also writes the part's windows compacted per tile into
-  // kB / pB (free until then) with their counts; a scan of the counts and one copy make them a
-  // dense (key, position) stream of ~1/n_parts of the windows, and every radix pass runs over
-  // that alone -- instead of encoding and hashing every window again in a first pass over all
-  // of them.  It costs a copy and one more pass over the part's windows, so it pays from 4
-  // parts on (one-GPU rehearsal, tools/part_step.py, per-rank step of 10 Mbp per part: 2 parts
-  // 0.397 -> 0.467 ms, 4 parts 0.504 -> 0.495, 8 parts 0.749 -> 0.581).  KMHG_PART_COMPACT=0 / 1
-  // forces the first pass over every window / the compaction (tests).
-  const char* pce = test_build_knob("KMHG_PART_COMPACT");
-  const bool partc = !from_keys && n_parts >= 2 && !bid && codes &&
-                     (pce ? pce[0] == '1' : n_parts >= 4);
   DBuf<uint32_t> tcnt(partc ? ntiles : 1, s);
   if (from_keys) {   // pass 0 reads the caller's key stream in place (positions implicit)
     HIPC(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(n_valid), (int)Nw, 1, s));
@@ -1451,37 +1474,29 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
     }
     LAUNCH("k_v2_hist0", s,
            launch_v2_hist0(d_seq, L, k, Nw, g, make_digit(1, R), hist.p, ntiles, status,
-                           n_status, meta, s, db.code, db.nbit, bid ? bB.p : nullptr,
+                           n_status, meta, s, db.code, db.nbit,
+                           bid ? static_cast<uint32_t*>(kptr(-1)) : nullptr,
                            partc ? kB.p : nullptr, partc ? pB.p : nullptr,
                            partc ? tcnt.p : nullptr));
     if (partc) {   // tile counts -> tile offsets, the part's window count -> n_valid
       LAUNCH("k_scan_u32", s, launch_scan_u32(tcnt.p, ntiles, status, n_valid, s));
-    } else {
+    } else {       // pass 0: over the sequence, or over V_hist0's ids
       LAUNCH("k_scan_u32", s, launch_scan_u32(hist.p, nhist, status, n_valid, s));
-      if (bid) {
-        const DigitOut ds0{ds16p, make_digit(R, R), ds8p};
-        LAUNCH("k_v2_scatter_seq", s,
-               launch_v2_scatter_bid0(bB.p, Nw, g, make_digit(1, R), hist.p, ntiles,
-                                      passes == 1 ? nullptr : bA.p, pA.p, pad, s,
-                                      ds_on ? &ds0 : nullptr, bid_pack));
-        ds_ready = ds_on;
-      } else {
-        const DigitOut ds0{ds16p, make_digit(R, R), ds8p};
-        LAUNCH("k_v2_scatter_seq", s,
-               launch_v2_scatter_seq(d_seq, L, k, Nw, g, make_digit(1, R), hist.p, ntiles, kA.p,
-                                     pA.p, pad, s, packed(0), pack8 ? &pk8 : nullptr,
-                                     ds_on ? &ds0 : nullptr));
-        ds_ready = ds_on;
-        // the segment table, before pass 1's histogram overwrites pass 0's
-        if (pack8)
-          LAUNCH("k_seg_bounds", s,
-                 launch_seg_bounds(hist.p, ntiles, R, nseg8, (uint32_t)(seg8 / PTILE), n_valid,
-                                   segb.p, s));
-      }
+      const DigitOut ds0{ds16p, make_digit(R, R), ds8p};
+      LAUNCH("k_v2_scatter_seq", s,
+             launch_v2_scatter(bid ? ScatterIn::first_pass(kptr(-1), Nw)
+                                   : ScatterIn::sequence(d_seq, L, k, Nw),
+                               F(-1), F(0), kptr(0), pptr(0), pad, n_valid, g, make_digit(1, R),
+                               hist.p, ntiles, s, nullptr, pack8 ? &pk8 : nullptr,
+                               ds_out(0) ? &ds0 : nullptr));
+      // the segment table, before pass 1's histogram overwrites pass 0's
+      if (pack8)
+        LAUNCH("k_seg_bounds", s,
+               launch_seg_bounds(hist.p, ntiles, R, nseg8, (uint32_t)(seg8 / PTILE), n_valid,
+                                 segb.p, s));
       div = R;
     }
   }
-  uint32_t *bin = bA.p, *bout = bB.p;
   // the later passes' histogram layout: [digit][tile] over the tiles of their input.  A part
   // build keeps ~1/n_parts of the windows after pass 0, so it reads that count back and sizes
   // the later passes to it (a separate histogram, so pass 0's column 0 stays readable) instead
@@ -1506,8 +1521,8 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
                             hipMemcpyDeviceToDevice, s));
   }
   if (partc)   // the part's windows, dense in window order: every radix pass reads these
-    LAUNCH("k_part_dense", s, launch_part_dense(kB.p, pB.p, tcnt.p, ntiles, n_valid, kA.p, pA.p,
-                                                s, packed(-1)));
+    LAUNCH("k_part_dense", s, launch_part_dense(kB.p, pB.p, tcnt.p, ntiles, n_valid, kptr(-1),
+                                                pptr(-1), F(-1), s));
   // where pass 1 saves column 0: pass 0's histogram is hp's unless pass 0 was the one over
   // every window (its own layout, copied above)
   uint32_t* save1 = hp == hist.p || partc ? lo_save.p : nullptr;
@@ -1516,69 +1531,39 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
   // (A/B) launches every level on its own
   const char* fbe = test_build_knob("KMHG_FUSE_BOUNDS");
   const bool fuse_on = !(fbe && fbe[0] == '0');
-  auto level_of = [&](uint32_t p, const void* kprev, bool is_bid, uint32_t spread) {
+  auto level_of = [&](uint32_t p, uint32_t spread) {
     uint64_t dv = 1;                                    // R^p lower-digit values
     for (uint32_t i = 0; i < p; ++i) dv *= R;
     const bool last = p + 1 == passes;
     const uint32_t* lin = p == 1 ? lo_save.p : ((p - 1) % 2 ? lvA.p : lvB.p);
     uint32_t* lout = last ? start.p : (p % 2 ? lvA.p : lvB.p);
-    const bool p8 = pack8 && p == 1;                    // the input is the packed 8-B stream
-    BoundsFuse f{reinterpret_cast<const uint64_t*>(kprev), lin, lout,
-                 make_digit((uint32_t)dv, R), (uint32_t)dv, spread,
-                 is_bid ? (bid_pack ? 4 : 1) : p8 ? 3 : packed((int)p - 1) ? 2 : 0,
-                 last ? g.nb : (uint32_t)(dv * R)};
-    f.sh = p8 ? sh8 : 0;
-    return f;
+    return BoundsFuse{lin, lout, make_digit((uint32_t)dv, R), (uint32_t)dv, spread,
+                      last ? g.nb : (uint32_t)(dv * R)};
   };
   auto fused = [&](uint32_t p) { return p >= 1 && fuse_on && !(co_auto && p + 1 == passes); };
-  auto launch_level = [&](const BoundsFuse& f) {
-    const uint64_t* kp = f.bid ? nullptr : f.kprev;
-    const uint32_t* bp = f.bid ? reinterpret_cast<const uint32_t*>(f.kprev) : nullptr;
-    LAUNCH("k_v2_bounds", s, launch_v2_bounds_lo(kp, n_valid, g, f.Dlast, f.div, hp, C,
-                                                 f.lo_start, f.spread, f.start, f.nlim, s, bp,
-                                                 f.bid == 2, f.bid == 3 ? f.sh : 0, f.bid == 4));
+  auto launch_level = [&](uint32_t p, const BoundsFuse& f) {   // over pass p's input
+    LAUNCH("k_v2_bounds", s,
+           launch_v2_bounds_lo(F((int)p - 1), kptr((int)p - 1), n_valid, g, f.Dlast, f.div, hp, C,
+                               f.lo_start, f.spread, f.start, f.nlim, s, pk8.sh));
   };
-  for (uint32_t p = 1; bid && p < passes; ++p) {
-    const Digit Dp = make_digit(div, R);
-    const bool last = p + 1 == passes;
-    if (ds_ready)
-      LAUNCH("k_v2_hist", s,
-             launch_v2_hist_digits(dsb.p, ds8, n_valid, g, Dp, hp, C, status, nst, s,
-                                   p == 1 ? save1 : nullptr));
-    else
-      LAUNCH("k_v2_hist", s,
-             launch_v2_hist_bid(bin, n_valid, g, Dp, hp, C, status, nst, s,
-                                p == 1 ? save1 : nullptr, bid_pack));
-    LAUNCH("k_scan_u32", s, launch_scan_u32(hp, nh, status, n_valid, s));
-    const BoundsFuse lv = level_of(p, bin, true, 1u);
-    const DigitOut dsn{ds16p, make_digit(div * R, R), ds8p};
-    LAUNCH("k_v2_scatter", s,
-           launch_v2_scatter_bid(bin, pin, n_valid, g, Dp, hp, C, last ? nullptr : bout,
-                                 pout, pad, s, fused(p) ? &lv : nullptr,
-                                 ds_on && !last ? &dsn : nullptr, bid_pack));
-    ds_ready = ds_on && !last;
-    if (!fused(p) && !last) launch_level(lv);
-    std::swap(bin, bout);
-    std::swap(pin, pout);
-    div *= R;
-  }
-  for (uint32_t p = from_keys || partc ? 0 : 1; !bid && p < passes; ++p) {
+  // the radix passes left: histogram (of the digits the pass before left, else of its input),
+  // scan, scatter with the fused level, the level on its own where it is not fused
+  for (uint32_t p = from_keys || partc ? 0 : 1; p < passes; ++p) {
     const Digit Dp = make_digit(div, R);
     const bool keys0 = from_keys && p == 0;
     const bool last = p + 1 == passes;
-    const uint64_t* src = keys0 ? d_keys : kin;
     const bool hll = co_auto && p == 0;
-    if (ds_ready)
+    const int pi = (int)p - 1;                          // the pass's input stream
+    if (keys0)
       LAUNCH("k_v2_hist", s,
-             launch_v2_hist_digits(dsb.p, ds8, n_valid, g, Dp, hp, C, status, nst, s,
-                                   p == 1 ? save1 : nullptr));
+             launch_v2_hist_keys0(d_keys, n_valid, g, Dp, hp, C, status, nst, s,
+                                  hll ? hll_rows.p : nullptr, hll ? hll_regs.p : nullptr,
+                                  skip_empty));
     else
       LAUNCH("k_v2_hist", s,
-             launch_v2_hist(src, n_valid, g, Dp, hp, C, status, nst, s,
-                            hll ? hll_rows.p : nullptr, hll ? hll_regs.p : nullptr,
-                            p == 1 ? save1 : nullptr, keys0 && skip_empty,
-                            /*padded=*/!keys0, !keys0 && packed((int)p - 1),
-                            pack8 && p == 1 ? sh8 : 0));
+             launch_v2_hist(!ds_out(pi) ? F(pi) : ds8 ? StreamFmt::Digits8 : StreamFmt::Digits16,
+                            ds_out(pi) ? dsb.p : kptr(pi), n_valid, g, Dp, hp, C, status, nst, s,
+                            p == 1 ? save1 : nullptr, pk8.sh));
     LAUNCH("k_scan_u32", s, launch_scan_u32(hp, nh, status, n_valid, s));
     if (hll) {   // after the scan: the estimate travels with the valid key count
       LAUNCH("k_v2_hll", s, launch_v2_hll(hll_rows.p, ntiles, hll_regs.p,
@@ -1586,31 +1571,18 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
                                           &hrec.meta->n_positions, s));
       HIPC(hipEventRecord(hrec.ev, s));
     }
-    if (keys0) {
-      LAUNCH("k_v2_scatter", s,
-             launch_v2_scatter_keys0(d_keys, (uint64_t)Nw, n_valid, g, Dp, hist.p, ntiles, kout,
-                                     pout, pad, no_pos, skip_empty, s));
-    } else {
-      const BoundsFuse lv = level_of(p, kin, false, 1u);
-      if (no_pos)
-        LAUNCH("k_v2_scatter", s,
-               launch_v2_scatter_nopos(kin, n_valid, g, Dp, hp, C, kout, pad, s,
-                                       fused(p) ? &lv : nullptr));
-      else {
-        const DigitOut dsn{ds16p, make_digit(div * R, R), ds8p};
-        LAUNCH("k_v2_scatter", s,
-               launch_v2_scatter(kin, pin, n_valid, g, Dp, hp, C, kout, pout, pad, s,
-                                 fused(p) ? &lv : nullptr, packed((int)p), packed((int)p - 1),
-                                 pack8 && p == 1 ? &pk8 : nullptr,
-                                 ds_on && !last ? &dsn : nullptr));
-      }
-      ds_ready = ds_on && !last;
-      if (p >= 1 && !fused(p) && !last) launch_level(lv);
-    }
-    std::swap(kin, kout);
-    std::swap(pin, pout);
+    const BoundsFuse lv = level_of(p, 1u);              // (pass 0 has none: never fused)
+    const DigitOut dsn{ds16p, make_digit(div * R, R), ds8p};
+    LAUNCH("k_v2_scatter", s,
+           launch_v2_scatter(keys0 ? ScatterIn::first_pass(d_keys, Nw, skip_empty)
+                                   : ScatterIn::stream(kptr(pi), pptr(pi)),
+                             F(pi), F((int)p), kptr((int)p), pptr((int)p), pad, n_valid, g, Dp, hp,
+                             C, s, fused(p) ? &lv : nullptr, pack8 ? &pk8 : nullptr,
+                             ds_out((int)p) ? &dsn : nullptr));
+    if (p >= 1 && !fused(p) && !last) launch_level(p, lv);
     div *= R;
   }
+  const int last_p = (int)passes - 1;   // its stream is the bucket kernel's
   Geom gb = g;                     // the bucket stage's geometry
   if (co_auto) {
     // the estimate landed while the later radix passes were still queued on the device
@@ -1626,13 +1598,11 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
   if (passes == 1) {
     // one pass (pass 0 reads chars or the caller's keys): the starts are the scanned column 0
     LAUNCH("k_v2_bounds", s,
-           launch_v2_bounds_lo(nullptr, n_valid, g, make_digit(1, R), 1u, partc ? hp : hist.p,
-                               partc ? C : ntiles, nullptr, g.nb / gb.nb, start.p, g.nb, s,
-                               nullptr));
+           launch_v2_bounds_lo(StreamFmt::Keys, nullptr, n_valid, g, make_digit(1, R), 1u,
+                               partc ? hp : hist.p, partc ? C : ntiles, nullptr, g.nb / gb.nb,
+                               start.p, g.nb, s));
   } else if (!fused(passes - 1)) {
-    // the last pass's input: kout / bout after the final swap
-    launch_level(level_of(passes - 1, bid ? static_cast<const void*>(bout) : kout, bid,
-                          g.nb / gb.nb));
+    launch_level(passes - 1, level_of(passes - 1, g.nb / gb.nb));
   }
 #ifdef KMHG_STAMPS
   static uint64_t* stamps = nullptr;
@@ -1644,8 +1614,8 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
   // checks -> v1 rebuild
   if (const char* td = test_build_knob("KMHG_TEST_DISORDER"))
     if (!no_pos && td[0] >= '1' && td[0] <= '3')
-      launch_v2_test_disorder(aos ? reinterpret_cast<uint32_t*>(kin) + 2 : pin, start.p, n_valid,
-                              td[0] - '0', s, aos ? 3u : 1u);
+      launch_v2_test_disorder(F(last_p), kptr(last_p), pptr(last_p), start.p, n_valid,
+                              td[0] - '0', s);
   // Build-time tags (round 6): a position build beyond the cache (key
   // streams, Nw > BID_MAX_WINDOWS) writes the diagonal query path's slot tags and repeated-key
   // bits itself, so the first seq.kmer.pos of a new index does not pay V_diag_prep (2.6 ms at
@@ -1678,9 +1648,9 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
     }
   }
   LAUNCH("k_v2_bucket_wg", s,
-         launch_v2_bucket_wg(kin, pin, start.p, gb, idx->table.p, idx->positions.p, idx->bstats.p,
-                             meta, no_pos, s, n_valid, (uint32_t)Nw, bid ? db.code : nullptr, k,
-                             aos, tg, rep, bucket_place_on(), bucket_place_counters()));
+         launch_v2_bucket_wg(F(last_p), kptr(last_p), pptr(last_p), start.p, gb, idx->table.p,
+                             idx->positions.p, idx->bstats.p, meta, s, n_valid, (uint32_t)Nw,
+                             db.code, k, tg, rep, bucket_place_on(), bucket_place_counters()));
   idx->tags_built = tg != nullptr;
   LAUNCH("k_v2_stats", s, launch_v2_stats(idx->bstats.p, gb.nb, n_valid, meta, idx->rec.meta, s));
   idx->bstats_nb = gb.nb;

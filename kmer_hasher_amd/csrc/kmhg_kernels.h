@@ -187,6 +187,42 @@ inline Digit make_digit(uint32_t div, uint32_t R) {
   while ((1u << d.nbits) < R) ++d.nbits;
   return d;
 }
+// What one element of a radix stream looks like.  The engine's plan, the launch wrappers and the
+// kernels' template parameters all name a stream's layout with this one type (DESIGN.md "Radix
+// stream formats" keeps the earlier per-kernel mode numbers findable).
+enum class StreamFmt : int {
+  Keys,      // u64 key only; the position is implicit (e + 1) or unused: a caller's key stream,
+             // the windows of the sequence, the streams of a count-only build
+  KeyPos,    // u64 key array + u32 pos array
+  Packed12,  // one 12-B element {key lo, key hi, pos}
+  Packed8,   // one 8-B element, key << sh | window-in-segment (Pack8 below)
+  Bids,      // u32 bucket id only (~0 = not indexed), position implicit: V_hist0's ids
+  BidPos,    // u32 bucket-id array + u32 pos array
+  DigitPos,  // one u32 digit-pos word, (the reading pass's digit << BID_POS_BITS) | pos
+  Pos,       // u32 pos only: what the last bucket-id pass writes
+  Digits8,   // the next pass's digit of each element, u8 / u16 (DigitOut below): read by that
+  Digits16,  // pass's histogram only
+};
+constexpr int BID_POS_BITS = 24;
+// the stream belongs to a bucket-id build: u32 words, digits without hashing
+constexpr bool fmt_bid(StreamFmt f) {
+  return f == StreamFmt::Bids || f == StreamFmt::BidPos || f == StreamFmt::DigitPos ||
+         f == StreamFmt::Pos;
+}
+// the positions travel in an array of their own (pin / pout)
+constexpr bool fmt_pos_array(StreamFmt f) {
+  return f == StreamFmt::KeyPos || f == StreamFmt::BidPos || f == StreamFmt::Pos;
+}
+// bytes per element of the stream's first array (kin / kout; 0: there is none)
+constexpr uint32_t fmt_key_bytes(StreamFmt f) {
+  return f == StreamFmt::Pos ? 0 : f == StreamFmt::Digits8 ? 1 : f == StreamFmt::Digits16 ? 2
+         : fmt_bid(f) ? 4 : f == StreamFmt::Packed12 ? 12 : 8;
+}
+// where an element's position lies, in u32 words of the array that holds it: offset and stride
+// (Packed12 keeps it inside the element; only formats that carry a position)
+constexpr uint32_t fmt_pos_word(StreamFmt f) { return f == StreamFmt::Packed12 ? 2 : 0; }
+constexpr uint32_t fmt_pos_stride(StreamFmt f) { return f == StreamFmt::Packed12 ? 3 : 1; }
+
 // Radix passes run over tiles of PTILE windows; histograms are [digit][tile] (ntiles columns),
 // and the persistent scatter grids give every XCD one contiguous tile range (xcd_remap).
 // V_hist0 also zeroes the look-back words of the scan that follows (n_status u64) and `meta`
@@ -201,10 +237,10 @@ void launch_v2_hist0(const uint8_t* seq, int64_t L, int k, int64_t Nw, Geom g, D
 // ckeys (a part build, key streams): instead of the histogram, the part's windows compacted
 // per tile, (key, position) at [t * PTILE, t * PTILE + tcnt[t]) in window order (ckeys / cpos
 // hold Nw + PTILE entries); after a scan of tcnt (offsets, total in n_total) launch_part_dense
-// packs them into dk / dp
+// packs them into dk / dp (out = KeyPos) or into packed elements in dk (out = Packed12)
 void launch_part_dense(const uint64_t* ck, const uint32_t* cp, const uint32_t* off,
-                       uint32_t ntiles, const uint32_t* n_total, uint64_t* dk, uint32_t* dp,
-                       hipStream_t s, bool aos = false);
+                       uint32_t ntiles, const uint32_t* n_total, void* dk, uint32_t* dp,
+                       StreamFmt out, hipStream_t s);
 // The scatter passes' outputs hold n_max + PTILE elements: lanes past a tile's end store into the
 // pad at [pad, pad + BLOCK) so every lane issues the same stores (see k_v2_scatter).
 // exclusive scan of a u32 array; status = tiles_for(n) + 1 u64, zeroed by the histogram kernel
@@ -217,21 +253,28 @@ void launch_scan_u32(uint32_t* a, uint64_t n, uint64_t* status, uint32_t* total,
 // of partial rows) and writes the distinct-key estimate to *host_est (pinned host memory)
 constexpr uint32_t HLL_REGS = 256;
 constexpr uint32_t HLL_PART_WORDS = 256 * 64 + 1;
-void launch_v2_hist(const uint64_t* keys, const uint32_t* n_ptr, Geom g, Digit D, uint32_t* hist,
-                    uint32_t ntiles, uint64_t* scan_status, uint32_t n_status, hipStream_t s,
-                    uint32_t* hll_rows = nullptr, uint32_t* hll_regs = nullptr,
-                    uint32_t* save_col0 = nullptr, bool skip_empty = false,
-                    bool padded = false, bool aos = false, int sh8 = 0);
+// the first pass over a caller's key stream (exactly *n_ptr keys, no pad; one workgroup per
+// tile); skip_empty: EMPTY_KEY entries are not keys
+void launch_v2_hist_keys0(const uint64_t* keys, const uint32_t* n_ptr, Geom g, Digit D,
+                          uint32_t* hist, uint32_t ntiles, uint64_t* scan_status,
+                          uint32_t n_status, hipStream_t s, uint32_t* hll_rows = nullptr,
+                          uint32_t* hll_regs = nullptr, bool skip_empty = false);
+// a later pass's histogram over its input stream `in` of format `fmt` (the first array of a
+// padded stream the passes wrote -- Keys / KeyPos, Packed12, Packed8, BidPos, DigitPos -- or the
+// digit stream the previous pass left: Digits8 / Digits16); sh: Pack8::sh of a Packed8 stream.
+// save_col0: the previous pass's scanned column 0 (its digit starts) is copied there first
+void launch_v2_hist(StreamFmt fmt, const void* in, const uint32_t* n_ptr, Geom g, Digit D,
+                    uint32_t* hist, uint32_t ntiles, uint64_t* scan_status, uint32_t n_status,
+                    hipStream_t s, uint32_t* save_col0 = nullptr, int sh = 0);
 // one level of the bucket starts from the histograms (the unfused form of BoundsFuse): one
-// workgroup per lo value (div of them); kprev = pass p's input keys, lo_start = S_(p-1) (pass 0's
-// column 0 saved by launch_v2_hist's save_col0 for p = 1; nullptr for one pass); start[c / spread]
-// for c < nlim that are multiples of spread, start[nlim / spread] = n
-// bprev (bucket-id streams): the pass's input bucket ids instead of kprev
-void launch_v2_bounds_lo(const uint64_t* kprev, const uint32_t* n_ptr, Geom g, Digit Dlast,
-                         uint32_t div, const uint32_t* hist, uint32_t C, const uint32_t* lo_start,
-                         uint32_t spread, uint32_t* start, uint32_t nlim, hipStream_t s,
-                         const uint32_t* bprev = nullptr, bool aos = false, int sh8 = 0,
-                         bool dpw = false);
+// workgroup per lo value (div of them); in = pass p's input stream of format fmt (sh as above),
+// lo_start = S_(p-1) (pass 0's column 0 saved by launch_v2_hist's save_col0 for p = 1; nullptr
+// for one pass, which reads no element); start[c / spread] for c < nlim that are multiples of
+// spread, start[nlim / spread] = n
+void launch_v2_bounds_lo(StreamFmt fmt, const void* in, const uint32_t* n_ptr, Geom g,
+                         Digit Dlast, uint32_t div, const uint32_t* hist, uint32_t C,
+                         const uint32_t* lo_start, uint32_t spread, uint32_t* start,
+                         uint32_t nlim, hipStream_t s, int sh = 0);
 // segb (Pack8) from pass 0's scanned histogram: R x (nseg + 1) entries, tps = tiles per segment
 void launch_seg_bounds(const uint32_t* hist, uint32_t ntiles, uint32_t R, uint32_t nseg,
                        uint32_t tps, const uint32_t* n_valid, uint32_t* segb, hipStream_t s);
@@ -243,19 +286,25 @@ void launch_v2_hll(const uint32_t* hll_rows, uint32_t n_rows, uint32_t* hll_regs
 // are complete before the pass starts, and its output (S_p: the bucket starts for the last pass)
 // is read only by the next level or the bucket kernel, so the pass's workgroups each compute
 // the starts of a few lower-digit values before their tiles (no launch, no key pass).
-// start == nullptr: not fused.
+// start == nullptr: not fused.  The level reads the pass's own input (its format, pointer and
+// Pack8::sh), so it carries none of them.
+struct BoundsFuse {
+  const uint32_t* lo_start;    // S_(p-1): starts of the input's combined lower digits
+  uint32_t* start;             // S_p
+  Digit Dlast;                 // the pass's own digit
+  uint32_t div, spread;        // div = R^p lower-digit values
+  uint32_t nlim;               // entries of S_p: nb for the last pass, R^(p+1) before
+};
 // A radix pass's digit stream (DS): out[i] = the next pass's digit of output element i (u16,
 // or u8 in out8 for a radix <= 256; n + PTILE entries), which the next pass's histogram reads
-// (launch_v2_hist_digits) instead of the keys: 1-2 B per element instead of 8 or 12.
+// (launch_v2_hist with Digits16 / Digits8) instead of the keys: 1-2 B per element instead of 8
+// or 12.
 struct DigitOut {
   uint16_t* out;
   Digit Dn;
   uint8_t* out8 = nullptr;
 };
 constexpr DigitOut kNoDigits{nullptr, Digit{}, nullptr};
-void launch_v2_hist_digits(const void* digits, bool u8, const uint32_t* n_ptr, Geom g, Digit D,
-                           uint32_t* hist, uint32_t ntiles, uint64_t* scan_status,
-                           uint32_t n_status, hipStream_t s, uint32_t* save_col0 = nullptr);
 // Packed 8-B elements of a small-k key stream (the first pass of a two-pass build with 2k <= 52,
 // i.e. k <= 26: the engine needs sh >= 12): the high 2k bits hold the key, the low sh = 64 - 2k bits the window's index inside its segment
 // of 2^sh windows.  The segment comes back from the element's place in the stream: pass 0 writes
@@ -267,73 +316,64 @@ struct Pack8 {
   uint32_t nseg;
   Digit d0;                    // pass 0's digit
 };
-struct BoundsFuse {
-  const uint64_t* kprev;       // the pass's input (keys, or bucket ids with bid = 1)
-  const uint32_t* lo_start;    // S_(p-1): starts of the input's combined lower digits
-  uint32_t* start;             // S_p
-  Digit Dlast;                 // the pass's own digit
-  uint32_t div, spread;        // div = R^p lower-digit values
-  int bid;                     // 0 u64 keys, 1 u32 bucket ids, 2 packed 12-B (key, pos) elements,
-                               // 3 packed 8-B (key << sh | window) elements, 4 digit-pos words
-  uint32_t nlim;               // entries of S_p: nb for the last pass, R^(p+1) before
-  int sh = 0;                  // bid 3: the element's key is e >> sh
+// What a radix pass reads: the sequence (16-B aligned: the engine copies an unaligned input;
+// format Keys, n0 = its windows), a first pass over n0 (>= 1) elements whose positions are
+// implicit (e + 1) -- a caller's key stream (Keys; skip_empty: EMPTY_KEY entries are not keys,
+// padded read k-mer streams of k <= 31) or V_hist0's ids (Bids) -- or a stream an earlier pass
+// wrote (kin, and pin where the format keeps a position array; *n_ptr elements).
+struct ScatterIn {
+  const uint8_t* seq;
+  int64_t L;
+  int k;
+  bool first;                  // not the sequence: positions implicit
+  int64_t n0;
+  bool skip_empty;
+  const void* kin;
+  const uint32_t* pin;
+  static ScatterIn sequence(const uint8_t* seq, int64_t L, int k, int64_t Nw) {
+    return {seq, L, k, false, Nw, false, nullptr, nullptr};
+  }
+  static ScatterIn first_pass(const void* kin, int64_t n0, bool skip_empty = false) {
+    return {nullptr, 0, 0, true, n0, skip_empty, kin, nullptr};
+  }
+  static ScatterIn stream(const void* kin, const uint32_t* pin) {
+    return {nullptr, 0, 0, false, 0, false, kin, pin};
+  }
 };
-// the sequence must be 16-B aligned (the engine copies an unaligned input)
-void launch_v2_scatter_seq(const uint8_t* seq, int64_t L, int k, int64_t Nw, Geom g, Digit D,
-                           const uint32_t* hist, uint32_t ntiles, uint64_t* kout, uint32_t* pout,
-                           uint32_t pad, hipStream_t s, bool aos = false,
-                           const Pack8* pk = nullptr, const DigitOut* ds = nullptr);
-// first pass over a caller's key stream of n_keys keys (>= 1): positions are e + 1; nopos:
-// keys only (count-only builds), pout unused; skip_empty: EMPTY_KEY entries are not keys (padded
-// read k-mer streams, k <= 31)
-void launch_v2_scatter_keys0(const uint64_t* kin, uint64_t n_keys, const uint32_t* n_ptr, Geom g,
-                             Digit D, const uint32_t* hist, uint32_t ntiles, uint64_t* kout,
-                             uint32_t* pout, uint32_t pad, bool nopos, bool skip_empty,
-                             hipStream_t s);
-void launch_v2_scatter_nopos(const uint64_t* kin, const uint32_t* n_ptr, Geom g, Digit D,
-                             const uint32_t* hist, uint32_t ntiles, uint64_t* kout, uint32_t pad,
-                             hipStream_t s, const BoundsFuse* bf = nullptr);
-void launch_v2_scatter(const uint64_t* kin, const uint32_t* pin, const uint32_t* n_ptr, Geom g,
-                       Digit D, const uint32_t* hist, uint32_t ntiles, uint64_t* kout, uint32_t* pout,
-                       uint32_t pad, hipStream_t s, const BoundsFuse* bf = nullptr,
-                       bool aos = false, bool aos_in = true, const Pack8* pk = nullptr,
+// One stable radix pass from `in` of format fin to (kout, pout) of format fout; kout (and pout
+// where fout keeps a position array) hold n + PTILE elements.  The legal (fin, fout) pairs:
+//   the sequence (Keys) -> KeyPos | Packed12 | Packed8
+//   a caller's keys (Keys, first pass) -> Keys | KeyPos;  Keys -> Keys (count-only builds)
+//   KeyPos -> KeyPos | Packed12;  Packed12 -> Packed12;  Packed8 -> Packed12
+//   Bids (first pass) -> BidPos | DigitPos | Pos;  BidPos -> BidPos | Pos;  DigitPos -> Pos
+// Packed12 (position builds on key streams): each window is ONE 12-B element, so a tile's digit
+// run is one contiguous write.
+// Bucket-id streams (position builds that keep the sequence's code words): V_hist0 stores every
+// window's bucket id (Bids), the radix passes carry BidPos and the last pass writes Pos; the
+// bucket kernel cuts the keys from the code words.  Histograms without hashing.
+// DigitPos (two passes, radix <= 256, Nw < 1 << BID_POS_BITS): the stream between the two
+// passes is one u32 per window, (pass-1 digit << 24) | pos -- pass 0 writes it to kout, pass 1,
+// its histogram and its bucket-start level read the digit as w >> 24 and pass 1 writes
+// w & 0xFFFFFF to pout.
+// pk: the Pack8 of a Packed8 input or output; ds: the pass also writes the next pass's digits.
+void launch_v2_scatter(const ScatterIn& in, StreamFmt fin, StreamFmt fout, void* kout,
+                       uint32_t* pout, uint32_t pad, const uint32_t* n_ptr, Geom g, Digit D,
+                       const uint32_t* hist, uint32_t ntiles, hipStream_t s,
+                       const BoundsFuse* bf = nullptr, const Pack8* pk = nullptr,
                        const DigitOut* ds = nullptr);
-// Packed key streams (aos): position builds on key streams carry each window as ONE 12-B
-// element {key lo, key hi, pos} (kout holds n + PTILE of them; pout unused), so a tile's digit
-// run is one contiguous write; aos_in: the input is packed too (else kin / pin arrays).
-// Bucket-id streams (position builds that keep the sequence's code words): V_hist0 stores
-// every window's bucket id (`bids`, Nw u32, ~0 = not indexed), the radix passes carry (bucket
-// id u32, pos u32) and the last pass writes positions only (bout = nullptr); the bucket kernel
-// cuts the keys from the code words.  Histograms without hashing.
-// dpw (two passes, radix <= 256, Nw < 2^24 = 1 << BID_POS_BITS): the stream between the two
-// passes is one u32 per window, the digit-pos word (pass-1 digit << 24) | pos -- pass 0 writes
-// it to bout (pout unused), pass 1 and its histogram and bucket-start level read the digit as
-// w >> 24 (bin; pin unused) and pass 1 writes w & 0xFFFFFF to pout.
-constexpr int BID_POS_BITS = 24;
-void launch_v2_scatter_bid0(const uint32_t* bids, int64_t Nw, Geom g, Digit D,
-                            const uint32_t* hist, uint32_t ntiles, uint32_t* bout, uint32_t* pout,
-                            uint32_t pad, hipStream_t s, const DigitOut* ds = nullptr,
-                            bool dpw = false);
-void launch_v2_scatter_bid(const uint32_t* bin, const uint32_t* pin, const uint32_t* n_ptr,
-                           Geom g, Digit D, const uint32_t* hist, uint32_t ntiles, uint32_t* bout,
-                           uint32_t* pout, uint32_t pad, hipStream_t s,
-                           const BoundsFuse* bf = nullptr, const DigitOut* ds = nullptr,
-                           bool dpw = false);
-void launch_v2_hist_bid(const uint32_t* bids, const uint32_t* n_ptr, Geom g, Digit D,
-                        uint32_t* hist, uint32_t ntiles, uint64_t* scan_status, uint32_t n_status,
-                        hipStream_t s, uint32_t* save_col0 = nullptr, bool dpw = false);
 struct BucketStats {           // per-bucket partials of the build statistics
   uint32_t n_kmers, max_count;
   uint64_t n_pairs;
 };
-// count_only: occurrence counts only (no positions written; slot aux unspecified)
-// code (bucket-id streams): keys unused, each window's key cut from the code words at its pos
-void launch_v2_bucket_wg(const uint64_t* keys, const uint32_t* pos, const uint32_t* start, Geom g,
-                         Slot* T, int32_t* positions, BucketStats* bstats, BuildMeta* meta,
-                         bool count_only, hipStream_t s, const uint32_t* n_ptr, uint32_t nw,
-                         const uint32_t* code = nullptr, int k = 0, bool aos = false,
-                         uint8_t* TG = nullptr, uint32_t* rep = nullptr, bool place = true,
-                         uint32_t* place_ctr = nullptr);
+// fmt = the bucket-sorted stream (keys, pos): KeyPos, Packed12 (pos unused), Keys (count-only:
+// occurrence counts only, no positions written, slot aux unspecified) or Pos (bucket-id builds:
+// keys unused, each window's key cut from the code words `code` at its pos)
+void launch_v2_bucket_wg(StreamFmt fmt, const void* keys, const uint32_t* pos,
+                         const uint32_t* start, Geom g, Slot* T, int32_t* positions,
+                         BucketStats* bstats, BuildMeta* meta, hipStream_t s,
+                         const uint32_t* n_ptr, uint32_t nw, const uint32_t* code = nullptr,
+                         int k = 0, uint8_t* TG = nullptr, uint32_t* rep = nullptr,
+                         bool place = true, uint32_t* place_ctr = nullptr);
 // place: one-batch position buckets try pass A by placement (home-slot counts + a scan) before
 // the CAS pass; place_ctr (test build, else null): three device counters -- buckets placed,
 // fallen back to the CAS pass for a repeated key, fallen back for a second wrap
@@ -344,8 +384,9 @@ void launch_v2_bucket_wg(const uint64_t* keys, const uint32_t* pos, const uint32
 // the radix passes and the bucket kernel then rank with ballots (kmhg_engine.cpp)
 bool ballot_ranks();
 void launch_lane_order_check(unsigned long long* res, hipStream_t s, int blocks = 1024);
-void launch_v2_test_disorder(uint32_t* pos, uint32_t* start, const uint32_t* n_ptr, int mode,
-                             hipStream_t s, uint32_t stride = 1);
+// (the bucket-sorted stream as launch_v2_bucket_wg takes it; a format that carries positions)
+void launch_v2_test_disorder(StreamFmt fmt, void* keys, uint32_t* pos, uint32_t* start,
+                             const uint32_t* n_ptr, int mode, hipStream_t s);
 void launch_v2_stats(const BucketStats* bstats, uint32_t nb, const uint32_t* n_valid,
                      BuildMeta* meta, BuildMeta* host_meta, hipStream_t s);
 

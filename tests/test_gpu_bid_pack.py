@@ -1,8 +1,9 @@
-"""The packed middle stream of two-pass bucket-id builds (kmhg_build_v2.hip k_v2_scatter BM 8 / 9,
-k_v2_histp mode 6, bounds_lo_body code 4): one u32 per window between the two radix passes, the
-digit-pos word (pass-1 digit << 24) | pos, instead of the (bucket id, pos) pair of arrays.  It is
-taken by a bucket-id build of two passes at a radix <= 256 and fewer than 2^24 windows without
-digit streams; every other bucket-id build keeps the two arrays.
+"""The packed middle stream of two-pass bucket-id builds (kmhg_kernels.h StreamFmt::DigitPos: the
+k_v2_scatter passes Bids -> DigitPos and DigitPos -> Pos, k_v2_histp<DigitPos> and the bucket-start
+level over a DigitPos input): one u32 per window between the two radix passes, the digit-pos word
+(pass-1 digit << 24) | pos, instead of the BidPos pair of arrays (bucket id, pos).  It is taken by
+a bucket-id build of two passes at a radix <= 256 and fewer than 2^24 windows without digit
+streams; every other bucket-id build keeps the two arrays.
 
 Every case is built with KMHG_BUILD_BID=1 under KMHG_BID_PACK=1 and =0.  Each build must equal the
 oracle on the build totals, the kmer.pos readout with pair rows and the seq.kmer.pos self-query,
