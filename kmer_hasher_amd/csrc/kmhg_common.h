@@ -15,6 +15,11 @@
 #pragma once
 #include <stdint.h>
 
+#if !defined(__HIPCC__) && !defined(__host__)   // a plain C++ compiler (kmhg_plan.h's users)
+#define __host__
+#define __device__
+#endif
+
 namespace kmhg {
 
 constexpr uint64_t EMPTY_KEY = ~0ull;

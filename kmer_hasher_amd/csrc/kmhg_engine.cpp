@@ -29,6 +29,7 @@
 
 #include "kmhg_common.h"
 #include "kmhg_kernels.h"
+#include "kmhg_plan.h"
 #include "kmhg_parts_read.h"
 #include "kmhg_fastx.h"
 #include "kmhg_khash.h"
@@ -38,12 +39,10 @@
 // KMHG_DEVICES (multi-device query), KMHG_ROW_ORDER and KMHG_D2H_THREADS.  Everything else exists
 // only in the test build (-DKMHG_TEST_BUILD: libkmhgpu_test.so, which the GPU suite loads for the
 // tests that force a path, tests/conftest.py `test_lib`): the path selectors that force each
-// build / query / counts path against the oracle (KMHG_BUILD, KMHG_BUILD_BID, KMHG_MAXR,
-// KMHG_FUSE_BOUNDS, KMHG_TEST_BALLOT, KMHG_QUERY_TAGS, KMHG_QUERY_DIAG, KMHG_DIAG_CODES,
-// KMHG_COUNT_TABLE, KMHG_COUNT_WALK, KMHG_CO_SPREAD, KMHG_CO_GLOBAL, KMHG_PART_COMPACT,
-// KMHG_ROW_ORDER_SORT, KMHG_PACK8, KMHG_NB_ROUND, KMHG_SLICE_POISON, KMHG_TEST_REPLICA,
-// KMHG_DIGIT_STREAM, KMHG_DS_BID, KMHG_DS_U8, KMHG_DS_PACK, KMHG_BUILD_TAGS,
-// KMHG_BUCKET_PLACE, KMHG_BID_PACK), which choose
+// build / query / counts path against the oracle (the partitioned build's: BuildKnobs,
+// kmhg_plan.h, filled by read_build_knobs below; KMHG_BUILD, KMHG_TEST_BALLOT, KMHG_QUERY_TAGS,
+// KMHG_QUERY_DIAG, KMHG_DIAG_CODES, KMHG_COUNT_TABLE, KMHG_COUNT_WALK, KMHG_CO_GLOBAL,
+// KMHG_ROW_ORDER_SORT, KMHG_SLICE_POISON, KMHG_TEST_REPLICA), which choose
 // between equivalent paths and change no result; fault injection (KMHG_TEST_DISORDER); and the
 // A/B-only switches (KMHG_D2H, KMHG_D2H_HUGE, KMHG_HOST_RUNS, KMHG_HOST_PAIRS, KMHG_HOST_POOL,
 // KMHG_COUNT_BID, KMHG_RK_CAP, KMHG_POOL_DEPTH, KMHG_POOL_BESTFIT, KMHG_POOL_TRACE).
@@ -1089,12 +1088,13 @@ kmhg_index* build_device_v1(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
   return idx.release();
 }
 
-// Bucket-id radix streams (position builds that keep their code words) up to this many windows
-// (build_device_v2); KMHG_BUILD_BID=0 / 1 forces key / bucket-id streams.
-constexpr int64_t BID_MAX_WINDOWS = 12 << 20;
-bool bid_streams_for(int64_t Nw) {
-  const char* bide = test_build_knob("KMHG_BUILD_BID");
-  return bide ? bide[0] == '1' : Nw <= BID_MAX_WINDOWS;
+// The partitioned build's switches, once per build: the defaults in the product library, the
+// environment's in the test build.  The only place these names are read.
+BuildKnobs read_build_knobs() {
+  BuildKnobs kn;
+  for (const char* name : BUILD_KNOB_NAMES)
+    if (const char* v = test_build_knob(name)) set_build_knob(kn, name, v);
+  return kn;
 }
 
 // One round of the bucket kernel on the current device: its CUs x the workgroups one CU holds
@@ -1114,43 +1114,17 @@ uint32_t bucket_round_of_current_device() {
   return v;
 }
 
-constexpr double CO_FILL = 0.6;                  // target mean occupancy of a count-only bucket
-
-// Stream entries per group bucket (in units of V2_BW_WG) for a batch of `total` keys with
-// ~`distinct` distinct ones: mean distinct keys per bucket ~CO_FILL x V2_CAPW, at most 4x.
-// KMHG_CO_SPREAD (tests) forces one, rounded down to a divisor of 12 (build_device_v2).
-int co_spread_for(double distinct, uint64_t total) {
-  if (const char* e = test_build_knob("KMHG_CO_SPREAD")) {
-    int f = std::max(1, std::min(12, std::atoi(e)));
-    while (12 % f) --f;
-    return f;
-  }
-  const double ratio = std::max(std::min(distinct / std::max<double>((double)total, 1.0), 1.0), 1e-3);
-  const int f = (int)(CO_FILL * V2_CAPW / (V2_BW_WG * ratio));
-  return std::max(1, std::min(4, f));
-}
-
 // Partitioned build (kmhg_build_v2.hip): LSD radix partition of the windows by hash bucket,
 // then one wave per bucket builds its sub-table in LDS.  Falls back to v1 if a bucket's LDS
 // sub-table overflows (position builds: never observed -- distinct keys per bucket ~ Binomial,
 // mean <= V2_BW; count-only builds retry at spread 1 instead, sh_count_reads_device).
-// Partitioned build over the windows of a sequence (d_seq), or over a stream of n_keys
-// distinct keys (d_keys, d_seq == nullptr; the counts index's table rebuild): key r is stored
-// with count 1 and aux = r + 1.
-// count_only (a key stream whose positions nobody reads: read counting): the group bucket kernel
-// skips its position pass and no positions array is kept.
-// count_only with co_spread = 0: the spread is chosen from the key stream's own HLL estimate
-// (co_spread_for), read back while the radix passes run.
-// skip_empty (count-only key streams of k <= 31): EMPTY_KEY entries are padding, not keys --
-// the first pass drops them, and the valid count comes from its scan.
+// What is built is a BuildRequest (kmhg_plan.h: the windows of a sequence, a part of them, a key
+// stream, a count-only key stream); every decision is plan_build's, and build_device_v2 below
+// allocates from the plan and launches.
 // Pass A by placement in the bucket kernel (kmhg_build_v2.hip): on unless KMHG_BUCKET_PLACE=0
 // (test build) forces the CAS pass everywhere.  The test build also counts, per device buffer
 // made once and kept, the buckets placed / fallen back for a repeated key / fallen back for a
 // second wrap (kmhg_bucket_place_counters); the product library passes no counters.
-bool bucket_place_on() {
-  const char* e = test_build_knob("KMHG_BUCKET_PLACE");
-  return !(e && e[0] == '0');
-}
 #ifdef KMHG_TEST_BUILD
 static std::mutex g_place_mu;
 static uint32_t* g_place_ctr = nullptr;              // 3 x u32 on g_place_dev
@@ -1180,24 +1154,40 @@ void count_bid_pack(bool packed) { g_bid_pack_ctr[packed ? 0 : 1].fetch_add(1, s
 void count_bid_pack(bool) {}
 #endif
 
-kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t s,
-                            const uint64_t* d_keys = nullptr, int64_t n_keys = 0,
-                            bool count_only = false, int co_spread = 1, bool skip_empty = false,
-                            bool codes = false, uint32_t part = 0, uint32_t n_parts = 0) {
+// the device buffers a BuildRequest speaks of: the sequence (16-B alignment not required), or
+// the key stream
+struct StreamPtrs {
+  const uint8_t* d_seq = nullptr;
+  const uint64_t* d_keys = nullptr;
+};
+
+kmhg_index* build_device_v2(const BuildRequest& rq, const StreamPtrs& in, hipStream_t s) {
   ReleaseGroup rg(s);             // the scratch buffers below: one release event
-  const uint8_t* d_src = d_seq;   // the caller's buffer (the v1 fallback re-reads it)
+  const BuildKnobs kn = read_build_knobs();
+  const BuildPlan P = plan_build(rq, kn, bucket_round_of_current_device());
+  if (P.err != KMHG_OK) fail(P.err, P.msg);
   auto idx = std::make_unique<kmhg_index>();
   idx->stream = s;
   HIPC(hipGetDevice(&idx->device));
   idx->build_kind = ballot_ranks() ? KMHG_BUILD_PARTITIONED_BALLOT : KMHG_BUILD_PARTITIONED;
-  idx->k = k;
-  idx->L = L;
-  const bool from_keys = d_seq == nullptr;
-  const int64_t Nw = from_keys ? n_keys : L - k + 1;
-  if (from_keys && Nw < 1) fail(KMHG_EINVAL, "empty key stream (internal error)");
-  if (skip_empty && !(from_keys && count_only && k < 32))
-    fail(KMHG_EINVAL, "padded key stream outside a count-only build (internal error)");
+  idx->k = rq.k;
+  idx->L = rq.L;
+  idx->is_part = P.is_part;
+  idx->geom = P.geom;
+  if (P.empty_part) {             // nothing to build
+    idx->table.reset(1);
+    idx->positions.reset(1);
+    return idx.release();
+  }
+  const int k = rq.k;
+  const int64_t L = rq.L, Nw = P.Nw;
+  const bool from_keys = P.from_keys, co_auto = P.co_auto, bid = P.bid, partc = P.partc;
+  const uint32_t passes = P.passes, R = P.R, ntiles = P.ntiles, nb = P.geom.nb;
+  const uint64_t nhist = P.nhist;
+  const Geom g = P.geom;
+  const uint64_t* d_keys = in.d_keys;
   // the partition kernels read the sequence as aligned 16-B words: copy an unaligned input
+  const uint8_t* d_seq = in.d_seq;
   DBuf<uint8_t> aligned_copy;
   if (!from_keys && (reinterpret_cast<uintptr_t>(d_seq) & 15) != 0) {
     aligned_copy.reset((size_t)L);
@@ -1205,237 +1195,28 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
     HIPC(hipMemcpyAsync(aligned_copy.p, d_seq, (size_t)L, hipMemcpyDeviceToDevice, s));
     d_seq = aligned_copy.p;
   }
-  const uint32_t ntiles = (uint32_t)((Nw + PTILE - 1) / PTILE);   // partition tiles
-  // radix plan: fewest passes whose radix fits LDS.  Tiles of PTILE windows keep ~PTILE / R
-  // elements per digit run: beyond ~300 digits the runs get too short for coalesced writes and
-  // an extra pass is cheaper.
-  uint32_t maxr = V2_MAXR_IL;
-  const char* e = test_build_knob("KMHG_MAXR");   // testing knob: force more radix passes
-  if (e && e[0])
-    maxr = std::max<uint32_t>(2u, std::min<uint32_t>(maxr, (uint32_t)std::atoi(e)));
-  auto plan = [&](uint32_t nbk, uint32_t& R) {
-    for (uint32_t passes = 1; passes <= 4; ++passes) {
-      R = (uint32_t)std::ceil(std::pow((double)nbk, 1.0 / passes) - 1e-9);
-      while (std::pow((double)R, (double)passes) < (double)nbk) ++R;
-      if (R <= maxr) return passes;
-    }
-    return 5u;
-  };
-  // group buckets: 1024 windows, one workgroup each.  (Wave buckets of 256 windows were
-  // removed in round 4: group buckets halve the radix -- config 2 26.1 vs 24.8 Gbp/s -- and save
-  // a pass from ~26 M windows -- config 3 26.3 vs 24.5.)
-  // count-only builds: co_spread x more stream entries per group bucket -- a read batch's
-  // distinct keys are a fraction of its key stream, so fewer buckets still fit their LDS
-  // sub-tables (co_spread_for); one overflowing bucket fails the whole build (meta->overflow)
-  // and sh_count_reads_device rebuilds at spread 1.  With co_spread = 0 the radix passes sort
-  // by the bucket b1 among nb1 = 12 * ceil(Nw / (12 * V2_BW_WG)): the bucket among nb1 / s is
-  // b1 / s exactly (floor(floor(h nb1 / 2^64) / s) = floor(h (nb1 / s) / 2^64)), so one sorted
-  // stream serves every spread s in {1, 2, 3, 4}, and s is picked only before the bucket stage.
-  const bool co_auto = count_only && co_spread == 0;
-  int64_t bw_g = V2_BW_WG;
-  if (count_only && !co_auto) bw_g *= std::max(1, std::min(8, co_spread));
-  uint32_t nb_g =
-      co_auto ? (uint32_t)(12 * std::max<int64_t>(1, (Nw + 12 * V2_BW_WG - 1) / (12 * V2_BW_WG)))
-              : (uint32_t)std::max<int64_t>(1, (Nw + bw_g - 1) / bw_g);
-  // Whole rounds of the bucket kernel: its workgroups take about equally long, so 4.77 rounds of
-  // the device's resident workgroups (config 2: 9,766 buckets on 256 CUs x 8) cost 5; rounding
-  // the bucket count up to whole rounds gives each bucket fewer windows instead (position builds
-  // of 2-16 rounds; the parts of an owner-computes build split the same rounded table, so they
-  // still assemble into the single-device table).  Only when the extra buckets are few (at most
-  // an eighth more: a build just past a round boundary would otherwise nearly double its table
-  // and halve its load).  The round is the building device's own (CUs x workgroups per CU).
-  // KMHG_NB_ROUND=0 (test build) keeps ceil(windows / 1,024).
-  if (!from_keys && !count_only) {
-    const char* nre = test_build_knob("KMHG_NB_ROUND");
-    if (!(nre && nre[0] == '0')) {
-      const uint32_t wave_wg = bucket_round_of_current_device();
-      if (wave_wg && nb_g > wave_wg && nb_g <= 16 * wave_wg) {
-        const uint32_t rounded = (nb_g + wave_wg - 1) / wave_wg * wave_wg;
-        if (rounded - nb_g <= nb_g / 8) nb_g = rounded;
-      }
-    }
-  }
-  uint32_t R = 0;
-  uint32_t nb = nb_g;
-  uint32_t passes = plan(nb_g, R);
-  // owner-computes part (the reference's reader-pool partition,
-  // src/kmer_reader.c:28-39): the whole build's geometry, of which this part keeps the buckets
-  // [b0, b1) -- every window is encoded and hashed, only the part's keys are partitioned
-  uint32_t b0 = 0, nbh = 0;
-  if (n_parts >= 1) {           // n_parts = 0: a whole build
-    if (from_keys || count_only) fail(KMHG_EINVAL, "part builds index sequences only");
-    b0 = (uint32_t)((uint64_t)nb * part / n_parts);
-    const uint32_t b1 = (uint32_t)((uint64_t)nb * (part + 1) / n_parts);
-    nbh = nb;
-    idx->is_part = true;
-    if (b1 <= b0) {              // more parts than buckets: an empty part (nothing to build)
-      idx->geom = Geom{0u, V2_CAPW, b0, nbh};
-      idx->table.reset(1);
-      idx->positions.reset(1);
-      return idx.release();
-    }
-    nb = b1 - b0;
-    passes = plan(nb, R);
-  }
-  if (passes > 4) fail(KMHG_EOVERFLOW, "sequence too long for the partitioned build");
-  idx->geom = Geom{nb, V2_CAPW, b0, nbh};
-  const Geom g = idx->geom;
-  const uint64_t nhist = (uint64_t)R * ntiles;
-  const uint32_t scan_tiles = tiles_for(nhist);
-  // bucket-id streams (position builds that keep the code words): the radix passes carry
-  // (bucket id, pos) -- 8 B per window instead of 12 -- the last pass positions only, and the
-  // bucket kernel cuts each key from the code words.  The cut is a random 12-B read per window:
-  // cheap while the code words (Nw / 4 bytes) stay in an XCD's 4 MB L2, a 128-B Infinity-Cache
-  // line per window beyond.  Measured (A/B in one run): config 2 (10 M windows, 2.5 MB of code)
-  // 30.1 -> 31.1 Gbp/s; config 3 (100 M, 25 MB) 28.5 -> 24.0 (bucket kernel 0.84 -> 2.0 ms).
-  // So on up to BID_MAX_WINDOWS; KMHG_BUILD_BID=0 / 1 forces key / bucket-id streams.
-  const bool bid = codes && !from_keys && !count_only && bid_streams_for(Nw);
-  // position builds on key streams carry packed 12-B (key, pos) elements: a tile's digit run is
-  // one contiguous write instead of a key piece and a position piece in two arrays
-  // (tools/scatter_pattern.hip layout, profiles/r5a_scatter_layout.txt: radix 313 1.09 -> 0.87
-  // ms per 100 M elements, radix 79 0.72 -> 0.61).  Built with -DKMHG_NO_AOS: SoA streams (A/B).
-#ifdef KMHG_NO_AOS
-  const bool aos = false;
-#else
-  const bool aos = !from_keys && !count_only && !bid;
-#endif
-  // Which streams are packed (stream p = pass p's output; -1 = a part build's dense stream):
-  // the last one, which only the bucket kernel reads, always; an earlier one only at a radix
-  // where the scatter's saving beats the 4 more bytes per element its histogram pass then reads.
-  // Measured: config 3 (2 passes, radix 313) every stream packed 3.49 -> 3.21 ms per build
-  // (scatters 0.94 + 1.03 -> 0.75 + 0.91 ms, histogram 0.27 -> 0.36); the 500 Mbp build (3
-  // passes, radix 79) 18.2 -> 18.6 ms (histograms 1.9 -> 2.8 ms, scatters 11.2 -> 10.3), A/B
-  // in one run (profiles/r5b_ab_aos_config3.log, r5c_ab_aos_config5.log).
-  constexpr uint32_t AOS_MIN_RADIX = 160;
-  // Pack8 (two-pass builds of small k: 2k <= 52): the first pass writes 8-B elements, key << sh
-  // | the window's index inside its segment of 2^sh windows (sh = 64 - 2k), and the second pass
-  // restores the position from the element's place in the stream (k_seg_bounds' table).  The
-  // first stream's writes and the histogram pass's reads shrink from 12 to 8 B per window.
-  // KMHG_PACK8=0 keeps the 12-B first stream (A/B, tests).
-  const int sh8 = 64 - 2 * k;
-  const uint64_t seg8 = sh8 >= 12 && sh8 < 64 ? (1ull << sh8) : 0;
-  const uint32_t nseg8 = seg8 ? (uint32_t)(((uint64_t)Nw + seg8 - 1) / seg8) : 0;
-  const char* p8e = test_build_knob("KMHG_PACK8");
-  const bool pack8 = aos && passes == 2 && n_parts < 2 && seg8 && nseg8 <= 256 &&
-                     !(p8e && p8e[0] == '0');
-  // Digit streams (DS): each pass before the last also writes every output element's digit of
-  // the next pass (u8 up to radix 256, else u16), and that pass's histogram reads 1-2 B per
-  // element instead of the keys -- which also takes away the reason to leave the middle streams
-  // unpacked.  The digit writes are short scattered runs (PTILE / R elements per tile and
-  // digit); u8 digits pay once the streams outgrow the Infinity Cache, u16 digits (radix
-  // 257-320: two-pass builds of ~66-100 M windows) did not.  Measured (A/B in one run,
-  // profiles/r5y_ab_ds_*, r5y_ds_sizes_build_only.txt, k = 31 unless noted):
-  //   u8: 500 Mbp (3 passes, radix 79) 18.37 -> 16.82 ms (u16 17.75; histograms 1.93 -> 0.48
-  //     ms); 200 Mbp (3 passes, radix 59) 6.85 -> 6.23; 60 Mbp 1.773 -> 1.744; 40 Mbp
-  //     1.115 -> 1.093; 30 Mbp 0.815 -> 0.804; but 20 Mbp 0.536 -> 0.549 and 16 Mbp
-  //     0.433 -> 0.446 (in cache);
-  //   u16: 100 Mbp (radix 317) 3.127 -> 3.149 ms; config 3 (k = 21, Pack8 first stream)
-  //     2.81 -> 2.93 (histogram -0.11, first scatter +0.22 ms).
-  // Sequence builds with positions on key streams without Pack8, radix <= 256, from
-  // DS_MIN_WINDOWS windows; KMHG_DIGIT_STREAM=0 / 1 forces off / on, KMHG_DS_U8=0 u16 digits.
-  // Bucket-id streams (u32 ids, in-cache sizes) can carry them too, but it is a wash: config 2
-  // histogram 10.2 -> 6.7 us, first scatter +3-6 us, build 0.2076-0.2092 ms either way
-  // (profiles/r5y_ab_ds_bid_config2.log).  KMHG_DS_BID=1 (or KMHG_DIGIT_STREAM=1) turns them on.
-  constexpr int64_t DS_MIN_WINDOWS = 25'000'000;
-  const char* dse = test_build_knob("KMHG_DIGIT_STREAM");
-  const char* dbe = test_build_knob("KMHG_DS_BID");
-  // (a part build's later streams hold ~1/n_parts of the windows)
-  const int64_t ds_windows = n_parts >= 2 ? Nw / n_parts : Nw;
-  const bool ds_keys = !bid && !from_keys && !count_only && passes >= 2 &&
-                       (dse && dse[0] ? dse[0] == '1'
-                                      : !pack8 && R <= 256 && ds_windows >= DS_MIN_WINDOWS);
-  const bool ds_bids = bid && passes >= 2 &&
-                       (dse && dse[0] ? dse[0] == '1' : R <= 256 && dbe && dbe[0] == '1');
-  const bool ds_on = ds_keys || ds_bids;
-  // Digit-pos words: a two-pass bucket-id build carries ONE u32 per window between its passes,
-  // (pass-1 digit << 24) | pos, instead of the (bucket id, pos) pair -- pass 1, its histogram
-  // and the bucket-start level need only that digit (the pass-0 digit is implied by where the
-  // element lies), the radix of a two-pass plan up to BID_MAX_WINDOWS is far below 256 (nb <=
-  // 13,824: R = 118) and the positions fit 24 bits.  Pass 0 writes and pass 1 reads 4 B per
-  // window less, and a tile's digit run is one piece instead of two.  Every other bucket-id
-  // build (one pass, 3+ passes under KMHG_MAXR, digit streams, KMHG_BUILD_BID=1 beyond 2^24
-  // windows) keeps the two arrays.  KMHG_BID_PACK=0 (test build) forces the two arrays.
-  static_assert(BID_MAX_WINDOWS < (int64_t(1) << BID_POS_BITS),
-                "a default bucket-id build's positions fit the digit-pos word");
-  const char* bpe = test_build_knob("KMHG_BID_PACK");
-  const bool bid_pack = bid && passes == 2 && R <= 256 && Nw < (int64_t(1) << BID_POS_BITS) &&
-                        !ds_bids && !(bpe && bpe[0] == '0');
-  if (bid) count_bid_pack(bid_pack);
-  const char* dpe = test_build_knob("KMHG_DS_PACK");
-  const bool ds_pack = ds_keys && !(dpe && dpe[0] == '0');
-  auto packed = [&](int p) {
-    return aos && (p + 1 == (int)passes || R >= AOS_MIN_RADIX || ds_pack);
-  };
-  const bool no_pos = count_only;                        // keys only through the passes
-  // a part of 4+ (key streams): V_hist0 also writes the part's windows compacted per tile into
-  // side 1's arrays (free until then) with their counts; a scan of the counts and one copy make
-  // them a dense (key, position) stream of ~1/n_parts of the windows, and every radix pass runs
-  // over that alone -- instead of encoding and hashing every window again in a first pass over
-  // all of them.  It costs a copy and one more pass over the part's windows, so it pays from 4
-  // parts on (one-GPU rehearsal, tools/part_step.py, per-rank step of 10 Mbp per part: 2 parts
-  // 0.397 -> 0.467 ms, 4 parts 0.504 -> 0.495, 8 parts 0.749 -> 0.581).  KMHG_PART_COMPACT=0 / 1
-  // forces the first pass over every window / the compaction (tests).
-  const char* pce = test_build_knob("KMHG_PART_COMPACT");
-  const bool partc = !from_keys && n_parts >= 2 && !bid && codes &&
-                     (pce ? pce[0] == '1' : n_parts >= 4);
-  // The plan's outcome, once: F(p) = the format of the stream pass p writes, F(-1) = what the
-  // first radix pass reads (the windows of the sequence and a caller's key stream are Keys,
-  // positions implicit).  Everything below -- buffer sizes, which kernel instance a pass, its
-  // histogram, its bucket-start level and the bucket kernel take -- reads this table.
-  std::vector<StreamFmt> fmt(passes + 1);
-  auto F = [&](int p) -> StreamFmt& { return fmt[(size_t)(p + 1)]; };
-  F(-1) = bid ? StreamFmt::Bids : partc && packed(-1) ? StreamFmt::Packed12
-          : partc ? StreamFmt::KeyPos : StreamFmt::Keys;
-  for (int p = 0; p < (int)passes; ++p) {
-    const bool last = p + 1 == (int)passes;
-    F(p) = no_pos ? StreamFmt::Keys
-           : bid  ? (last ? StreamFmt::Pos : bid_pack ? StreamFmt::DigitPos : StreamFmt::BidPos)
-           : pack8 && p == 0 ? StreamFmt::Packed8
-           : packed(p)       ? StreamFmt::Packed12
-                             : StreamFmt::KeyPos;
-  }
-  // pass p also writes the next pass's digits, which that pass's histogram reads instead of F(p)
-  auto ds_out = [&](int p) { return ds_on && p >= 0 && p + 1 < (int)passes; };
-  // Stream p lives on side p mod 2 of two (first array, position array) buffer pairs -- flipped
-  // where the radix passes start at pass 0 in the loop below, so that their first output lands
-  // on side 1 -- each side sized for the widest stream it holds (+ pad).  F(-1) is stored here
-  // only where V_hist0 / V_part_dense wrote it (ids, a part's dense stream).
-  // (Removed in round 4 after measurement, DESIGN.md §5: radix passes writing whole 128-B lines
-  // through LDS write-combining buffers -- config 3 29.2 -> 25.0-28.7 Gbp/s, the 500 Mbp build
-  // 18.1 -> 18.9-22.7 ms.)
-  auto side = [&](int p) { return (p & 1) ^ (from_keys || partc ? 1 : 0); };
-  uint32_t key_bytes[2] = {0, 0};
-  bool pos_array[2] = {false, false};
-  for (int p = bid || partc ? -1 : 0; p < (int)passes; ++p) {
-    key_bytes[side(p)] = std::max(key_bytes[side(p)], fmt_key_bytes(F(p)));
-    pos_array[side(p)] |= fmt_pos_array(F(p));
-  }
-  if (partc) {                 // the compacted tiles: u64 keys and positions on side 1
-    key_bytes[1] = std::max(key_bytes[1], 8u);
-    pos_array[1] = true;
-  }
-  auto kwords = [&](int sd) { return ((uint64_t)(Nw + PTILE) * key_bytes[sd] + 7) / 8; };
+  if (bid) count_bid_pack(P.bid_pack);
+  // two (first array, position array) buffer pairs, stream p on side P.side(p), each side as
+  // wide as the plan says (+ pad)
+  auto kwords = [&](int sd) { return ((uint64_t)(Nw + PTILE) * P.key_bytes[sd] + 7) / 8; };
   DBuf<uint64_t> kA(kwords(0), s), kB(kwords(1), s);
-  DBuf<uint32_t> pA(pos_array[0] ? Nw + PTILE : 1, s), pB(pos_array[1] ? Nw + PTILE : 1, s);
+  DBuf<uint32_t> pA(P.pos_array[0] ? Nw + PTILE : 1, s), pB(P.pos_array[1] ? Nw + PTILE : 1, s);
   auto kptr = [&](int p) -> void* {
-    return p < 0 && from_keys ? const_cast<uint64_t*>(d_keys) : side(p) ? kB.p : kA.p;
+    return p < 0 && from_keys ? const_cast<uint64_t*>(d_keys) : P.side(p) ? kB.p : kA.p;
   };
-  auto pptr = [&](int p) { return side(p) ? pB.p : pA.p; };
+  auto pptr = [&](int p) { return P.side(p) ? pB.p : pA.p; };
   const uint32_t pad = (uint32_t)Nw;
   DBuf<uint32_t> hist(nhist, s);
   DBuf<uint32_t> start((uint64_t)nb + 1, s);
-  DBuf<uint32_t> segb(pack8 ? (uint64_t)R * (nseg8 + 1) : 1, s);
+  DBuf<uint32_t> segb(P.pack8 ? (uint64_t)R * (P.nseg8 + 1) : 1, s);
   // one digit buffer: pass p's histogram has read it before pass p rewrites it for pass p + 1
-  // u8 digits at a radix <= 256 (KMHG_DS_U8=0: u16, A/B)
-  const char* d8e = test_build_knob("KMHG_DS_U8");
-  const bool ds8 = ds_on && R <= 256 && !(d8e && d8e[0] == '0');
-  DBuf<uint16_t> dsb(ds_on ? ((uint64_t)Nw + PTILE + 8) / (ds8 ? 2 : 1) + 8 : 1, s);
-  uint8_t* ds8p = ds8 ? reinterpret_cast<uint8_t*>(dsb.p) : nullptr;
-  uint16_t* ds16p = ds8 ? nullptr : dsb.p;
-  const Pack8 pk8{pack8 ? sh8 : 0, segb.p, nseg8, make_digit(1, R)};
+  DBuf<uint16_t> dsb(P.ds_on ? ((uint64_t)Nw + PTILE + 8) / (P.ds8 ? 2 : 1) + 8 : 1, s);
+  uint8_t* ds8p = P.ds8 ? reinterpret_cast<uint8_t*>(dsb.p) : nullptr;
+  uint16_t* ds16p = P.ds8 ? nullptr : dsb.p;
+  const Pack8 pk8{P.pack8 ? P.sh8 : 0, segb.p, P.nseg8, make_digit(1, R)};
   // scratch (zeroed in-kernel by V_hist0 / V_hist, no memset): [n_valid][meta][scan status]
   const size_t off_meta = 64, off_status = 128;
-  const uint32_t n_status = scan_tiles + 1;               // look-back words + ticket
+  const uint32_t n_status = P.scan_tiles + 1;               // look-back words + ticket
   const size_t scratch_bytes = off_status + (size_t)n_status * 8;
   DBuf<uint8_t> scratch(scratch_bytes, s);
   uint8_t* sc = scratch.p;
@@ -1444,7 +1225,7 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
   uint64_t* status = reinterpret_cast<uint64_t*>(sc + off_status);
   idx->rec = PinnedPool::get().take();                     // V_stats writes the totals here
   if (!co_auto) idx->table.reset(idx->slots());
-  idx->positions.reset(no_pos ? 1 : Nw);
+  idx->positions.reset(P.no_pos ? 1 : Nw);
   idx->bstats.reset(nb);            // kept: a batch index's walk takes its row offsets from it
   // co_auto: HLL rows of the first histogram pass, V_hll's registers + ticket, its pinned record
   DBuf<uint32_t> hll_rows(co_auto ? (size_t)ntiles * (HLL_REGS / 4) : 1, s);
@@ -1468,7 +1249,7 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
   } else {
     // a position index keeps its sequence's code words + window bits for the diagonal query
     // path (code words + N flags, 0.5 B per window with the first query's bits; V_hist0 writes them)
-    if (codes) {
+    if (rq.codes) {
       idx->dcodes.reset(diag_block_words(Nw));
       db = idx->diag_block_of();
     }
@@ -1486,13 +1267,13 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
       LAUNCH("k_v2_scatter_seq", s,
              launch_v2_scatter(bid ? ScatterIn::first_pass(kptr(-1), Nw)
                                    : ScatterIn::sequence(d_seq, L, k, Nw),
-                               F(-1), F(0), kptr(0), pptr(0), pad, n_valid, g, make_digit(1, R),
-                               hist.p, ntiles, s, nullptr, pack8 ? &pk8 : nullptr,
-                               ds_out(0) ? &ds0 : nullptr));
+                               P.F(-1), P.F(0), kptr(0), pptr(0), pad, n_valid, g, make_digit(1, R),
+                               hist.p, ntiles, s, nullptr, P.pack8 ? &pk8 : nullptr,
+                               P.ds_out(0) ? &ds0 : nullptr));
       // the segment table, before pass 1's histogram overwrites pass 0's
-      if (pack8)
+      if (P.pack8)
         LAUNCH("k_seg_bounds", s,
-               launch_seg_bounds(hist.p, ntiles, R, nseg8, (uint32_t)(seg8 / PTILE), n_valid,
+               launch_seg_bounds(hist.p, ntiles, R, P.nseg8, (uint32_t)(P.seg8 / PTILE), n_valid,
                                  segb.p, s));
       div = R;
     }
@@ -1505,7 +1286,7 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
   uint32_t C = ntiles, nst = n_status;
   uint64_t nh = nhist;
   DBuf<uint32_t> hist1;
-  if (n_parts >= 2 && (passes > 1 || partc)) {
+  if (rq.n_parts >= 2 && (passes > 1 || partc)) {
     uint32_t nv = 0;
     HIPC(hipMemcpyAsync(&nv, n_valid, 4, hipMemcpyDeviceToHost, s));
     HIPC(hipStreamSynchronize(s));
@@ -1522,15 +1303,11 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
   }
   if (partc)   // the part's windows, dense in window order: every radix pass reads these
     LAUNCH("k_part_dense", s, launch_part_dense(kB.p, pB.p, tcnt.p, ntiles, n_valid, kptr(-1),
-                                                pptr(-1), F(-1), s));
+                                                pptr(-1), P.F(-1), s));
   // where pass 1 saves column 0: pass 0's histogram is hp's unless pass 0 was the one over
   // every window (its own layout, copied above)
   uint32_t* save1 = hp == hist.p || partc ? lo_save.p : nullptr;
-  // each level of the bucket starts rides in its pass (BoundsFuse), except the last one of a
-  // count-only build whose spread is chosen after the passes (co_auto); KMHG_FUSE_BOUNDS=0
-  // (A/B) launches every level on its own
-  const char* fbe = test_build_knob("KMHG_FUSE_BOUNDS");
-  const bool fuse_on = !(fbe && fbe[0] == '0');
+  // each level of the bucket starts rides in its pass (BoundsFuse) where the plan fused it
   auto level_of = [&](uint32_t p, uint32_t spread) {
     uint64_t dv = 1;                                    // R^p lower-digit values
     for (uint32_t i = 0; i < p; ++i) dv *= R;
@@ -1540,15 +1317,14 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
     return BoundsFuse{lin, lout, make_digit((uint32_t)dv, R), (uint32_t)dv, spread,
                       last ? g.nb : (uint32_t)(dv * R)};
   };
-  auto fused = [&](uint32_t p) { return p >= 1 && fuse_on && !(co_auto && p + 1 == passes); };
   auto launch_level = [&](uint32_t p, const BoundsFuse& f) {   // over pass p's input
     LAUNCH("k_v2_bounds", s,
-           launch_v2_bounds_lo(F((int)p - 1), kptr((int)p - 1), n_valid, g, f.Dlast, f.div, hp, C,
+           launch_v2_bounds_lo(P.F((int)p - 1), kptr((int)p - 1), n_valid, g, f.Dlast, f.div, hp, C,
                                f.lo_start, f.spread, f.start, f.nlim, s, pk8.sh));
   };
   // the radix passes left: histogram (of the digits the pass before left, else of its input),
   // scan, scatter with the fused level, the level on its own where it is not fused
-  for (uint32_t p = from_keys || partc ? 0 : 1; p < passes; ++p) {
+  for (uint32_t p = P.first_pass; p < passes; ++p) {
     const Digit Dp = make_digit(div, R);
     const bool keys0 = from_keys && p == 0;
     const bool last = p + 1 == passes;
@@ -1558,11 +1334,13 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
       LAUNCH("k_v2_hist", s,
              launch_v2_hist_keys0(d_keys, n_valid, g, Dp, hp, C, status, nst, s,
                                   hll ? hll_rows.p : nullptr, hll ? hll_regs.p : nullptr,
-                                  skip_empty));
+                                  rq.skip_empty));
     else
       LAUNCH("k_v2_hist", s,
-             launch_v2_hist(!ds_out(pi) ? F(pi) : ds8 ? StreamFmt::Digits8 : StreamFmt::Digits16,
-                            ds_out(pi) ? dsb.p : kptr(pi), n_valid, g, Dp, hp, C, status, nst, s,
+             launch_v2_hist(!P.ds_out(pi) ? P.F(pi)
+                            : P.ds8       ? StreamFmt::Digits8
+                                          : StreamFmt::Digits16,
+                            P.ds_out(pi) ? dsb.p : kptr(pi), n_valid, g, Dp, hp, C, status, nst, s,
                             p == 1 ? save1 : nullptr, pk8.sh));
     LAUNCH("k_scan_u32", s, launch_scan_u32(hp, nh, status, n_valid, s));
     if (hll) {   // after the scan: the estimate travels with the valid key count
@@ -1574,12 +1352,12 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
     const BoundsFuse lv = level_of(p, 1u);              // (pass 0 has none: never fused)
     const DigitOut dsn{ds16p, make_digit(div * R, R), ds8p};
     LAUNCH("k_v2_scatter", s,
-           launch_v2_scatter(keys0 ? ScatterIn::first_pass(d_keys, Nw, skip_empty)
+           launch_v2_scatter(keys0 ? ScatterIn::first_pass(d_keys, Nw, rq.skip_empty)
                                    : ScatterIn::stream(kptr(pi), pptr(pi)),
-                             F(pi), F((int)p), kptr((int)p), pptr((int)p), pad, n_valid, g, Dp, hp,
-                             C, s, fused(p) ? &lv : nullptr, pack8 ? &pk8 : nullptr,
-                             ds_out((int)p) ? &dsn : nullptr));
-    if (p >= 1 && !fused(p) && !last) launch_level(p, lv);
+                             P.F(pi), P.F((int)p), kptr((int)p), pptr((int)p), pad, n_valid, g, Dp,
+                             hp, C, s, P.fused(p) ? &lv : nullptr, P.pack8 ? &pk8 : nullptr,
+                             P.ds_out((int)p) ? &dsn : nullptr));
+    if (p >= 1 && !P.fused(p) && !last) launch_level(p, lv);
     div *= R;
   }
   const int last_p = (int)passes - 1;   // its stream is the bucket kernel's
@@ -1590,7 +1368,7 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
     idx->co_est = hrec.meta->distinct_est;
     const uint64_t n_keys_valid = hrec.meta->n_positions;
     PinnedPool::get().give(hrec, false);
-    idx->co_spread = co_spread_for(idx->co_est, n_keys_valid);
+    idx->co_spread = co_spread_for(idx->co_est, n_keys_valid, kn.co_spread);
     gb = Geom{nb / (uint32_t)idx->co_spread, V2_CAPW};
     idx->geom = gb;
     idx->table.reset(idx->slots());
@@ -1601,7 +1379,7 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
            launch_v2_bounds_lo(StreamFmt::Keys, nullptr, n_valid, g, make_digit(1, R), 1u,
                                partc ? hp : hist.p, partc ? C : ntiles, nullptr, g.nb / gb.nb,
                                start.p, g.nb, s));
-  } else if (!fused(passes - 1)) {
+  } else if (!P.fused(passes - 1)) {
     launch_level(passes - 1, level_of(passes - 1, g.nb / gb.nb));
   }
 #ifdef KMHG_STAMPS
@@ -1612,45 +1390,33 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
 #endif
   // tests only: a corrupted stream or bound (KMHG_TEST_DISORDER=1|2|3) -> the bucket kernel's
   // checks -> v1 rebuild
-  if (const char* td = test_build_knob("KMHG_TEST_DISORDER"))
-    if (!no_pos && td[0] >= '1' && td[0] <= '3')
-      launch_v2_test_disorder(F(last_p), kptr(last_p), pptr(last_p), start.p, n_valid,
-                              td[0] - '0', s);
-  // Build-time tags (round 6): a position build beyond the cache (key
-  // streams, Nw > BID_MAX_WINDOWS) writes the diagonal query path's slot tags and repeated-key
-  // bits itself, so the first seq.kmer.pos of a new index does not pay V_diag_prep (2.6 ms at
-  // 500 Mbp, +70 % on the query).  In cache (config 2) the build is the headline and the
-  // preparation stays with the first query (round-3 A/B: tags in the build +1-1.5 % there).
-  // A part of an owner-computes build does the same for its own slots and keys (the owner-
-  // routed query runs the diagonal path on it).  KMHG_BUILD_TAGS=0 / 1 (test build) forces
-  // either on key streams.
+  if (kn.test_disorder && !P.no_pos)
+    launch_v2_test_disorder(P.F(last_p), kptr(last_p), pptr(last_p), start.p, n_valid,
+                            kn.test_disorder, s);
+  // Build-time tags (the plan's want_tags): the build writes the diagonal query path's slot
+  // tags and repeated-key bits itself
   uint8_t* tg = nullptr;
   uint32_t* rep = nullptr;
-  {
-    const char* bte = test_build_knob("KMHG_BUILD_TAGS");
-    const bool want = codes && !bid && !from_keys && !count_only &&
-                      (bte ? bte[0] == '1' : Nw > BID_MAX_WINDOWS);
-    if (want) {
-      try {
-        idx->ptag.reset(idx->slots() + 32);    // + the 32-B span the last probe group reads
-        idx->ptag.bind(s);
-        tg = idx->ptag.p;
-        rep = db.uniq;
-        HIPC(hipMemsetAsync(rep, 0, diag_uniq_words(Nw) * 4, s));
-        // the side slot's tag (its key is the empty sentinel: 0) and the tail
-        HIPC(hipMemsetAsync(tg + idx->slots() - 1, 0, 33, s));
-      } catch (const Error& e) {               // no room for the tags: the first query makes them
-        if (e.code != KMHG_ENOMEM) throw;
-        (void)hipGetLastError();
-        tg = nullptr;
-        rep = nullptr;
-      }
+  if (P.want_tags) {
+    try {
+      idx->ptag.reset(idx->slots() + 32);    // + the 32-B span the last probe group reads
+      idx->ptag.bind(s);
+      tg = idx->ptag.p;
+      rep = db.uniq;
+      HIPC(hipMemsetAsync(rep, 0, diag_uniq_words(Nw) * 4, s));
+      // the side slot's tag (its key is the empty sentinel: 0) and the tail
+      HIPC(hipMemsetAsync(tg + idx->slots() - 1, 0, 33, s));
+    } catch (const Error& e) {               // no room for the tags: the first query makes them
+      if (e.code != KMHG_ENOMEM) throw;
+      (void)hipGetLastError();
+      tg = nullptr;
+      rep = nullptr;
     }
   }
   LAUNCH("k_v2_bucket_wg", s,
-         launch_v2_bucket_wg(F(last_p), kptr(last_p), pptr(last_p), start.p, gb, idx->table.p,
+         launch_v2_bucket_wg(P.F(last_p), kptr(last_p), pptr(last_p), start.p, gb, idx->table.p,
                              idx->positions.p, idx->bstats.p, meta, s, n_valid, (uint32_t)Nw,
-                             db.code, k, tg, rep, bucket_place_on(), bucket_place_counters()));
+                             db.code, k, tg, rep, kn.bucket_place, bucket_place_counters()));
   idx->tags_built = tg != nullptr;
   LAUNCH("k_v2_stats", s, launch_v2_stats(idx->bstats.p, gb.nb, n_valid, meta, idx->rec.meta, s));
   idx->bstats_nb = gb.nb;
@@ -1663,7 +1429,7 @@ kmhg_index* build_device_v2(const uint8_t* d_seq, int64_t L, int k, hipStream_t 
 #endif
   // no wait here: the build completes in stream order and finish_build() collects the totals
   idx->pending = true;
-  idx->src = d_src;
+  idx->src = in.d_seq;             // the caller's buffer (the v1 fallback re-reads it)
   return idx.release();
 }
 
@@ -1736,7 +1502,7 @@ kmhg_index* build_device(const uint8_t* d_seq, int64_t L, int k, hipStream_t s, 
   if (const char* e = test_build_knob("KMHG_DIAG_CODES"))   // tests / A/B: no code block
     if (e[0] == '0') codes = false;
   if (build_version() == 2)
-    return build_device_v2(d_seq, L, k, s, nullptr, 0, false, 1, false, codes);
+    return build_device_v2(BuildRequest::sequence(L, k, codes), StreamPtrs{d_seq, nullptr}, s);
   return build_device_v1(d_seq, L, k, s);
 }
 
@@ -2072,7 +1838,7 @@ void count_device(kmhg_index* idx, const uint8_t* d_seq, int64_t L, uint32_t sou
   // allocated or written for a batch that is discarded after the merge); KMHG_COUNT_BID=0 (A/B)
   // builds every batch with key streams
   const char* cbe = test_build_knob("KMHG_COUNT_BID");
-  const bool codes = !(cbe && cbe[0] == '0') && bid_streams_for(L - k + 1);
+  const bool codes = !(cbe && cbe[0] == '0') && bid_streams_for(L - k + 1, read_build_knobs());
   std::unique_ptr<kmhg_index> B(build_device(d_seq, L, k, s, codes));
   Release rel{B.get(), s};
   finish_build(B.get());
@@ -2132,7 +1898,8 @@ void merge_batch(kmhg_index* idx, kmhg_index* B, uint32_t source, uint64_t base,
   std::unique_ptr<kmhg_index> K;
   bool ovf = true;
   if (!probe_only) {
-    K.reset(build_device_v2(nullptr, 0, k, s, idx->ckeys.p, (int64_t)U1));
+    K.reset(build_device_v2(BuildRequest::key_stream(k, (int64_t)U1),
+                            StreamPtrs{nullptr, idx->ckeys.p}, s));
     HIPC(hipEventSynchronize(K->rec.ev));
     ovf = K->rec.meta->overflow != 0;
     PinnedPool::get().give(K->rec, false);
@@ -2260,8 +2027,8 @@ double qll_host(int q) {   // the same table on the host (the iterator's thresho
 // `keys` is a padded stream (EMPTY_KEY entries skipped, k <= 31).
 std::unique_ptr<kmhg_index> count_only_build(const uint64_t* keys, uint32_t total, int k,
                                              int spread, hipStream_t s, bool& overflow) {
-  std::unique_ptr<kmhg_index> B(
-      build_device_v2(nullptr, 0, k, s, keys, (int64_t)total, true, spread, true));
+  std::unique_ptr<kmhg_index> B(build_device_v2(
+      BuildRequest::count_keys(k, (int64_t)total, spread), StreamPtrs{nullptr, keys}, s));
   HIPC(hipEventSynchronize(B->rec.ev));
   const BuildMeta hm = *B->rec.meta;
   PinnedPool::get().give(B->rec, false);
@@ -3027,8 +2794,9 @@ int kmhg_build_device_part(const void* d_seq, size_t L, int k, int part, int n_p
     if (const char* e = test_build_knob("KMHG_BUILD"))
       if (std::string(e) == "v1") fail(KMHG_EINVAL, "part builds need the partitioned build");
     hipStream_t s = (hipStream_t)stream;
-    *out = build_device_v2((const uint8_t*)d_seq, (int64_t)L, k, s, nullptr, 0, false, 1, false,
-                           true, (uint32_t)part, (uint32_t)n_parts);
+    *out = build_device_v2(
+        BuildRequest::sequence_part((int64_t)L, k, (uint32_t)part, (uint32_t)n_parts),
+        StreamPtrs{(const uint8_t*)d_seq, nullptr}, s);
   });
 }
 

@@ -2,28 +2,16 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kmhg_common.h"
+#include "kmhg_plan.h"
 
 namespace kmhg {
 
 constexpr uint32_t LARGE_MIN = 64;     // keys with >= this many positions sort per workgroup
-// partitioned build (kmhg_build_v2.hip)
-// group buckets: mean windows per bucket and LDS sub-table slots (load 2/3).  Variant builds
-// (A/B, `make variant`) may set -DKMHG_BW_WG=2048 -DKMHG_CAPW=3072 -DKMHG_BUCKET_WGS=4.
-#ifndef KMHG_BW_WG
-#define KMHG_BW_WG 1024
-#endif
-#ifndef KMHG_CAPW
-#define KMHG_CAPW 1536
-#endif
-#ifndef KMHG_BUCKET_WGS
-#define KMHG_BUCKET_WGS 8      // workgroups per CU the compact LDS table allows (1,536 slots)
-#endif
-constexpr uint32_t V2_BW_WG = KMHG_BW_WG;
-constexpr uint32_t V2_CAPW = KMHG_CAPW;  // slots per group bucket (LDS sub-table of one workgroup)
+// partitioned build (kmhg_build_v2.hip): the bucket geometry (V2_BW_WG, V2_CAPW,
+// KMHG_BUCKET_WGS) and V2_MAXR_IL are kmhg_plan.h's
 constexpr uint32_t V2_SLOT_BITS_WG = V2_CAPW >= 2048 ? 12 : 11;
 static_assert(V2_CAPW < (1u << V2_SLOT_BITS_WG), "slot index bits");
 constexpr uint32_t V2_MAXR = 640;      // LDS digit arrays of the histogram / bounds kernels
-constexpr uint32_t V2_MAXR_IL = 320;   // max radix of one partition pass (the scatter's LDS)
 constexpr uint32_t SORT_CHUNK = 4096;  // LDS bitonic chunk (16 KiB)
 
 struct BuildMeta {              // written by the build kernels, read once by the host
@@ -187,41 +175,7 @@ inline Digit make_digit(uint32_t div, uint32_t R) {
   while ((1u << d.nbits) < R) ++d.nbits;
   return d;
 }
-// What one element of a radix stream looks like.  The engine's plan, the launch wrappers and the
-// kernels' template parameters all name a stream's layout with this one type (DESIGN.md "Radix
-// stream formats" keeps the earlier per-kernel mode numbers findable).
-enum class StreamFmt : int {
-  Keys,      // u64 key only; the position is implicit (e + 1) or unused: a caller's key stream,
-             // the windows of the sequence, the streams of a count-only build
-  KeyPos,    // u64 key array + u32 pos array
-  Packed12,  // one 12-B element {key lo, key hi, pos}
-  Packed8,   // one 8-B element, key << sh | window-in-segment (Pack8 below)
-  Bids,      // u32 bucket id only (~0 = not indexed), position implicit: V_hist0's ids
-  BidPos,    // u32 bucket-id array + u32 pos array
-  DigitPos,  // one u32 digit-pos word, (the reading pass's digit << BID_POS_BITS) | pos
-  Pos,       // u32 pos only: what the last bucket-id pass writes
-  Digits8,   // the next pass's digit of each element, u8 / u16 (DigitOut below): read by that
-  Digits16,  // pass's histogram only
-};
-constexpr int BID_POS_BITS = 24;
-// the stream belongs to a bucket-id build: u32 words, digits without hashing
-constexpr bool fmt_bid(StreamFmt f) {
-  return f == StreamFmt::Bids || f == StreamFmt::BidPos || f == StreamFmt::DigitPos ||
-         f == StreamFmt::Pos;
-}
-// the positions travel in an array of their own (pin / pout)
-constexpr bool fmt_pos_array(StreamFmt f) {
-  return f == StreamFmt::KeyPos || f == StreamFmt::BidPos || f == StreamFmt::Pos;
-}
-// bytes per element of the stream's first array (kin / kout; 0: there is none)
-constexpr uint32_t fmt_key_bytes(StreamFmt f) {
-  return f == StreamFmt::Pos ? 0 : f == StreamFmt::Digits8 ? 1 : f == StreamFmt::Digits16 ? 2
-         : fmt_bid(f) ? 4 : f == StreamFmt::Packed12 ? 12 : 8;
-}
-// where an element's position lies, in u32 words of the array that holds it: offset and stride
-// (Packed12 keeps it inside the element; only formats that carry a position)
-constexpr uint32_t fmt_pos_word(StreamFmt f) { return f == StreamFmt::Packed12 ? 2 : 0; }
-constexpr uint32_t fmt_pos_stride(StreamFmt f) { return f == StreamFmt::Packed12 ? 3 : 1; }
+// StreamFmt, what one element of a radix stream looks like, and its predicates: kmhg_plan.h.
 
 // Radix passes run over tiles of PTILE windows; histograms are [digit][tile] (ntiles columns),
 // and the persistent scatter grids give every XCD one contiguous tile range (xcd_remap).

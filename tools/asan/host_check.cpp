@@ -3,7 +3,8 @@
 // with fortify / stack protection, src/debug.sh:17-23).  Built by tools/asan/Makefile, driven by
 // tests/test_asan_host.py (CPU only).  What runs here is exactly the source the product and the
 // checker compile: kmhg_fastx.h (the FASTA/FASTQ reader that parses untrusted input),
-// kmhg_khash.h (the khash row-order replay), oracle/kmer_oracle.c and oracle/sh_oracle.c.
+// kmhg_khash.h (the khash row-order replay), kmhg_plan.h (the partitioned build's plan),
+// oracle/kmer_oracle.c and oracle/sh_oracle.c.
 //
 //   host_check fastx <path> <max_records>   one line per record: R <len> <has_qual> <fnv seq>
 //                                           <fnv qual>, then E <last return code>
@@ -12,17 +13,25 @@
 //   host_check index <path> <k>             orc_index_build + orc_query (self) of the file's
 //                                           bytes: U N P maxn H <wsum rows>
 //   host_check reads <path> <k> <min_q>     orc_read_kmers of every record: n <wsum keys>
+//   host_check plan <request> [round=<device round>] [KMHG_<knob>=<value> ...]
+//                                           plan_build's plan, one line of field=value.  Request:
+//                                           seq L=<chars> k=<k> [codes=0|1] [part=<p> n_parts=<n>]
+//                                           | keys n=<keys> k=<k> | count n=<keys> k=<k> spread=<s>
+//   host_check plan @<file>                 one plan per line of the file (the same arguments)
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <set>
+#include <sstream>
 #include <string>
 #include <type_traits>
 #include <vector>
 
 #include "../../kmer_hasher_amd/csrc/kmhg_fastx.h"
 #include "../../kmer_hasher_amd/csrc/kmhg_khash.h"
+#include "../../kmer_hasher_amd/csrc/kmhg_plan.h"
 
 extern "C" {
 long orc_windows(const char* seq, long L, int k, uint64_t* keys, int32_t* s, int32_t* e);
@@ -157,9 +166,75 @@ static int cmd_reads(const char* path, int k, int min_q) {
   return 0;
 }
 
+// one request line -> one line with the plan's fields; false: bad arguments
+static bool plan_line(const std::vector<std::string>& a) {
+  using namespace kmhg;
+  if (a.empty()) return false;
+  long long L = 0, n = 0, k = 0, codes = 1, part = 0, n_parts = 0, spread = 1, round = 0;
+  BuildKnobs kn;
+  for (size_t i = 1; i < a.size(); ++i) {
+    const size_t eq = a[i].find('=');
+    if (eq == std::string::npos) return false;
+    const std::string name = a[i].substr(0, eq), v = a[i].substr(eq + 1);
+    long long* dst = name == "L" ? &L : name == "n" ? &n : name == "k" ? &k
+                     : name == "codes" ? &codes : name == "part" ? &part
+                     : name == "n_parts" ? &n_parts : name == "spread" ? &spread
+                     : name == "round" ? &round : nullptr;
+    if (dst) *dst = atoll(v.c_str());
+    else if (!set_build_knob(kn, name.c_str(), v.c_str())) return false;
+  }
+  BuildRequest rq;
+  if (a[0] == "seq")
+    rq = n_parts ? BuildRequest::sequence_part(L, (int)k, (uint32_t)part, (uint32_t)n_parts)
+                 : BuildRequest::sequence(L, (int)k, codes != 0);
+  else if (a[0] == "keys") rq = BuildRequest::key_stream((int)k, n);
+  else if (a[0] == "count") rq = BuildRequest::count_keys((int)k, n, (int)spread);
+  else return false;
+  const BuildPlan P = plan_build(rq, kn, (uint32_t)round);
+  if (P.err) { printf("err=%d msg=%s\n", P.err, P.msg); return true; }
+  printf("err=0 empty=%d Nw=%lld ntiles=%u nb=%u b0=%u nbh=%u", P.empty_part ? 1 : 0,
+         (long long)P.Nw, P.ntiles, P.geom.nb, P.geom.b0, P.geom.nbh);
+  if (P.empty_part) { printf("\n"); return true; }
+  printf(" R=%u passes=%u first=%u bid=%d bid_pack=%d aos=%d pack8=%d sh8=%d nseg8=%u ds=%d ds8=%d"
+         " partc=%d co_auto=%d tags=%d nhist=%llu scan_tiles=%u key_bytes=%u,%u pos_array=%d,%d",
+         P.R, P.passes, P.first_pass, P.bid, P.bid_pack, P.aos, P.pack8, P.sh8, P.nseg8, P.ds_on,
+         P.ds8, P.partc, P.co_auto, P.want_tags, (unsigned long long)P.nhist, P.scan_tiles,
+         P.key_bytes[0], P.key_bytes[1], P.pos_array[0], P.pos_array[1]);
+  const int passes = (int)P.passes;
+  printf(" fmt=");
+  for (int p = -1; p < passes; ++p) printf("%s%s", p < 0 ? "" : ",", fmt_name(P.F(p)));
+  printf(" side=");
+  for (int p = -1; p < passes; ++p) printf("%s%d", p < 0 ? "" : ",", P.side(p));
+  printf(" ds_out=");
+  for (int p = -1; p < passes; ++p) printf("%s%d", p < 0 ? "" : ",", P.ds_out(p) ? 1 : 0);
+  printf(" fused=");
+  for (int p = 0; p < passes; ++p) printf("%s%d", p ? "," : "", P.fused((uint32_t)p) ? 1 : 0);
+  printf("\n");
+  return true;
+}
+
+static int cmd_plan(int argc, char** argv) {
+  if (argc == 3 && argv[2][0] == '@') {
+    std::ifstream f(argv[2] + 1);
+    if (!f) { perror(argv[2] + 1); return 2; }
+    std::string line;
+    while (std::getline(f, line)) {
+      std::istringstream is(line);
+      std::vector<std::string> a;
+      for (std::string w; is >> w;) a.push_back(w);
+      if (!plan_line(a)) { fprintf(stderr, "bad plan arguments: %s\n", line.c_str()); return 2; }
+    }
+    return 0;
+  }
+  if (plan_line(std::vector<std::string>(argv + 2, argv + argc))) return 0;
+  fprintf(stderr, "bad plan arguments\n");
+  return 2;
+}
+
 int main(int argc, char** argv) {
   if (argc < 3) { fprintf(stderr, "usage: see the file header\n"); return 2; }
   const std::string c = argv[1];
+  if (c == "plan") return cmd_plan(argc, argv);
   if (c == "fastx" && argc == 4) return cmd_fastx(argv[2], atol(argv[3]));
   if (c == "khash" && argc == 4) return cmd_khash(atol(argv[2]), strtoull(argv[3], nullptr, 10));
   if (c == "index" && argc == 4) return cmd_index(argv[2], atoi(argv[3]));
