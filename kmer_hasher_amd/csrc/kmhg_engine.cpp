@@ -7,7 +7,6 @@
 // Reference entry points each C function replaces are listed in include/kmhgpu.h.
 #include <atomic>
 #include <hip/hip_runtime.h>
-#include <sched.h>
 #include <sys/mman.h>
 
 #include <algorithm>
@@ -16,8 +15,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <condition_variable>
-#include <deque>
 #include <exception>
 #include <functional>
 #include <map>
@@ -30,6 +27,7 @@
 #include "kmhg_common.h"
 #include "kmhg_kernels.h"
 #include "kmhg_plan.h"
+#include "kmhg_hostwork.h"
 #include "kmhg_parts_read.h"
 #include "kmhg_fastx.h"
 #include "kmhg_khash.h"
@@ -112,7 +110,7 @@ class DevicePool {
   }
   void* alloc(size_t bytes) {
     if (bytes == 0) bytes = 256;
-    size_t sz = round(bytes);
+    size_t sz = pool_size_class(bytes);
     int dev = 0;
     HIPC(hipGetDevice(&dev));
     {
@@ -189,17 +187,7 @@ class DevicePool {
   // the group's blocks: one event recorded on `stream` for all of them
   void release_batch(const std::vector<void*>& ps, hipStream_t stream) {
     if (ps.empty()) return;
-    hipEvent_t ev = nullptr;
-    {
-      std::lock_guard<std::mutex> g(mu_);
-      if (!events_.empty()) { ev = events_.back(); events_.pop_back(); }
-    }
-    if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) ev = nullptr;
-    if (!ev || hipEventRecord(ev, stream) != hipSuccess) {
-      (void)hipStreamSynchronize(stream);
-      if (ev) { std::lock_guard<std::mutex> g(mu_); events_.push_back(ev); }
-      ev = nullptr;
-    }
+    hipEvent_t ev = recorded_event(stream);
     std::lock_guard<std::mutex> g(mu_);
     size_t owner = SIZE_MAX;            // the last entry actually queued recycles the event
     for (size_t i = 0; i < ps.size(); ++i) {
@@ -232,19 +220,7 @@ class DevicePool {
   }
   void release_one(void* p, hipStream_t stream, bool ordered) {
     if (!p) return;
-    hipEvent_t ev = nullptr;
-    if (ordered) {
-      {
-        std::lock_guard<std::mutex> g(mu_);
-        if (!events_.empty()) { ev = events_.back(); events_.pop_back(); }
-      }
-      if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) ev = nullptr;
-      if (!ev || hipEventRecord(ev, stream) != hipSuccess) {
-        (void)hipStreamSynchronize(stream);
-        if (ev) { std::lock_guard<std::mutex> g(mu_); events_.push_back(ev); }
-        ev = nullptr;
-      }
-    }
+    hipEvent_t ev = ordered ? recorded_event(stream) : nullptr;
     std::lock_guard<std::mutex> g(mu_);
     auto it = live_.find(p);
     if (it == live_.end()) return;
@@ -284,6 +260,22 @@ class DevicePool {
   // owns_ev: the one entry of a batch that recycles the shared event.  An entry polled after
   // its batch's event was recycled and recorded again only waits for later work (safe).
   struct Pending { void* p; std::pair<int, size_t> key; hipEvent_t ev; bool owns_ev; };
+  // An event (recycled if one is idle) recorded on `stream`; where none can be made or recorded,
+  // the stream is synchronized instead and nullptr returned.  Takes mu_ itself: call unlocked.
+  hipEvent_t recorded_event(hipStream_t stream) {
+    hipEvent_t ev = nullptr;
+    {
+      std::lock_guard<std::mutex> g(mu_);
+      if (!events_.empty()) { ev = events_.back(); events_.pop_back(); }
+    }
+    if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) ev = nullptr;
+    if (!ev || hipEventRecord(ev, stream) != hipSuccess) {
+      (void)hipStreamSynchronize(stream);
+      if (ev) { std::lock_guard<std::mutex> g(mu_); events_.push_back(ev); }
+      ev = nullptr;
+    }
+    return ev;
+  }
   void poll_pending() {
     for (size_t i = 0; i < pending_.size();) {
       if (hipEventQuery(pending_[i].ev) == hipSuccess) {
@@ -300,15 +292,6 @@ class DevicePool {
   }
   static constexpr size_t BEST_FIT_MIN = (size_t)256 << 20;
   static constexpr size_t POOL_DEPTH = 1;   // depth 2 measured: no gain
-  static size_t round(size_t b) {
-    if (b <= (1u << 20)) {           // small: power of two >= 256 B
-      size_t r = 256;
-      while (r < b) r <<= 1;
-      return r;
-    }
-    const size_t g = 2u << 20;       // large: 2 MiB granules
-    return (b + g - 1) / g * g;
-  }
   std::mutex mu_;
   std::map<std::pair<int, size_t>, std::vector<void*>> free_;
   std::map<std::pair<int, size_t>, size_t> count_;   // blocks of each size class (any state)
@@ -520,110 +503,12 @@ hipStream_t lib_stream() {
   return s;
 }
 
-// Host worker pool for the host-side copies: HOST_WORKERS threads made on first use and kept,
-// so a call that splits a few MB over threads does not pay their creation and join (8 threads:
-// ~0.1-0.35 ms a round -- per 16-MB chunk of a staged copy before).  run(n, fn) runs fn(0) ..
-// fn(n - 1), the calling thread taking tasks too, and returns when all are done; calls from
-// several threads at once (a multi-device query's parts) share the workers.  No task may call
-// run() itself.  big = true (GB-scale writes: the expansions) starts fresh threads instead: the
-// kernel spreads new threads over the machine's memory controllers, while woken pool workers
-// crowd near their waker (A/B in one run, profiles/r6al_pool_ab/: config 5's run expansion
-// 18-21 ms fresh, 30-54 pooled; config 4's pair rows 108-112 fresh, 99-164 pooled).
-constexpr uint64_t HOST_BIG_BYTES = 512u << 20;   // (config 2's 80 MB of rows: pooled 0.84-0.91
-                                                  // ms, fresh 1.19-1.41; profiles/r6ak*, r6al*)
-class HostPool {
- public:
-  static constexpr int HOST_WORKERS = 15;        // + the calling thread = 16
-  static HostPool& get() {
-    static HostPool p;
-    return p;
-  }
-  void run(int n, const std::function<void(int)>& fn, bool big = false) {
-    if (n <= 1) {
-      if (n == 1) fn(0);
-      return;
-    }
-    const char* pe = test_build_knob("KMHG_HOST_POOL");   // "0": a thread per task (A/B)
-    if (big || (pe && pe[0] == '0')) {
-      std::vector<std::thread> th;
-      for (int i = 1; i < n; ++i) th.emplace_back(fn, i);
-      fn(0);
-      for (auto& t : th) t.join();
-      return;
-    }
-    Job job{&fn, n};
-    {
-      std::lock_guard<std::mutex> g(mu_);
-      if (workers_.empty()) start();
-      jobs_.push_back(&job);
-    }
-    cv_.notify_all();
-    work_on(job, false);                         // until every task is handed out
-    {
-      std::lock_guard<std::mutex> g(mu_);        // no worker takes the job from here on
-      for (auto it = jobs_.begin(); it != jobs_.end(); ++it)
-        if (*it == &job) {
-          jobs_.erase(it);
-          break;
-        }
-    }
-    std::unique_lock<std::mutex> g(job.m);       // the job lives until its last worker is out
-    job.cv.wait(g, [&] { return job.done == job.n && job.refs == 0; });
-  }
-  ~HostPool() {
-    {
-      std::lock_guard<std::mutex> g(mu_);
-      stop_ = true;
-    }
-    cv_.notify_all();
-    for (auto& t : workers_) t.join();
-  }
-
- private:
-  struct Job {
-    const std::function<void(int)>* fn;
-    int n;
-    std::atomic<int> next{0};
-    int done = 0, refs = 0;                      // guarded by m (refs: workers inside)
-    std::mutex m;
-    std::condition_variable cv;
-    Job(const std::function<void(int)>* f, int count) : fn(f), n(count) {}
-  };
-  void work_on(Job& job, bool worker) {
-    int ran = 0;
-    for (int i; (i = job.next.fetch_add(1)) < job.n; ++ran) (*job.fn)(i);
-    std::lock_guard<std::mutex> g(job.m);
-    job.done += ran;
-    if (worker) --job.refs;
-    if (job.done == job.n && job.refs == 0) job.cv.notify_all();
-  }
-  void start() {
-    for (int w = 0; w < HOST_WORKERS; ++w)
-      workers_.emplace_back([this] {
-        for (;;) {
-          Job* job = nullptr;
-          {
-            std::unique_lock<std::mutex> g(mu_);
-            cv_.wait(g, [&] {
-              while (!jobs_.empty() && jobs_.front()->next.load() >= jobs_.front()->n)
-                jobs_.pop_front();                 // handed out completely
-              return stop_ || !jobs_.empty();
-            });
-            if (stop_) return;
-            job = jobs_.front();
-            std::lock_guard<std::mutex> gj(job->m);
-            ++job->refs;                           // (the caller waits for it)
-          }
-          work_on(*job, true);
-        }
-      });
-  }
-  std::mutex mu_;
-  std::condition_variable cv_;
-  std::deque<Job*> jobs_;
-  std::vector<std::thread> workers_;
-  bool stop_ = false;
-};
+// KMHG_HOST_POOL=0 (test build): HostPool (kmhg_hostwork.h) starts a thread per task for every
+// job, not only for the GB-scale ones (A/B)
+static bool fresh_threads() {
+  const char* pe = test_build_knob("KMHG_HOST_POOL");
+  return pe && pe[0] == '0';
+}
 
 // Device -> pageable host copy for the host-pointer entry points (R matrices, numpy arrays):
 // results above D2H_STAGE_MIN go through two pinned chunks, the DMA of chunk i + 1 overlapping
@@ -643,12 +528,8 @@ static int d2h_threads() {
 }
 
 static void host_copy_par(char* dst, const char* src, size_t n) {
-  const int T = d2h_threads();
-  const size_t stripe = ((n + T - 1) / T + 4095) & ~(size_t)4095;
-  HostPool::get().run(T, [=](int t) {
-    const size_t a = std::min(n, t * stripe), b = std::min(n, a + stripe);
-    if (a < b) std::memcpy(dst + a, src + a, b - a);
-  });
+  for_stripes(n, d2h_threads(), 4096, fresh_threads(),
+              [=](uint64_t a, uint64_t b) { std::memcpy(dst + a, src + a, b - a); });
 }
 
 struct PinStage {
@@ -671,16 +552,13 @@ static PinStage& pin_stage() {           // the device's two pinned D2H_CHUNK bu
 // the box (tools/host_thp_probe.py, profiles/r6r_thp.json, 10 M rows = 80 MB into a fresh
 // array): 7.49 ms with 4-KB pages, 2.82 ms with huge pages (numpy asks for them itself).
 // KMHG_D2H_HUGE=0 (test build) leaves the destination alone (A/B).
-constexpr size_t HUGE_SPAN = 2u << 20;
 static void hint_huge_pages(void* dst, size_t bytes) {
   static const bool on = [] {
     const char* e = test_build_knob("KMHG_D2H_HUGE");
     return !(e && e[0] == '0');
   }();
-  if (!on || bytes < 2 * HUGE_SPAN) return;
-  const uintptr_t m = ~(uintptr_t)(HUGE_SPAN - 1), d = reinterpret_cast<uintptr_t>(dst);
-  const uintptr_t a = (d + HUGE_SPAN - 1) & m, b = (d + bytes) & m;
-  if (b > a) (void)madvise(reinterpret_cast<void*>(a), b - a, MADV_HUGEPAGE);   // a hint only
+  const Span h = on ? huge_span(dst, bytes) : Span{0, 0};
+  if (h.len) (void)madvise(reinterpret_cast<void*>(h.begin), h.len, MADV_HUGEPAGE);   // a hint only
 }
 
 void d2h_host(void* dst, const void* src, size_t bytes, hipStream_t s) {
@@ -732,15 +610,6 @@ void d2h_host(void* dst, const void* src, size_t bytes, hipStream_t s) {
   }
 }
 
-// Query rows into a host matrix (kmhg_query_fill, the R matrix of seq.kmer.pos).  A dot plot's
-// rows are diagonal runs -- (i, j), (i + 1, j + 1), ... (config 5: 133 rows per run) -- so from
-// RUNS_HOST_MIN rows on, the device writes the runs (R_count, scan, R_emit: the sharded
-// query's gather format), 12 B per run cross PCIe into a pinned buffer, and host threads
-// expand them into dst: the link carries ~1/90 of the bytes and the host's memory bandwidth
-// writes the rows.  Rows that do not shrink RUNS_HOST_GAIN-fold (multi-hit windows) take
-// d2h_host.  KMHG_HOST_RUNS=0 (test build): always d2h_host (A/B).
-constexpr uint64_t RUNS_HOST_MIN = 1u << 19;           // rows (4 MB)
-constexpr uint64_t RUNS_HOST_GAIN = 4;
 struct PinRuns {
   std::mutex mu;
   int32_t* p = nullptr;
@@ -755,51 +624,22 @@ static PinRuns& pin_runs() {                            // the device's pinned r
   return bufs[dev];
 }
 
-// Host threads for the expansion: it is bound by the host's write bandwidth, which more threads
-// reach (box, 16 CPUs, config 5's 376 M rows: 4 threads 51 ms, 8 30 ms, 16 16.5 ms;
-// profiles/r6y_runs_probe*.json): every CPU this process may run on, at most 16.
-// (The host's later unmapping of the matrix grows with the threads that wrote it -- 80 MB: 2.5
-// ms written by one thread, 5.2 by 16, profiles/r6af_release_probe.json -- but giving each thread
-// 16 MB instead (5 threads at 80 MB) traded 0.85 ms of fill for 0.9 of release,
-// profiles/r6ag_release.json: every thread is used from 1 MB of output per thread on.)
-constexpr uint64_t EXPAND_MIN_BYTES = 1u << 20;
-static int expand_threads(uint64_t out_bytes) {
-  static const int n = [] {
-    cpu_set_t cs;
-    CPU_ZERO(&cs);
-    const int c = sched_getaffinity(0, sizeof(cs), &cs) == 0 ? CPU_COUNT(&cs) : 8;
-    return std::max(1, std::min(16, c));
-  }();
-  return (int)std::max<uint64_t>(1, std::min<uint64_t>(n, out_bytes / EXPAND_MIN_BYTES));
+// The runs of H rows: their count per tile, scanned in place (what k_runs_emit reads), and their
+// number, which the scan writes to the pinned `total`.  tiles: H / TILE rounded up + the scan's
+// scratch.  Waits for the stream.
+uint64_t count_runs(const int2* d_rows, uint64_t H, uint64_t* tiles, uint64_t* total,
+                    hipStream_t s) {
+  const uint64_t nt = (H + TILE - 1) / TILE;
+  LAUNCH("k_runs_count", s, launch_runs_count(d_rows, H, tiles, s));
+  LAUNCH("k_scan_tiles_u64", s, launch_scan_u64(tiles, nt, total, tiles + nt, s));
+  HIPC(hipStreamSynchronize(s));
+  return __atomic_load_n(total, __ATOMIC_ACQUIRE);
 }
 
-static void expand_runs_host(const int32_t* runs, uint64_t n, uint64_t H, int32_t* dst) {
-  const int T = expand_threads(H * 8);
-  const uint64_t stripe = (((H + T - 1) / T) + 511) & ~(uint64_t)511;
-  auto work = [=](uint64_t r0, uint64_t r1) {
-    uint64_t lo = 0, hi = n;                            // the run covering r0
-    while (hi - lo > 1) {
-      const uint64_t mid = (lo + hi) >> 1;
-      if ((uint64_t)(uint32_t)runs[3 * mid] <= r0) lo = mid; else hi = mid;
-    }
-    uint64_t r = r0;
-    for (uint64_t q = lo; r < r1; ++q) {
-      const uint64_t st = (uint32_t)runs[3 * q];
-      const uint32_t i0 = (uint32_t)runs[3 * q + 1], j0 = (uint32_t)runs[3 * q + 2];
-      const uint64_t e = std::min(r1, q + 1 < n ? (uint64_t)(uint32_t)runs[3 * q + 3] : H);
-      uint32_t* o = reinterpret_cast<uint32_t*>(dst) + 2 * r;
-      for (uint32_t d = (uint32_t)(r - st); r < e; ++r, ++d, o += 2) {
-        o[0] = i0 + d;
-        o[1] = j0 + d;
-      }
-    }
-  };
-  HostPool::get().run(T, [&](int t) {
-    const uint64_t a = std::min(H, t * stripe), b = std::min(H, a + stripe);
-    if (a < b) work(a, b);
-  }, H * 8 >= HOST_BIG_BYTES);
-}
-
+// Query rows into a host matrix (kmhg_query_fill, the R matrix of seq.kmer.pos): from
+// RUNS_HOST_MIN rows on as runs that host threads expand (kmhg_hostwork.h), unless the rows do
+// not shrink RUNS_HOST_GAIN-fold; else d2h_host.  KMHG_HOST_RUNS=0 (test build): always d2h_host
+// (A/B).
 void rows_to_host(const int2* d_rows, uint64_t H, int32_t* dst, hipStream_t s) {
   if (!H) return;
   const char* hre = test_build_knob("KMHG_HOST_RUNS");    // (read per call: tests flip it)
@@ -813,11 +653,7 @@ void rows_to_host(const int2* d_rows, uint64_t H, int32_t* dst, hipStream_t s) {
   DBuf<uint64_t> tiles(nt + scan_u64_scratch(nt), s);
   PinnedRec hrec = PinnedPool::get().take();
   GiveBack give_back{hrec, s};
-  uint64_t* total = &hrec.meta->n_kmers;
-  LAUNCH("k_runs_count", s, launch_runs_count(d_rows, H, tiles.p, s));
-  LAUNCH("k_scan_tiles_u64", s, launch_scan_u64(tiles.p, nt, total, tiles.p + nt, s));
-  HIPC(hipStreamSynchronize(s));
-  const uint64_t n = __atomic_load_n(total, __ATOMIC_ACQUIRE);
+  const uint64_t n = count_runs(d_rows, H, tiles.p, &hrec.meta->n_kmers, s);
   if (n * 12 * RUNS_HOST_GAIN > H * 8) {                // runs would not pay: the rows
     d2h_host(dst, d_rows, H * 8, s);
     return;
@@ -837,7 +673,7 @@ void rows_to_host(const int2* d_rows, uint64_t H, int32_t* dst, hipStream_t s) {
   HIPC(hipMemcpyAsync(pr.p, druns.p, 3 * n * 4, hipMemcpyDeviceToHost, s));
   HIPC(hipStreamSynchronize(s));
   hint_huge_pages(dst, H * 8);
-  expand_runs_host(pr.p, n, H, dst);
+  expand_runs_host(pr.p, n, H, dst, expand_threads(H * 8), fresh_threads());
 }
 
 // Pageable host -> device copy for the host-pointer entry points (the R string of make.kmer.hash
@@ -849,13 +685,6 @@ void h2d_host(void* dst, const void* src, size_t bytes, hipStream_t s) {
   // the previous chunk's DMA runs (round 3: 0.81-0.92 ms against 0.63 for the config-2 host
   // build), and pinning the caller's pages in place (hipHostRegister: the same 0.194 ms).
   HIPC(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
-}
-
-// The hash table is sized from the number of windows (an upper bound on distinct k-mers) for a
-// load factor <= 0.7; capacity is not a power of two (slot = mulhi(hash, cap)).
-uint64_t table_capacity(int64_t Nw) {
-  uint64_t cap = (uint64_t)((double)Nw / 0.7) + 16;
-  return (cap + 7) & ~7ull;
 }
 
 // KMHG_ROW_ORDER=khash makes new indices label kmer.pos rows in the reference's khash order.
@@ -988,11 +817,6 @@ struct DeviceGuard {
 };
 
 inline bool LCN(char c) { return (c | 0x20) == 'n'; }   // LC(c) == 'n', src/kmer_util.h:10
-
-size_t effective_len(const char* seq, size_t L) {   // a C string ends at its first NUL
-  const void* z = memchr(seq, 0, L);
-  return z ? (size_t)((const char*)z - seq) : L;
-}
 
 // A host string to the device, returning its C length (its first NUL, else L).  From
 // H2D_SCAN_MIN bytes on, a second thread issues the copy of all L bytes while this one scans
@@ -3335,63 +3159,16 @@ int kmhg_positions_fill_device(kmhg_index* idx, uint32_t opt, char* d_kmers, int
   });
 }
 
-// kmer.pos's pair rows into a host matrix (the R API's readout).  A pair row is {key label,
-// position j, position q} for every j < q of a repeated key's list -- P rows from the lists'
-// ~N positions (config 4: 686 M rows, 8.2 GB, from 40 M positions) -- so from HOST_PAIRS_MIN
-// rows on, the lists and their keys' offsets cross PCIe (pkeys, pair_off, rinfo, positions:
-// ~0.4 GB at config 4) and host threads write the rows, each from its stripe's first pair on
-// (the pair t of a key with n positions: the largest j with j (2n - j - 1) / 2 <= t, as
-// V_read_pairs).  KMHG_HOST_PAIRS=0 (test build): the rows are made on the device and copied.
-constexpr uint64_t HOST_PAIRS_MIN = 1u << 22;           // rows (48 MB)
-static void expand_pairs_host(const uint32_t* pk, const uint64_t* po, uint64_t M, const uint2* ri,
-                              const int32_t* ps, uint64_t P, int32_t* out) {
-  const int T = expand_threads(P * 12);
-  const uint64_t stripe = (P + T - 1) / T;
-  auto work = [=](uint64_t r0, uint64_t r1) {
-    uint64_t m = (uint64_t)(std::upper_bound(po, po + M, r0) - po) - 1;
-    uint64_t t = r0 - po[m], r = r0;
-    while (r < r1) {
-      const uint32_t c = pk[m];
-      const uint64_t n = ri[c].x;
-      const int32_t* lst = ps + (ri[c].y - n);
-      auto S = [n](uint64_t x) { return x * (2 * n - x - 1) / 2; };
-      uint64_t j = 0;
-      if (t) {
-        const double dn = 2.0 * (double)n - 1.0, disc = dn * dn - 8.0 * (double)t;
-        j = (uint64_t)std::max(0.0, (dn - std::sqrt(std::max(disc, 0.0))) * 0.5);
-        j = std::min<uint64_t>(j, n - 2);
-        while (j > 0 && S(j) > t) --j;
-        while (j + 1 <= n - 2 && S(j + 1) <= t) ++j;
-      }
-      uint64_t q = j + 1 + (t - S(j));
-      const int32_t lab = (int32_t)(c + 1);
-      for (; j + 1 < n && r < r1; ++j, q = j + 1) {
-        const int32_t pj = lst[j];
-        const uint64_t qe = std::min<uint64_t>(n, q + (r1 - r));
-        int32_t* o = out + 3 * r;
-        for (uint64_t x = q; x < qe; ++x, o += 3) {
-          o[0] = lab;
-          o[1] = pj;
-          o[2] = lst[x];
-        }
-        r += qe - q;
-      }
-      ++m;
-      t = 0;
-    }
-  };
-  HostPool::get().run(T, [&](int i) {
-    const uint64_t a = std::min(P, i * stripe), b = std::min(P, a + stripe);
-    if (a < b) work(a, b);
-  }, P * 12 >= HOST_BIG_BYTES);
-}
-
+// kmer.pos's pair rows into a host matrix (the R API's readout) from HOST_PAIRS_MIN rows on: the
+// lists and their keys' offsets cross PCIe and host threads write the rows (kmhg_hostwork.h).
+// KMHG_HOST_PAIRS=0 (test build): the rows are made on the device and copied.
+static_assert(sizeof(RowInfo) == sizeof(uint2), "RowInfo is copied straight from Canon::rinfo");
 static void pairs_to_host(kmhg_index* idx, int32_t* out, hipStream_t s) {
   Canon& c = idx->canon;                     // prepare_readout ran (positions_device)
   const uint64_t M = c.n_multi, U = idx->U, P = idx->P;
   std::unique_ptr<uint32_t[]> pk(new uint32_t[M]);
   std::unique_ptr<uint64_t[]> po(new uint64_t[M]);
-  std::unique_ptr<uint2[]> ri(new uint2[U]);
+  std::unique_ptr<RowInfo[]> ri(new RowInfo[U]);
   d2h_host(pk.get(), c.pkeys.p, M * 4, s);
   d2h_host(po.get(), c.pair_off.p, M * 8, s);
   d2h_host(ri.get(), c.rinfo.p, U * 8, s);
@@ -3401,7 +3178,8 @@ static void pairs_to_host(kmhg_index* idx, int32_t* out, hipStream_t s) {
   std::unique_ptr<int32_t[]> ps(new int32_t[std::max<uint64_t>(n_lists, 1)]);
   d2h_host(ps.get(), idx->positions.p, n_lists * 4, s);
   hint_huge_pages(out, P * 12);
-  expand_pairs_host(pk.get(), po.get(), M, ri.get(), ps.get(), P, out);
+  expand_pairs_host(pk.get(), po.get(), M, ri.get(), ps.get(), P, out, expand_threads(P * 12),
+                    fresh_threads());
 }
 
 int kmhg_positions_fill(kmhg_index* idx, uint32_t opt, char* kmers, int32_t* pos, int32_t* pairs,
@@ -3667,12 +3445,8 @@ int kmhg_rows_runs(const void* d_rows, int64_t n_rows, void* d_runs, int64_t cap
     DBuf<uint64_t> tiles(nt + scan_u64_scratch(nt), s);
     PinnedRec hrec = PinnedPool::get().take();
     GiveBack give_back{hrec, s};
-    uint64_t* total = &hrec.meta->n_kmers;
     const int2* rows = reinterpret_cast<const int2*>(d_rows);
-    LAUNCH("k_runs_count", s, launch_runs_count(rows, (uint64_t)n_rows, tiles.p, s));
-    LAUNCH("k_scan_tiles_u64", s, launch_scan_u64(tiles.p, nt, total, tiles.p + nt, s));
-    HIPC(hipStreamSynchronize(s));
-    const uint64_t n = __atomic_load_n(total, __ATOMIC_ACQUIRE);
+    const uint64_t n = count_runs(rows, (uint64_t)n_rows, tiles.p, &hrec.meta->n_kmers, s);
     *n_runs = (int64_t)n;
     if (d_runs && (int64_t)n <= cap_runs)
       LAUNCH("k_runs_emit", s, launch_runs_emit(rows, (uint64_t)n_rows, tiles.p,

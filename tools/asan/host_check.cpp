@@ -4,7 +4,9 @@
 // tests/test_asan_host.py (CPU only).  What runs here is exactly the source the product and the
 // checker compile: kmhg_fastx.h (the FASTA/FASTQ reader that parses untrusted input),
 // kmhg_khash.h (the khash row-order replay), kmhg_plan.h (the partitioned build's plan),
-// oracle/kmer_oracle.c and oracle/sh_oracle.c.
+// kmhg_hostwork.h (the readout's worker pool, stripes and row expansions), oracle/kmer_oracle.c
+// and oracle/sh_oracle.c.  host_check_tsan is this file under ThreadSanitizer
+// (tests/test_host_work.py).
 //
 //   host_check fastx <path> <max_records>   one line per record: R <len> <has_qual> <fnv seq>
 //                                           <fnv qual>, then E <last return code>
@@ -18,6 +20,21 @@
 //                                           seq L=<chars> k=<k> [codes=0|1] [part=<p> n_parts=<n>]
 //                                           | keys n=<keys> k=<k> | count n=<keys> k=<k> spread=<s>
 //   host_check plan @<file>                 one plan per line of the file (the same arguments)
+// kmhg_hostwork.h; the .bin files are raw little-endian arrays, outputs are the rows:
+//   host_check stripes <total> <T> <align>  for_stripes' bounds, one "a b" line per stripe
+//   host_check runs <runs.bin> <H> <T> <out.bin>           expand_runs_host on T threads
+//   host_check runs-split <runs.bin> <H> <out.bin>         expand_runs_range over [0, c) and
+//                                           [c, H) for every cut c; fails on the first output
+//                                           that differs from the first cut's
+//   host_check pairs <pk.bin> <po.bin> <ri.bin> <ps.bin> <T> <out.bin>     expand_pairs_host
+//   host_check pairs-split <pk.bin> <po.bin> <ri.bin> <ps.bin> <out.bin>   as runs-split
+//   host_check pair-start <file of "n t" lines>            pair_start's j, one per line
+//   host_check pool <callers> <jobs> <max_tasks> <fresh 0|1>   caller threads submit jobs of
+//                                           0 .. max_tasks tasks to HostPool at once; each task
+//                                           adds its index to its job's sum; "ok" if all are right
+//   host_check misc span=<address>,<bytes> | class=<bytes> | cap=<windows> | len=<hex bytes> ...
+//                                           huge_span, pool_size_class, table_capacity,
+//                                           effective_len: one line per argument
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
@@ -32,6 +49,7 @@
 #include "../../kmer_hasher_amd/csrc/kmhg_fastx.h"
 #include "../../kmer_hasher_amd/csrc/kmhg_khash.h"
 #include "../../kmer_hasher_amd/csrc/kmhg_plan.h"
+#include "../../kmer_hasher_amd/csrc/kmhg_hostwork.h"
 
 extern "C" {
 long orc_windows(const char* seq, long L, int k, uint64_t* keys, int32_t* s, int32_t* e);
@@ -231,10 +249,151 @@ static int cmd_plan(int argc, char** argv) {
   return 2;
 }
 
+// a raw file as an array of T, heap-allocated at its exact size (so ASan sees any overrun)
+template <class T>
+static std::vector<T> load(const char* path) {
+  const std::string s = slurp(path);
+  std::vector<T> v(s.size() / sizeof(T));
+  memcpy(v.data(), s.data(), v.size() * sizeof(T));
+  return v;
+}
+
+static int store(const char* path, const std::vector<int32_t>& v) {
+  FILE* f = fopen(path, "wb");
+  if (!f) { perror(path); return 2; }
+  const size_t n = fwrite(v.data(), 4, v.size(), f);
+  return (fclose(f) == 0 && n == v.size()) ? 0 : 2;
+}
+
+static int cmd_stripes(uint64_t total, int T, uint64_t align) {
+  std::mutex mu;
+  std::vector<std::pair<uint64_t, uint64_t>> got;
+  kmhg::for_stripes(total, T, align, false, [&](uint64_t a, uint64_t b) {
+    std::lock_guard<std::mutex> g(mu);
+    got.push_back({a, b});
+  });
+  std::sort(got.begin(), got.end());
+  for (auto& s : got) printf("%" PRIu64 " %" PRIu64 "\n", s.first, s.second);
+  return 0;
+}
+
+// range(r0, r1, out) over [0, c) and [c, total) for every cut c: every output must equal the first
+template <class F>
+static int every_cut(uint64_t total, size_t words, const char* out_path, F&& range) {
+  std::vector<int32_t> first, out;
+  for (uint64_t c = 0; c <= total; ++c) {
+    out.assign(words, -1);
+    if (c > 0) range((uint64_t)0, c, out.data());
+    if (c < total) range(c, total, out.data());
+    if (c == 0) first = out;
+    else if (out != first) { printf("cut %" PRIu64 " differs\n", c); return 1; }
+  }
+  printf("ok %" PRIu64 "\n", total + 1);
+  return store(out_path, first);
+}
+
+static int cmd_runs(const char* runs_path, uint64_t H, int T, const char* out_path) {
+  const std::vector<int32_t> runs = load<int32_t>(runs_path);
+  const uint64_t n = runs.size() / 3;
+  if (T > 0) {
+    std::vector<int32_t> out(2 * H, -1);
+    kmhg::expand_runs_host(runs.data(), n, H, out.data(), T);
+    return store(out_path, out);
+  }
+  return every_cut(H, 2 * H, out_path, [&](uint64_t r0, uint64_t r1, int32_t* out) {
+    kmhg::expand_runs_range(runs.data(), n, H, r0, r1, out);
+  });
+}
+
+static int cmd_pairs(char** a, int T, const char* out_path) {
+  const std::vector<uint32_t> pk = load<uint32_t>(a[0]);
+  const std::vector<uint64_t> po = load<uint64_t>(a[1]);
+  const std::vector<kmhg::RowInfo> ri = load<kmhg::RowInfo>(a[2]);
+  const std::vector<int32_t> ps = load<int32_t>(a[3]);
+  const uint64_t M = pk.size();
+  if (!M || po.size() != M) { fprintf(stderr, "bad pair inputs\n"); return 2; }
+  const uint64_t nl = ri[pk[M - 1]].x, P = po[M - 1] + nl * (nl - 1) / 2;
+  if (T > 0) {
+    std::vector<int32_t> out(3 * P, -1);
+    kmhg::expand_pairs_host(pk.data(), po.data(), M, ri.data(), ps.data(), P, out.data(), T);
+    return store(out_path, out);
+  }
+  return every_cut(P, 3 * P, out_path, [&](uint64_t r0, uint64_t r1, int32_t* out) {
+    kmhg::expand_pairs_range(pk.data(), po.data(), M, ri.data(), ps.data(), r0, r1, out);
+  });
+}
+
+static int cmd_pair_start(const char* path) {
+  std::ifstream f(path);
+  if (!f) { perror(path); return 2; }
+  for (uint64_t n, t; f >> n >> t;) printf("%" PRIu64 "\n", kmhg::pair_start(n, t));
+  return 0;
+}
+
+static int cmd_pool(int callers, int jobs, int max_tasks, bool fresh) {
+  std::atomic<int> bad{0};
+  std::vector<std::thread> th;
+  for (int c = 0; c < callers; ++c)
+    th.emplace_back([=, &bad] {
+      uint64_t x = 77 + (uint64_t)c;
+      for (int j = 0; j < jobs; ++j) {
+        // 0 and 1 tasks first, then random counts up to max_tasks
+        const int n = j < 2 ? std::min(j, max_tasks) : (int)(splitmix(x) % (uint64_t)(max_tasks + 1));
+        std::atomic<int64_t> sum{0}, ran{0};
+        kmhg::HostPool::get().run(n, [&](int i) { sum += i; ++ran; }, fresh);
+        if (ran != n || sum != (int64_t)n * (n - 1) / 2) ++bad;
+      }
+    });
+  for (auto& t : th) t.join();
+  if (bad) printf("bad %d\n", bad.load());
+  else printf("ok\n");
+  return bad ? 1 : 0;
+}
+
+static int cmd_misc(int argc, char** argv) {
+  for (int i = 2; i < argc; ++i) {
+    const std::string a = argv[i];
+    const size_t eq = a.find('=');
+    if (eq == std::string::npos) return 2;
+    const std::string name = a.substr(0, eq), v = a.substr(eq + 1);
+    if (name == "span") {
+      const size_t c = v.find(',');
+      if (c == std::string::npos) return 2;
+      const kmhg::Span s = kmhg::huge_span(
+          reinterpret_cast<const void*>((uintptr_t)strtoull(v.c_str(), nullptr, 10)),
+          (size_t)strtoull(v.c_str() + c + 1, nullptr, 10));
+      printf("%" PRIu64 " %" PRIu64 "\n", (uint64_t)s.begin, (uint64_t)s.len);
+    } else if (name == "class") {
+      printf("%" PRIu64 "\n", (uint64_t)kmhg::pool_size_class((size_t)strtoull(v.c_str(), nullptr, 10)));
+    } else if (name == "cap") {
+      printf("%" PRIu64 "\n", kmhg::table_capacity(atoll(v.c_str())));
+    } else if (name == "len") {
+      std::vector<char> b(v.size() / 2);       // exact size: a scan past L is an ASan report
+      for (size_t k = 0; k < b.size(); ++k) b[k] = (char)strtoul(v.substr(2 * k, 2).c_str(), nullptr, 16);
+      printf("%zu\n", kmhg::effective_len(b.data(), b.size()));
+    } else {
+      return 2;
+    }
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 3) { fprintf(stderr, "usage: see the file header\n"); return 2; }
   const std::string c = argv[1];
   if (c == "plan") return cmd_plan(argc, argv);
+  if (c == "misc") return cmd_misc(argc, argv);
+  if (c == "stripes" && argc == 5)
+    return cmd_stripes(strtoull(argv[2], nullptr, 10), atoi(argv[3]), strtoull(argv[4], nullptr, 10));
+  if (c == "runs" && argc == 6 && atoi(argv[4]) > 0)
+    return cmd_runs(argv[2], strtoull(argv[3], nullptr, 10), atoi(argv[4]), argv[5]);
+  if (c == "runs-split" && argc == 5)
+    return cmd_runs(argv[2], strtoull(argv[3], nullptr, 10), 0, argv[4]);
+  if (c == "pairs" && argc == 8 && atoi(argv[6]) > 0) return cmd_pairs(argv + 2, atoi(argv[6]), argv[7]);
+  if (c == "pairs-split" && argc == 7) return cmd_pairs(argv + 2, 0, argv[6]);
+  if (c == "pair-start" && argc == 3) return cmd_pair_start(argv[2]);
+  if (c == "pool" && argc == 6)
+    return cmd_pool(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]) != 0);
   if (c == "fastx" && argc == 4) return cmd_fastx(argv[2], atol(argv[3]));
   if (c == "khash" && argc == 4) return cmd_khash(atol(argv[2]), strtoull(argv[3], nullptr, 10));
   if (c == "index" && argc == 4) return cmd_index(argv[2], atoi(argv[3]));
