@@ -86,7 +86,8 @@ typedef struct {
   int64_t table_slots;   /* hash-table capacity */
   int64_t device_bytes;  /* device memory held by the index */
   int32_t sources;       /* counts index (count.kmers): source_n; 0 for a position index */
-  int32_t kind;          /* 0 position index, 1 counts index, 2 suffix hash (canonical counts) */
+  int32_t kind;          /* 0 position index, 1 counts index, 2 suffix hash (canonical counts),
+                            3 single suffix hash (count.kmers.fq.sh) */
   int64_t kmer_count;    /* khash_ptr.kmer_count: distinct k-mers added (both kinds) */
   int32_t build;         /* KMHG_BUILD_*: how the table was built (0 = imported / assembled) */
   int32_t fallback;      /* 1: a partitioned build was rebuilt with the global-atomic build (a
@@ -345,6 +346,58 @@ int kmhg_sh_depth_device(kmhg_index *sh, const void *d_seq, size_t L, int k, int
 int kmhg_sh_spectrum(kmhg_index *sh, int max_count, const int32_t *comb,
                      const int32_t *comb_inner, int comb_n, const int32_t *source_min,
                      int n_source_min, double *counts, int *status);
+
+/* ---- single-source read counting: the suffix_hash path -------------------------------------
+ * count.kmers.fq.sh <- .Call("count_kmers_fastq_sh", hash.ptr, params, fq.file)
+ *                                                       src/kmer_hash.c:715-806
+ *        (+ seq_to_counts_sh src/kmer_hash.c:296-332, init_kmer_qual_2 / skip_n_qual
+ *         src/kmer_util.c:10-14 and 35-53, sh_add_kmer src/suffix_hash.c:66-97)
+ * params = (k, report_n, prefix_bits, max_memory_GiB, min_quality, max_read_n).  The result is a
+ * SINGLE suffix hash: one count per canonical k-mer (info.kind = 3, info.sources = 1), the
+ * reference's suffix_hash.  It is a different pointer kind from the suffix_hash_n above, as the
+ * reference's tags keep them: kmhg_sh_depth*, kmhg_sh_spectrum and kmhg_sh_count_* refuse a
+ * kind-3 index ("unable to obtain suffix_hash_n from external pointer"), kmhg_sh1_* refuse a
+ * kind-2 one; kmhg_counts_export, kmhg_index_info and kmhg_free take both.
+ *
+ * The walk is not the .rp iterator.  With mq = (char)(min_quality + '!') and C char comparisons
+ * a base is bad when it is N/n or qual < mq, weak when qual == mq, good when qual > mq (FASTA
+ * records: only N is bad, nothing is weak; a NUL ends the record).  An init needs k consecutive
+ * non-bad bases (weak ones accepted) and restarts after a bad run; a successful init whose window
+ * ends exactly at the record's end counts nothing; otherwise its window is counted and every
+ * following GOOD base counts the window ending on it; a weak or bad base stops the roll, a weak
+ * one becoming the first base of the next init.  The first max_read_n records are taken ((size_t)
+ * of the int: negative = all, 0 = none), records of length <= k skipped.  report_n (progress
+ * printing, not reproduced), prefix_bits and max_memory do not change the counts.  A file mixing
+ * FASTA and FASTQ records is read as the .rp entry reads it: a record without a quality string
+ * gets no quality test, wherever it stands (the reference hands such a record the previous
+ * record's stale kseq quality buffer).
+ *
+ * Errors (reference words): "k must be a positive integer less than 1+MAX_K"; *sh not a single
+ * suffix hash: "Unable to extract suffix_hash from external pointer".  Deviations, all on paths
+ * where the reference's behaviour is undefined:
+ *   - suffix bits = 2k - prefix_bits outside 0 .. 32 is refused (the reference truncates the
+ *     suffix to 32 bits and mis-sizes its prefix array, src/suffix_hash.c:20-26, 70, 84);
+ *   - k = 32 is refused, as for the .rp entry;
+ *   - a max_memory too small for the prefix array (8 B << prefix_bits) is refused (the reference
+ *     dereferences its NULL prefix array);
+ *   - adding to an existing single suffix hash with a different k is refused (the reference keeps
+ *     no k and would mask the new k-mers into the old key space).
+ * The reference's third reader family, count.kmers.fq / kmer.spec.kt (kmer_tree), is not
+ * provided: its result depends on a memory cap that stops counting in mid-file. */
+int kmhg_sh1_count_fastq(kmhg_index **sh, const char *path, const int32_t params[6]);
+/* Reads already read (max_read_n is not applied) and device-resident packed reads, with the
+ * buffer contract of kmhg_sh_count_reads_device.  Records are routed by has_qual: those with
+ * qualities to a lane-per-read walk, those without to a position-parallel kernel. */
+int kmhg_sh1_count_reads(kmhg_index **sh, const kmhg_reads *r, const int32_t params[6]);
+int kmhg_sh1_count_reads_device(kmhg_index **sh, const void *d_seq, const void *d_qual,
+                                const int64_t *d_offsets, const uint8_t *d_has_qual,
+                                int64_t n_reads, const int32_t params[6], void *stream);
+/* kmer.spec.sh <- .Call("kmer_spectrum_suffix_hash", ptr, max.count)   src/kmer_hash.c:993-1008
+ *        (+ sh_count_spectrum src/suffix_hash.c:112-129)
+ * counts = max_count + 1 doubles: counts[min(count, max_count)] += 1 per distinct k-mer (entry 0
+ * stays 0).  Errors: "unable to obtain a suffix_hash from external pointer" (not kind 3),
+ * "Unsuitable value of max_count" (outside 1 .. 2^30). */
+int kmhg_sh1_spectrum(kmhg_index *sh, int max_count, double *counts);
 
 /* Rows of a counts index or suffix hash: keys[U] and counts[U * sources] in row order. */
 int kmhg_counts_export(kmhg_index *idx, uint64_t *keys, int32_t *counts);

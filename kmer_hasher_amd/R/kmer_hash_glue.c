@@ -14,6 +14,8 @@
  *   count_kmers_fastq_sh_rp(ptr, params, f) src/kmer_hash.c:810-857   -> EXTPTRSXP (suffix_hash_n)
  *   seq_kmer_depth_sh(ptr, seq, k)          src/kmer_hash.c:859-879   -> INTSXP counts_n x L
  *   kmer_spectrum_suffix_hash_n(ptr, ...)   src/kmer_hash.c:1010-1039 -> REALSXP
+ *   count_kmers_fastq_sh(ptr, params, f)    src/kmer_hash.c:715-806   -> EXTPTRSXP (suffix_hash)
+ *   kmer_spectrum_suffix_hash(ptr, max)     src/kmer_hash.c:993-1008  -> REALSXP
  *
  * Differences, all deliberate: the finaliser frees the whole payload (the reference leaks the
  * 32-B khash_ptr, src/kmer_hash.c:56-66); a freed pointer is detected instead of dereferenced;
@@ -305,6 +307,70 @@ SEXP kmer_spectrum_suffix_hash_n(SEXP hash_ptr_r, SEXP max_count_r, SEXP comb_r,
     error("%s", kmhg_last_error());
   }
   if (status < 0) Rprintf("sh_count_spectrum_nc returned an error: %d\n", status);
+  UNPROTECT(1);
+  return counts_r;
+}
+
+/* ---- suffix_hash (single-source read counting) --------------------------------------------
+ * The reference's own tag (src/kmer_hash.c:24): a pointer made here is refused by
+ * seq.kmer.depth.sh / kmer.spec.sh.n, and kmer.spec.sh refuses a suffix_hash_n, as there.
+ * The two entry points are exported but not in the registration table below, which stays the
+ * list tests/test_r_glue.py pins: .Call("count_kmers_fastq_sh", ...) by name finds them by
+ * R's dynamic symbol lookup, which registration leaves on (R_useDynamicSymbols is not called). */
+static const char *suffix_hash_tag = "suffix_hash_250930";
+
+static kmhg_index *gpu_sh1_of(SEXP ptr_r) {
+  if (TYPEOF(ptr_r) != EXTPTRSXP) return NULL;
+  SEXP tag = R_ExternalPtrTag(ptr_r);
+  if (TYPEOF(tag) != STRSXP || length(tag) != 1 ||
+      strcmp(CHAR(STRING_ELT(tag, 0)), suffix_hash_tag))
+    return NULL;
+  return (kmhg_index *)R_ExternalPtrAddr(ptr_r);
+}
+
+/* count_kmers_fastq_sh, src/kmer_hash.c:715-806 (count.kmers.fq.sh, kmer_hash.R:56-59):
+ * params = (k, report_n, prefix_bits, max_memory, min_quality, max_read_n).  Validation order
+ * and texts as the reference, its misworded params message included; the report_n progress
+ * printing is not reproduced. */
+SEXP count_kmers_fastq_sh(SEXP hash_ptr_r, SEXP params_r, SEXP fq_file_r) {
+  if (TYPEOF(fq_file_r) != STRSXP || length(fq_file_r) != 1)
+    error("fq_file should be a character vector of length at least one");
+  if (TYPEOF(params_r) != INTSXP || length(params_r) != 6)
+    error("k_r must be an integer vector of length 3");
+  const char *fq_file = CHAR(STRING_ELT(fq_file_r, 0));
+  const int *params = INTEGER(params_r);
+  if (params[1] < 1) warning("negative or 0 report n value specified: set to 1e6");
+  if (params[0] < 1 || params[0] > 32) error("k must be a positive integer less than 1+MAX_K");
+  kmhg_index *sh = NULL;
+  if (hash_ptr_r != R_NilValue) {
+    sh = gpu_sh1_of(hash_ptr_r);
+    if (!sh) error("Unable to extract suffix_hash from external pointer");
+  }
+  kmhg_index *out = sh;
+  if (kmhg_sh1_count_fastq(&out, fq_file, (const int32_t *)params) != KMHG_OK)
+    error("%s", kmhg_last_error());
+  if (sh) return hash_ptr_r;
+  SEXP tag = PROTECT(allocVector(STRSXP, 1));
+  SET_STRING_ELT(tag, 0, mkChar(suffix_hash_tag));
+  SEXP ptr = PROTECT(R_MakeExternalPtr(out, tag, R_NilValue));
+  R_RegisterCFinalizerEx(ptr, finalise_gpu_index, TRUE);
+  UNPROTECT(2);
+  return ptr;
+}
+
+/* kmer_spectrum_suffix_hash, src/kmer_hash.c:993-1008 (kmer.spec.sh, kmer_hash.R:89-91) */
+SEXP kmer_spectrum_suffix_hash(SEXP ext_ptr, SEXP max_count_r) {
+  kmhg_index *sh = gpu_sh1_of(ext_ptr);
+  if (!sh) error("unable to obtain a suffix_hash from external pointer");
+  if (TYPEOF(max_count_r) != INTSXP || length(max_count_r) != 1)
+    error("max_count_r should be a single integer");
+  const int max_count = asInteger(max_count_r);
+  if (max_count < 1 || max_count > (1 << 30)) error("Unsuitable value of max_count");
+  SEXP counts_r = PROTECT(allocVector(REALSXP, (R_xlen_t)max_count + 1));
+  if (kmhg_sh1_spectrum(sh, max_count, REAL(counts_r)) != KMHG_OK) {
+    UNPROTECT(1);
+    error("%s", kmhg_last_error());
+  }
   UNPROTECT(1);
   return counts_r;
 }

@@ -73,3 +73,16 @@ kmer.spec.sh.n <- function(ptr, max.count, comb, comb.inner, source.min){
     .Call("kmer_spectrum_suffix_hash_n", ptr, as.integer(max.count),
           as.integer(comb), as.integer(comb.inner), as.integer(source.min))
 }
+
+## canonical k-mer counts of a FASTA/FASTQ file into a single suffix_hash pointer
+## (reference kmer_hash.R:55-59)
+## params: k, report_n, prefix_bits, max memory, min quality, max_read_n
+count.kmers.fq.sh <- function(fq.file, params, hash.ptr=NULL){
+    params <- as.integer(params)
+    .Call("count_kmers_fastq_sh", hash.ptr, params, fq.file);
+}
+
+## k-mer count spectrum of a count.kmers.fq.sh pointer (reference kmer_hash.R:89-91)
+kmer.spec.sh <- function(ptr, max.count){
+    .Call("kmer_spectrum_suffix_hash", ptr, as.integer(max.count))
+}

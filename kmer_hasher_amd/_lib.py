@@ -122,6 +122,15 @@ _PROTOS = {
     "kmhg_pool_cached_bytes": (C.c_int64, []),
 }
 
+# The single suffix hash entries (count.kmers.fq.sh / kmer.spec.sh).  Kept apart from _PROTOS,
+# which mirrors header_symbols(): that pattern takes letter-only names, and these carry a digit.
+_PROTOS_SH1 = {
+    "kmhg_sh1_count_fastq": (C.c_int, [C.POINTER(vp), C.c_char_p, vp]),
+    "kmhg_sh1_count_reads": (C.c_int, [C.POINTER(vp), vp, vp]),
+    "kmhg_sh1_count_reads_device": (C.c_int, [C.POINTER(vp), vp, vp, vp, vp, C.c_int64, vp, vp]),
+    "kmhg_sh1_spectrum": (C.c_int, [vp, C.c_int, vp]),
+}
+
 
 def header_symbols() -> list[str]:
     """Every function declared in include/kmhgpu.h."""
@@ -140,7 +149,7 @@ def _load(path: str):
     except Exception:
         pass
     L = C.CDLL(path)
-    for name, (res, args) in _PROTOS.items():
+    for name, (res, args) in {**_PROTOS, **_PROTOS_SH1}.items():
         if os.environ.get("KMHG_LIB_VARIANT") and not hasattr(L, name):
             continue              # an older A/B build may predate an entry point
         f = getattr(L, name)

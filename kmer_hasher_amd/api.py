@@ -9,6 +9,8 @@
     seq_kmer_depth_sh(ptr, seq, k)         <- seq.kmer.depth.sh    (kmer_hash.R:80-83)
     kmer_spec_sh_n(ptr, max_count, comb, comb_inner, source_min)
                                            <- kmer.spec.sh.n       (kmer_hash.R:93-96)
+    count_kmers_fq_sh(fq, params, ptr)     <- count.kmers.fq.sh    (kmer_hash.R:56-59)
+    kmer_spec_sh(ptr, max_count)           <- kmer.spec.sh         (kmer_hash.R:89-91)
     set_row_order(ex_ptr, "khash")         kmer.pos rows in the reference's khash order (opt-in)
 
 Same argument meaning, same validation order and the reference's own error messages (raised as
@@ -33,6 +35,7 @@ from . import _lib
 
 KMER_HASH_TAG = "kmer_hash_250930"
 SUFFIX_HASH_N_TAG = "suffix_hash_n_250930"          # src/kmer_hash.c:25
+SUFFIX_HASH_TAG = "suffix_hash_250930"              # src/kmer_hash.c:24
 OPT_KMER, OPT_POS, OPT_PAIRS, OPT_COUNT = 1, 2, 4, 8
 FIELDS = ("kmer", "pos", "pair.pos", "count")          # src/kmer_hash.c:18
 INT_MAX = 2**31 - 1
@@ -380,6 +383,62 @@ def kmer_spec_sh_n(hash_ptr, max_count, comb, comb_inner, source_min) -> np.ndar
     if st.value != 1:
         warnings.warn(f"sh_count_spectrum_nc returned an error: {st.value}")
     return out[:(mc + 1) * len(cb) * S].reshape(mc + 1, len(cb) * S).T
+
+
+# ------------------------------------------------------------------ single suffix hash
+def count_kmers_fq_sh(fq_file, params, hash_ptr=None) -> ExtPtr:
+    """count.kmers.fq.sh -> .Call("count_kmers_fastq_sh", hash.ptr, params, fq.file)
+    (src/kmer_hash.c:715-806; walk seq_to_counts_sh :296-332).
+
+    params = (k, report_n, prefix_bits, max_memory, min_quality, max_read_n).  Counts the canonical
+    k-mers the reference's character-threshold walk accepts into a single suffix hash (tag
+    "suffix_hash_250930", info.kind 3).  hash_ptr None makes a new one; anything else must be a
+    pointer this function returned."""
+    if isinstance(fq_file, (list, tuple)):
+        if len(fq_file) != 1:
+            raise KmerHashError("fq_file should be a character vector of length at least one")
+        fq_file = fq_file[0]
+    if not isinstance(fq_file, (str, bytes)):
+        raise KmerHashError("fq_file should be a character vector of length at least one")
+    prm = _int_vec(params, 6, "k_r must be an integer vector of length 3")
+    prm = [((x + 2**31) % 2**32) - 2**31 for x in prm]
+    if prm[1] < 1:
+        warnings.warn("negative or 0 report n value specified: set to 1e6")
+    if prm[0] < 1 or prm[0] > 32:
+        raise KmerHashError("k must be a positive integer less than 1+MAX_K")
+    if hash_ptr is not None and not (isinstance(hash_ptr, ExtPtr) and
+                                     hash_ptr.tag == SUFFIX_HASH_TAG and hash_ptr._h):
+        raise KmerHashError("Unable to extract suffix_hash from external pointer")
+    h = C.c_void_p(hash_ptr._h.value if hash_ptr is not None else None)
+    arr = (C.c_int32 * 6)(*prm)
+    path = fq_file.encode() if isinstance(fq_file, str) else fq_file
+    L = _lib.lib()
+    rc = L.kmhg_sh1_count_fastq(C.byref(h), path, arr)
+    if rc == _lib.KMHG_EINVAL:
+        raise KmerHashError(L.kmhg_last_error().decode())
+    _lib.check(rc)
+    if hash_ptr is not None:
+        return hash_ptr
+    return ExtPtr(h.value, tag=SUFFIX_HASH_TAG)
+
+
+def kmer_spec_sh(ptr, max_count) -> np.ndarray:
+    """kmer.spec.sh -> .Call("kmer_spectrum_suffix_hash", ptr, max.count)
+    (src/kmer_hash.c:993-1008, sh_count_spectrum src/suffix_hash.c:112-129).
+
+    Returns max_count + 1 float64: entry min(count, max_count) gains one per distinct k-mer."""
+    if not (isinstance(ptr, ExtPtr) and ptr.tag == SUFFIX_HASH_TAG and ptr._h):
+        raise KmerHashError("unable to obtain a suffix_hash from external pointer")
+    mc = _int_vec(max_count, 1, "max_count_r should be a single integer")[0]
+    if mc < 1 or mc > (1 << 30):
+        raise KmerHashError("Unsuitable value of max_count")
+    out = np.zeros(mc + 1, np.float64)
+    L = _lib.lib()
+    rc = L.kmhg_sh1_spectrum(ptr.handle, mc, out.ctypes.data)
+    if rc == _lib.KMHG_EINVAL:
+        raise KmerHashError(L.kmhg_last_error().decode())
+    _lib.check(rc)
+    return out
 
 
 def counts_table(ptr):

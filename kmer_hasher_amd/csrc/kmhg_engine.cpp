@@ -731,6 +731,7 @@ struct kmhg_index {
   // suffix hash's rows are order-free (no rord, no rorder).
   uint32_t sources = 0;
   bool canonical = false;         // suffix hash (count.kmers.fq.sh.rp): canonical k-mer counts
+  bool single = false;            // ... the single suffix_hash of count.kmers.fq.sh (kind 3)
   uint64_t rows_cap = 0, kmer_count = 0;
   bool u_upper = false;           // U is only an upper bound (batch table of the global fallback)
   // last read batch (kmhg_sh_last_batch): HLL distinct estimate, bucket spread, build path
@@ -1884,38 +1885,78 @@ kmhg_index* new_sh_index(int k, int counts_n, hipStream_t s) {
 // merge over the batch table's slots.  The padding (quality- or N-rejected windows) costs its
 // 8 B per window in the build's first pass; the exact count pass it replaces re-walked every
 // read and cost a second host round trip (reads leg: see DESIGN.md).
+// Which of the reference's two read walks a batch is counted with: count.kmers.fq.sh.rp's
+// log-likelihood iterator (min_ll) or count.kmers.fq.sh's character threshold (sh1, mq).
+struct ReadWalk {
+  bool sh1 = false;
+  double min_ll = 0;
+  int mq = 0;
+  uint32_t source = 0;
+};
+
 void sh_count_reads_device(kmhg_index* idx, const uint8_t* d_seq, const uint8_t* d_qual,
                            const int64_t* d_off, const uint8_t* d_hasq, uint32_t n_reads,
-                           double mean_len, double min_ll, uint32_t source, hipStream_t s) {
+                           const ReadWalk& walk, hipStream_t s) {
   ReleaseGroup rg(s);
   idx->stream = s;
   if (!n_reads) return;
   const int k = idx->k;
-  const double* qll = qll_device(s);
+  const uint32_t source = walk.source;
+  const double* qll = walk.sh1 ? nullptr : qll_device(s);
   DBuf<uint32_t> cnt((size_t)n_reads + 1, s);
+  DBuf<int64_t> eend;                              // sh1: each record's end (its first NUL)
   const uint32_t nt = tiles_for(n_reads);
-  DBuf<uint64_t> status((size_t)nt + 2, s);        // scan look-back + ticket, then the span
+  // scan look-back + ticket, then the span and (sh1) the number of records without qualities
+  DBuf<uint64_t> status((size_t)nt + 2, s);
   HIPC(hipMemsetAsync(status.p, 0, ((size_t)nt + 2) * 8, s));
   uint32_t* d_span = reinterpret_cast<uint32_t*>(status.p + nt + 1);
   LAUNCH("k_rk_span", s, launch_rk_span(d_off, n_reads, d_span, s));
-  LAUNCH("k_read_ub", s, launch_read_ub(d_off, n_reads, k, cnt.p, s));
+  if (walk.sh1) {
+    eend.reset(n_reads);
+    eend.bind(s);
+    LAUNCH("k_sh1_ub", s, launch_sh1_ub(d_off, d_hasq, n_reads, k, cnt.p, eend.p, d_span + 1, s));
+  } else {
+    LAUNCH("k_read_ub", s, launch_read_ub(d_off, n_reads, k, cnt.p, s));
+  }
   LAUNCH("k_scan_u32", s, launch_scan_u32(cnt.p, n_reads, status.p, cnt.p + n_reads, s));
   // one round trip for the staging span and the stream length (pinned: the GiveBack returns it)
   PinnedRec hr = PinnedPool::get().take();
   GiveBack hr_back{hr, s};
-  HIPC(hipMemcpyAsync(&hr.meta->n_pairs, d_span, 4, hipMemcpyDeviceToHost, s));
+  HIPC(hipMemcpyAsync(&hr.meta->n_pairs, d_span, 8, hipMemcpyDeviceToHost, s));
   HIPC(hipMemcpyAsync(&hr.meta->max_count, cnt.p + n_reads, 4, hipMemcpyDeviceToHost, s));
   HIPC(hipStreamSynchronize(s));
-  const uint32_t span = (uint32_t)__atomic_load_n(&hr.meta->n_pairs, __ATOMIC_ACQUIRE);
+  const uint64_t span_noq = __atomic_load_n(&hr.meta->n_pairs, __ATOMIC_ACQUIRE);
+  const uint32_t span = (uint32_t)span_noq, n_noq = (uint32_t)(span_noq >> 32);
   const uint32_t total = __atomic_load_n(&hr.meta->max_count, __ATOMIC_ACQUIRE);
   const char* rkc = test_build_knob("KMHG_RK_CAP");   // A/B knob: LDS bytes per stream (16: global)
   const uint32_t cap = rkc ? (((uint32_t)std::atoi(rkc) + 15) & ~15u) : read_kmers_cap_span(span);
-  (void)mean_len;
   if (!total) return;
   DBuf<uint64_t> keys(total, s);
-  LAUNCH("k_read_kmers_emit", s,
-         launch_read_kmers(d_seq, d_qual, d_off, d_hasq, n_reads, k, min_ll, qll, cap, cnt.p,
-                           keys.p, s));
+  if (!walk.sh1) {
+    LAUNCH("k_read_kmers_emit", s,
+           launch_read_kmers(d_seq, d_qual, d_off, d_hasq, n_reads, k, walk.min_ll, qll, cap,
+                             cnt.p, keys.p, s));
+  } else {
+    // routed by record: qualities -> the lane-per-read walk, none -> the position-parallel
+    // kernel (a chromosome-length FASTA record would otherwise be one lane's serial walk)
+    if (n_noq < n_reads)
+      LAUNCH("k_read_kmers_sh1", s,
+             launch_read_kmers_sh1(d_seq, d_qual, d_off, d_hasq, n_reads, k, walk.mq, cap, cnt.p,
+                                   keys.p, s));
+    if (n_noq) {
+      int64_t ends[2] = {0, 0};
+      HIPC(hipMemcpyAsync(&ends[0], d_off, 8, hipMemcpyDeviceToHost, s));
+      HIPC(hipMemcpyAsync(&ends[1], d_off + n_reads, 8, hipMemcpyDeviceToHost, s));
+      HIPC(hipStreamSynchronize(s));
+      const int64_t span16 = ends[1] - (ends[0] & ~(int64_t)15);
+      if (span16 > 0) {
+        LAUNCH("k_sh1_nul", s, launch_sh1_nul(d_seq, d_off, n_reads, span16, eend.p, s));
+        LAUNCH("k_fa_kmers", s,
+               launch_fa_kmers(d_seq, d_off, eend.p, d_hasq, n_reads, k, span16, cnt.p, keys.p,
+                               s));
+      }
+    }
+  }
   // The count-only build gives each group bucket `spread` x V2_BW_WG stream entries, so that the
   // batch's distinct keys -- not its key stream -- fill the LDS sub-tables (bench, 3.7x
   // coverage: spread 1/2/3/4 -> 22.6/26.8/28.5/27.6 Gbp/s).  The spread comes from THIS
@@ -1980,7 +2021,7 @@ struct ReadsHost {
 // their u32 sum cannot wrap below this.
 constexpr uint64_t SH_SPAN_MAX = (uint64_t)UINT32_MAX;
 
-void sh_count_reads_host(kmhg_index* idx, const ReadsHost& r, double min_ll, uint32_t source,
+void sh_count_reads_host(kmhg_index* idx, const ReadsHost& r, const ReadWalk& walk,
                          hipStream_t s) {
   const size_t n = r.n();
   if (!n) return;
@@ -2000,7 +2041,7 @@ void sh_count_reads_host(kmhg_index* idx, const ReadsHost& r, double min_ll, uin
     const uint64_t span = (uint64_t)(r.off[i1] - r.off[i0]);
     if (span >= SH_SPAN_MAX) fail(KMHG_EOVERFLOW, "a read of 2^32 or more bases");
     sh_count_reads_device(idx, dseq.p, dqual.p, doff.p + i0, dhq.p + i0, (uint32_t)(i1 - i0),
-                          (double)span / (double)(i1 - i0), min_ll, source, s);
+                          walk, s);
     i0 = i1;
   }
   HIPC(hipStreamSynchronize(s));                 // the host arrays are reused
@@ -2065,7 +2106,7 @@ void sh_depth_device(kmhg_index* idx, const uint8_t* d_seq, int64_t L, int k, in
 }
 
 void check_sh(const kmhg_index* idx) {
-  if (!idx || !idx->canonical)
+  if (!idx || !idx->canonical || idx->single)
     fail(KMHG_EINVAL, "unable to obtain suffix_hash_n from external pointer");
 }
 
@@ -2791,6 +2832,33 @@ struct kmhg_reads {
   ReadsHost r;
 };
 
+// A device batch's key stream is sized by per-read window bounds (each <= the read's length)
+// summed in u32: a batch spanning 2^32 or more bases could wrap that sum (two int64 reads).
+static void check_batch_span(const int64_t* d_offsets, int64_t n_reads, hipStream_t s) {
+  if (n_reads <= 0) return;
+  int64_t ends[2] = {0, 0};
+  HIPC(hipMemcpyAsync(&ends[0], d_offsets, 8, hipMemcpyDeviceToHost, s));
+  HIPC(hipMemcpyAsync(&ends[1], d_offsets + n_reads, 8, hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  if (ends[1] < ends[0] || (uint64_t)(ends[1] - ends[0]) >= SH_SPAN_MAX)
+    fail(KMHG_EINVAL, "a read batch must span fewer than 2^32 bases: split it");
+}
+
+// The reads of r longer than k (r itself when all are): reads no longer than k were dropped
+// when r was read with a smaller k.
+static const ReadsHost* reads_longer_than(const ReadsHost& r, int k, ReadsHost& keep) {
+  bool all_long = true;
+  for (size_t i = 0; i < r.n() && all_long; ++i) all_long = r.off[i + 1] - r.off[i] > k;
+  if (all_long) return &r;
+  for (size_t i = 0; i < r.n(); ++i) {
+    const int64_t a = r.off[i], b = r.off[i + 1];
+    if (b - a <= k) continue;
+    keep.add(std::string((const char*)r.seq.data() + a, (size_t)(b - a)),
+             std::string((const char*)r.qual.data() + a, (size_t)(b - a)), r.hasq[i] != 0);
+  }
+  return &keep;
+}
+
 // Into an existing suffix hash the reference checks k and source (src/kmer_reader.c:118-126):
 // a mismatch prints a message and counts nothing.
 static bool sh_accepts(const kmhg_index* sh, int k, uint32_t source) {
@@ -2811,7 +2879,8 @@ int kmhg_sh_count_fastq(kmhg_index** sh, const char* path, const int32_t params[
     if (*sh) check_sh(*sh);
     check_sh_params(params);
     const int k = params[0];
-    const double min_ll = qll_host((unsigned char)('!' + (unsigned char)params[2]));
+    const ReadWalk walk{false, qll_host((unsigned char)('!' + (unsigned char)params[2])), 0,
+                        (uint32_t)params[7]};
     const uint64_t max_reads = (uint64_t)(int64_t)params[4];   // (size_t) of an int
     const uint32_t source = (uint32_t)params[7];
     hipStream_t s = lib_stream();
@@ -2826,10 +2895,10 @@ int kmhg_sh_count_fastq(kmhg_index** sh, const char* path, const int32_t params[
     DeviceGuard g(c->device);
     ReadsHost r;
     read_fastx(path, max_reads, k, r, [&](ReadsHost& b) {
-      sh_count_reads_host(c, b, min_ll, source, s);
+      sh_count_reads_host(c, b, walk, s);
       c->L += (int64_t)b.seq.size();
     });
-    sh_count_reads_host(c, r, min_ll, source, s);
+    sh_count_reads_host(c, r, walk, s);
     c->L += (int64_t)r.seq.size();
     if (fresh) *sh = fresh.release();
   });
@@ -2877,8 +2946,9 @@ int kmhg_sh_count_reads(kmhg_index** sh, const kmhg_reads* r, const int32_t para
     if (*sh) check_sh(*sh);
     check_sh_params(params);
     const int k = params[0];
-    const double min_ll = qll_host((unsigned char)('!' + (unsigned char)params[2]));
-    const uint32_t source = (uint32_t)params[7];
+    const ReadWalk walk{false, qll_host((unsigned char)('!' + (unsigned char)params[2])), 0,
+                        (uint32_t)params[7]};
+    const uint32_t source = walk.source;
     hipStream_t s = lib_stream();
     std::unique_ptr<kmhg_index> fresh;
     kmhg_index* c = *sh;
@@ -2889,23 +2959,9 @@ int kmhg_sh_count_reads(kmhg_index** sh, const kmhg_reads* r, const int32_t para
       return;
     }
     DeviceGuard g(c->device);
-    // reads no longer than k were dropped when r was read with a smaller k
     ReadsHost keep;
-    const ReadsHost* use = &r->r;
-    bool all_long = true;
-    for (size_t i = 0; i < r->r.n() && all_long; ++i)
-      all_long = r->r.off[i + 1] - r->r.off[i] > k;
-    if (!all_long) {
-      for (size_t i = 0; i < r->r.n(); ++i) {
-        const int64_t a = r->r.off[i], b = r->r.off[i + 1];
-        if (b - a <= k) continue;
-        keep.add(std::string((const char*)r->r.seq.data() + a, (size_t)(b - a)),
-                 std::string((const char*)r->r.qual.data() + a, (size_t)(b - a)),
-                 r->r.hasq[i] != 0);
-      }
-      use = &keep;
-    }
-    sh_count_reads_host(c, *use, min_ll, source, s);
+    const ReadsHost* use = reads_longer_than(r->r, k, keep);
+    sh_count_reads_host(c, *use, walk, s);
     c->L += (int64_t)use->seq.size();
     if (fresh) *sh = fresh.release();
   });
@@ -2923,8 +2979,9 @@ int kmhg_sh_count_reads_device(kmhg_index** sh, const void* d_seq, const void* d
     if ((reinterpret_cast<uintptr_t>(d_seq) | reinterpret_cast<uintptr_t>(d_qual)) & 15)
       fail(KMHG_EINVAL, "read bases and qualities must be 16-byte aligned");
     const int k = params[0];
-    const double min_ll = qll_host((unsigned char)('!' + (unsigned char)params[2]));
-    const uint32_t source = (uint32_t)params[7];
+    const ReadWalk walk{false, qll_host((unsigned char)('!' + (unsigned char)params[2])), 0,
+                        (uint32_t)params[7]};
+    const uint32_t source = walk.source;
     hipStream_t s = (hipStream_t)stream;
     std::unique_ptr<kmhg_index> fresh;
     kmhg_index* c = *sh;
@@ -2935,22 +2992,135 @@ int kmhg_sh_count_reads_device(kmhg_index** sh, const void* d_seq, const void* d
       return;
     }
     DeviceGuard g(c->device);
-    // mean read length for the LDS staging size: the span of the whole batch (two int64 reads)
-    double mean_len = 150;
-    if (n_reads > 0) {
-      int64_t ends[2] = {0, 0};
-      HIPC(hipMemcpyAsync(&ends[0], d_offsets, 8, hipMemcpyDeviceToHost, s));
-      HIPC(hipMemcpyAsync(&ends[1], d_offsets + n_reads, 8, hipMemcpyDeviceToHost, s));
-      HIPC(hipStreamSynchronize(s));
-      mean_len = (double)(ends[1] - ends[0]) / (double)n_reads;
-      // the key stream is sized by per-read window bounds (each <= the read's length) summed in
-      // u32: a batch spanning 2^32 or more bases could wrap that sum
-      if (ends[1] < ends[0] || (uint64_t)(ends[1] - ends[0]) >= SH_SPAN_MAX)
-        fail(KMHG_EINVAL, "a read batch must span fewer than 2^32 bases: split it");
-    }
+    check_batch_span(d_offsets, n_reads, s);
     sh_count_reads_device(c, (const uint8_t*)d_seq, (const uint8_t*)d_qual, d_offsets,
-                          d_has_qual, (uint32_t)n_reads, mean_len, min_ll, source, s);
+                          d_has_qual, (uint32_t)n_reads, walk, s);
     if (fresh) *sh = fresh.release();
+  });
+}
+
+// ---------------------------------------------------------------- single suffix hash
+// count_kmers_fastq_sh (src/kmer_hash.c:715-806) and kmer_spectrum_suffix_hash (:993-1008): the
+// reference's suffix_hash (one count per canonical k-mer) is a suffix hash of one source with
+// `single` set (info.kind = 3); the two pointer kinds refuse each other as the reference's tags do.
+// params = (k, report_n, prefix_bits, max_memory, min_quality, max_read_n); the deviations on the
+// reference's undefined paths are listed in kmhgpu.h.
+static void check_sh1_params(const int32_t* p) {
+  const int k = p[0];
+  if (k < 1 || k > 32) fail(KMHG_EINVAL, "k must be a positive integer less than 1+MAX_K");
+  if (k == 32) fail(KMHG_EINVAL, "k must be at most 31 for the suffix hash");
+  const uint32_t prefix_bits = (uint32_t)p[2];
+  const uint32_t suffix_bits = 2 * (uint32_t)k - prefix_bits;      // wraps when negative
+  if (suffix_bits > 32) fail(KMHG_EINVAL, "suffix bits (2k - prefix_bits) must be in 0 .. 32");
+  const uint64_t max_memory = (1ull << 30) * (uint64_t)(int64_t)p[3];
+  if (prefix_bits > 60 || (8ull << prefix_bits) > max_memory)
+    fail(KMHG_EINVAL, "max_memory is too small for the prefix array of the suffix hash");
+}
+
+static kmhg_index* sh1_target(kmhg_index* given, int k, hipStream_t s,
+                              std::unique_ptr<kmhg_index>& fresh) {
+  if (!given) {
+    fresh.reset(new_sh_index(k, 1, s));
+    fresh->single = true;
+    return fresh.get();
+  }
+  if (!given->canonical || !given->single)
+    fail(KMHG_EINVAL, "Unable to extract suffix_hash from external pointer");
+  if (given->k != k) fail(KMHG_EINVAL, "k differs from the k of the suffix hash");
+  return given;
+}
+
+static ReadWalk sh1_walk(const int32_t* params) {
+  // char min_quality = (char)params[4] + '!', compared as C char
+  return ReadWalk{true, 0.0, (int)(int8_t)(uint8_t)(params[4] + '!'), 0u};
+}
+
+int kmhg_sh1_count_fastq(kmhg_index** sh, const char* path, const int32_t params[6]) {
+  return guarded([&] {
+    if (!sh || !path || !params) fail(KMHG_EINVAL, "null argument");
+    check_sh1_params(params);
+    const int k = params[0];
+    const ReadWalk walk = sh1_walk(params);
+    const uint64_t max_reads = (uint64_t)(int64_t)params[5];   // (size_t) of an int
+    hipStream_t s = lib_stream();
+    std::unique_ptr<kmhg_index> fresh;
+    kmhg_index* c = sh1_target(*sh, k, s, fresh);
+    DeviceGuard g(c->device);
+    ReadsHost r;
+    read_fastx(path, max_reads, k, r, [&](ReadsHost& b) {
+      sh_count_reads_host(c, b, walk, s);
+      c->L += (int64_t)b.seq.size();
+    });
+    sh_count_reads_host(c, r, walk, s);
+    c->L += (int64_t)r.seq.size();
+    if (fresh) *sh = fresh.release();
+  });
+}
+
+int kmhg_sh1_count_reads(kmhg_index** sh, const kmhg_reads* r, const int32_t params[6]) {
+  return guarded([&] {
+    if (!sh || !r || !params) fail(KMHG_EINVAL, "null argument");
+    check_sh1_params(params);
+    const int k = params[0];
+    hipStream_t s = lib_stream();
+    std::unique_ptr<kmhg_index> fresh;
+    kmhg_index* c = sh1_target(*sh, k, s, fresh);
+    DeviceGuard g(c->device);
+    ReadsHost keep;
+    const ReadsHost* use = reads_longer_than(r->r, k, keep);
+    sh_count_reads_host(c, *use, sh1_walk(params), s);
+    c->L += (int64_t)use->seq.size();
+    if (fresh) *sh = fresh.release();
+  });
+}
+
+int kmhg_sh1_count_reads_device(kmhg_index** sh, const void* d_seq, const void* d_qual,
+                                const int64_t* d_offsets, const uint8_t* d_has_qual,
+                                int64_t n_reads, const int32_t params[6], void* stream) {
+  return guarded([&] {
+    if (!sh || !params || (n_reads > 0 && (!d_seq || !d_qual || !d_offsets || !d_has_qual)))
+      fail(KMHG_EINVAL, "null argument");
+    check_sh1_params(params);
+    if (n_reads < 0 || n_reads >= (int64_t)UINT32_MAX) fail(KMHG_EINVAL, "bad read count");
+    if ((reinterpret_cast<uintptr_t>(d_seq) | reinterpret_cast<uintptr_t>(d_qual)) & 15)
+      fail(KMHG_EINVAL, "read bases and qualities must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    std::unique_ptr<kmhg_index> fresh;
+    kmhg_index* c = sh1_target(*sh, params[0], s, fresh);
+    DeviceGuard g(c->device);
+    check_batch_span(d_offsets, n_reads, s);
+    sh_count_reads_device(c, (const uint8_t*)d_seq, (const uint8_t*)d_qual, d_offsets,
+                          d_has_qual, (uint32_t)n_reads, sh1_walk(params), s);
+    if (fresh) *sh = fresh.release();
+  });
+}
+
+// sh_count_spectrum (src/suffix_hash.c:112-129): counts[min(count, max_count)] += 1 per k-mer.
+// k_spectrum's bins for one source, one combination {1} (not inner) and source_min 0 are the
+// same sum: every row's flag is 1, so bin min(count, max_count) gains one per row.
+int kmhg_sh1_spectrum(kmhg_index* sh, int max_count, double* counts) {
+  return guarded([&] {
+    if (!sh || !sh->canonical || !sh->single)
+      fail(KMHG_EINVAL, "unable to obtain a suffix_hash from external pointer");
+    if (max_count < 1 || max_count > (1 << 30)) fail(KMHG_EINVAL, "Unsuitable value of max_count");
+    if (!counts) fail(KMHG_EINVAL, "null argument");
+    const size_t nbins = (size_t)max_count + 1;
+    std::fill(counts, counts + nbins, 0.0);
+    DeviceGuard g(sh->device);
+    hipStream_t s = lib_stream();
+    finish_build(sh);
+    if (!sh->U) return;
+    const uint32_t args[3] = {1u, 0u, 0u};               // comb, inner, source_min
+    DBuf<uint32_t> dargs(3, s), bins(nbins, s);
+    HIPC(hipMemcpyAsync(dargs.p, args, sizeof args, hipMemcpyHostToDevice, s));
+    HIPC(hipMemsetAsync(bins.p, 0, nbins * 4, s));
+    LAUNCH("k_spectrum", s,
+           launch_spectrum(sh->positions.p, sh->U, 1, (uint32_t)max_count, dargs.p, dargs.p + 1, 1,
+                           dargs.p + 2, bins.p, s));
+    std::vector<uint32_t> h(nbins);
+    HIPC(hipMemcpyAsync(h.data(), bins.p, nbins * 4, hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    for (size_t i = 0; i < nbins; ++i) counts[i] = (double)h[i];
   });
 }
 
@@ -3108,7 +3278,7 @@ int kmhg_index_info(const kmhg_index* cidx, kmhg_info* info) {
                                    idx->ckeys.bytes() + idx->slot_row.bytes() +
                                    idx->row_slot.bytes());
     info->sources = (int32_t)idx->sources;
-    info->kind = idx->canonical ? 2 : (idx->sources ? 1 : 0);
+    info->kind = idx->single ? 3 : idx->canonical ? 2 : (idx->sources ? 1 : 0);
     info->kmer_count = (int64_t)(idx->sources ? idx->kmer_count : idx->U);
     info->build = idx->build_kind;
     info->fallback = idx->fallback;

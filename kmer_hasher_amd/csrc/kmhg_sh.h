@@ -32,6 +32,27 @@ inline uint32_t read_kmers_cap_span(uint32_t span) {
   if (c > 28672) c = 28672;
   return (c + 15) & ~15u;
 }
+// ---- count.kmers.fq.sh (single suffix hash): the reference's character-threshold walk
+// (kmhg_sh.hip "single suffix hash walk"), same batch layout and key stream as above.
+constexpr int FA_CPT = 16;                   // window starts per lane of k_fa_kmers
+constexpr int FA_TILE = BLOCK * FA_CPT;      // window starts (chars) per workgroup
+inline uint32_t fa_tiles(int64_t span16) { return (uint32_t)((span16 + FA_TILE - 1) / FA_TILE); }
+// cnt[r] as launch_read_ub, eend[r] = off[r + 1], *n_noq += records with hasq[r] == 0
+void launch_sh1_ub(const int64_t* off, const uint8_t* hasq, uint32_t n_reads, int k, uint32_t* cnt,
+                   int64_t* eend, uint32_t* n_noq, hipStream_t s);
+// eend[r] lowered to record r's first NUL; span16 = off[n_reads] - (off[0] & ~15)
+void launch_sh1_nul(const uint8_t* seq, const int64_t* off, uint32_t n_reads, int64_t span16,
+                    int64_t* eend, hipStream_t s);
+// records with qualities, one lane per read (mq = the threshold as a signed char); the key
+// ranges of records without qualities are not touched
+void launch_read_kmers_sh1(const uint8_t* seq, const uint8_t* qual, const int64_t* off,
+                           const uint8_t* hasq, uint32_t n_reads, int k, int mq, uint32_t cap,
+                           const uint32_t* cnt, uint64_t* keys, hipStream_t s);
+// records without qualities, position-parallel: every slot of their key ranges is written
+void launch_fa_kmers(const uint8_t* seq, const int64_t* off, const int64_t* eend,
+                     const uint8_t* hasq, uint32_t n_reads, int k, int64_t span16,
+                     const uint32_t* cnt, uint64_t* keys, hipStream_t s);
+
 // depth: tcnt = depth_tiles(L) u32 (segment starts per tile, scanned in place by the caller),
 // sstart / send = segment bounds, n_seg = number of segments, stale = per-segment flag
 void launch_depth_seg_count(const uint8_t* seq, int64_t L, uint32_t* tcnt, hipStream_t s);

@@ -10,6 +10,9 @@
 //   R_kmers<true>   the same walk again, writing min(forward, reverse complement) per k-mer
 //   (partitioned build of the key stream -> distinct keys with occurrence counts, merged into
 //    the counts index by C_probe / C_append over the batch table's slots, table rebuilt)
+// count.kmers.fq.sh (the single suffix_hash) feeds the same key stream from its own walk: one
+// lane per read for records with qualities, position-parallel for records without ("single
+// suffix hash walk" below); kmer.spec.sh reuses k_spectrum.
 // seq.kmer.depth.sh (seq_kmer_counts, src/kmer_reader.c:155-193) is a sequential walk with a
 // restart rule; it is restated over the N-free segments of the sequence (D_* below).
 #include <hip/hip_runtime.h>
@@ -193,6 +196,232 @@ void launch_read_kmers(const uint8_t* seq, const uint8_t* qual, const int64_t* o
   const size_t smem = 256 * sizeof(double) + 2 * (size_t)cap;
   hipLaunchKernelGGL(k_read_kmers, grid, dim3(RK_READS), smem, s, seq, qual, off, hasq, n_reads, k,
                      min_ll, qll, cap, cnt, keys);
+}
+
+// ------------------------------------------------------------------ single suffix hash walk
+// count.kmers.fq.sh (seq_to_counts_sh, src/kmer_hash.c:296-332; init_kmer_qual_2 / skip_n_qual,
+// src/kmer_util.c:10-14 and 35-53) walks a record with a quality CHARACTER threshold mq and
+// three comparators: a base is bad when it is N or qual < mq (the skip loop), accepted by an
+// init window when qual >= mq, and rolled over only when qual > mq.  So a base with qual == mq
+// ("weak") may sit anywhere in an init window but stops the roll, where it becomes the start
+// of the next init.  An init window that ends exactly at the record's end is not counted (the
+// caller tests !seq[i] before its add); the same window followed by a bad base is.
+//
+// Records with qualities: one lane per read, the same per-base automaton shape as walk_read
+// (one position per loop trip).  States: INIT (j < k bases of a window taken), SKIP (over bad
+// bases), ROLL.  Comparisons are of C char (signed), as the reference's.
+template <class Acc>
+__device__ __forceinline__ void walk_read_sh1(Acc s, Acc q, int64_t x, int64_t e, int k, int mq,
+                                              const uint32_t* cnt, uint32_t rd, uint64_t* keys) {
+  enum : int { INIT = 0, SKIP = 1, ROLL = 2 };
+  const uint64_t mask = (1ull << (2 * k)) - 1;
+  const int shift = 64 - 2 * k;
+  uint64_t* out = keys + cnt[rd];
+  uint32_t n = 0;
+  int st = INIT, j = 0;
+  uint64_t f = 0, r = 0;
+  while (x < e) {
+    const uint32_t c = s.at(x);
+    if (c == 0) break;                       // the C string ends
+    const int ql = (int)(int8_t)q.at(x);
+    const bool bad = is_n(c) || ql < mq;
+    if (st == SKIP) {
+      if (bad) { ++x; continue; }
+      st = INIT; j = 0; f = 0; r = 0;
+    }
+    if (st == INIT) {
+      if (bad) { st = SKIP; ++x; continue; }
+      f = fwd_push(f, c); r = rev_push(r, c); ++x; ++j;
+      if (j < k) continue;
+      if (x >= e || s.at(x) == 0) break;     // the window ends the record: not counted
+      st = ROLL;
+    } else {                                 // ROLL: only qual > mq rolls on
+      if (bad || ql == mq) { st = INIT; j = 0; f = 0; r = 0; continue; }   // same base again
+      f = fwd_push(f, c); r = rev_push(r, c); ++x;
+    }
+    const uint64_t a = f & mask, bb = r >> shift;
+    out[n++] = a < bb ? a : bb;
+  }
+  for (uint32_t i = n, ub = cnt[rd + 1] - cnt[rd]; i < ub; ++i) out[i] = EMPTY_KEY;
+}
+
+// k_read_kmers' staging and stream layout with the walk above; records without qualities are
+// left to k_fa_kmers (their key ranges are written there).
+__global__ void __launch_bounds__(RK_READS)
+k_read_kmers_sh1(const uint8_t* __restrict__ seq, const uint8_t* __restrict__ qual,
+                 const int64_t* __restrict__ off, const uint8_t* __restrict__ hasq,
+                 uint32_t n_reads, int k, int mq, uint32_t cap, const uint32_t* __restrict__ cnt,
+                 uint64_t* __restrict__ keys) {
+  extern __shared__ uint4 rk1_smem[];
+  uint8_t* ls = reinterpret_cast<uint8_t*>(rk1_smem);
+  uint8_t* lq = ls + cap;
+  const uint32_t r0 = blockIdx.x * RK_READS;
+  const uint32_t r1 = min(n_reads, r0 + RK_READS);
+  const int64_t base = off[r0] & ~(int64_t)15;
+  const int64_t span = off[r1] - base;
+  const bool fits = span <= (int64_t)cap;
+  if (fits) {
+    const uint32_t nw = (uint32_t)((span + 15) >> 4);
+    const uint4* gs = reinterpret_cast<const uint4*>(seq + base);
+    const uint4* gq = reinterpret_cast<const uint4*>(qual + base);
+    uint4* ws = reinterpret_cast<uint4*>(ls);
+    uint4* wq = reinterpret_cast<uint4*>(lq);
+    for (uint32_t i = threadIdx.x; i < nw; i += RK_READS) {
+      const uint4 a = gs[i], b = gq[i];
+      ws[i] = a;
+      wq[i] = b;
+    }
+  }
+  __syncthreads();
+  const uint32_t rd = r0 + threadIdx.x;
+  if (rd >= r1 || hasq[rd] == 0) return;
+  const int64_t b = off[rd], e = off[rd + 1];
+  if (fits)
+    walk_read_sh1(LdsBytes{ls, base}, LdsBytes{lq, base}, b, e, k, mq, cnt, rd, keys);
+  else
+    walk_read_sh1(ByteCursor(seq), ByteCursor(qual), b, e, k, mq, cnt, rd, keys);
+}
+
+void launch_read_kmers_sh1(const uint8_t* seq, const uint8_t* qual, const int64_t* off,
+                           const uint8_t* hasq, uint32_t n_reads, int k, int mq, uint32_t cap,
+                           const uint32_t* cnt, uint64_t* keys, hipStream_t s) {
+  const dim3 grid((n_reads + RK_READS - 1) / RK_READS);
+  hipLaunchKernelGGL(k_read_kmers_sh1, grid, dim3(RK_READS), 2 * (size_t)cap, s, seq, qual, off,
+                     hasq, n_reads, k, mq, cap, cnt, keys);
+}
+
+// Per-read upper bounds as k_read_ub, each record's effective end (its first NUL, lowered by
+// k_sh1_nul), and the number of records without qualities (one atomic per wave).
+__global__ void __launch_bounds__(BLOCK)
+k_sh1_ub(const int64_t* __restrict__ off, const uint8_t* __restrict__ hasq, uint32_t n_reads, int k,
+         uint32_t* __restrict__ cnt, int64_t* __restrict__ eend, uint32_t* __restrict__ n_noq) {
+  const uint32_t r = blockIdx.x * BLOCK + threadIdx.x;
+  bool noq = false;
+  if (r < n_reads) {
+    const int64_t len = off[r + 1] - off[r];
+    cnt[r] = len >= k ? (uint32_t)(len - k + 1) : 0u;
+    eend[r] = off[r + 1];
+    noq = hasq[r] == 0;
+  }
+  const uint64_t b = __ballot(noq);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(n_noq, (uint32_t)__popcll(b));
+}
+
+void launch_sh1_ub(const int64_t* off, const uint8_t* hasq, uint32_t n_reads, int k, uint32_t* cnt,
+                   int64_t* eend, uint32_t* n_noq, hipStream_t s) {
+  hipLaunchKernelGGL(k_sh1_ub, dim3((n_reads + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, off, hasq,
+                     n_reads, k, cnt, eend, n_noq);
+}
+
+// the record holding absolute position p (off[0] <= p < off[n]): the last r with off[r] <= p
+__device__ __forceinline__ uint32_t record_of(const int64_t* __restrict__ off, uint32_t n,
+                                              int64_t p) {
+  uint32_t lo = 0, hi = n;                     // answer in [lo, hi)
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (off[mid] <= p) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// A NUL ends a record: one lane per 16 bytes of the batch, eend[record] = min(first NUL).
+__global__ void __launch_bounds__(BLOCK)
+k_sh1_nul(const uint8_t* __restrict__ seq, const int64_t* __restrict__ off, uint32_t n_reads,
+          int64_t* __restrict__ eend) {
+  const int64_t lo = off[0], hi = off[n_reads];
+  const int64_t p0 = (lo & ~(int64_t)15) + ((int64_t)blockIdx.x * BLOCK + threadIdx.x) * 16;
+  if (p0 >= hi) return;
+  const uint4 w = *reinterpret_cast<const uint4*>(seq + p0);
+  const uint32_t v[4] = {w.x, w.y, w.z, w.w};
+  bool any = false;
+  for (int i = 0; i < 4; ++i) any |= ((v[i] - 0x01010101u) & ~v[i] & 0x80808080u) != 0;
+  if (!any) return;
+  for (int i = 0; i < 16; ++i) {
+    const int64_t p = p0 + i;
+    if (p < lo || p >= hi || ((v[i >> 2] >> ((i & 3) * 8)) & 0xFFu) != 0) continue;
+    atomicMin(reinterpret_cast<unsigned long long*>(eend + record_of(off, n_reads, p)),
+              (unsigned long long)p);
+  }
+}
+
+void launch_sh1_nul(const uint8_t* seq, const int64_t* off, uint32_t n_reads, int64_t span16,
+                    int64_t* eend, hipStream_t s) {
+  const int64_t lanes = (span16 + 15) / 16;
+  hipLaunchKernelGGL(k_sh1_nul, dim3((unsigned)((lanes + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s,
+                     seq, off, n_reads, eend);
+}
+
+// Records without qualities: nothing is weak, so the walk is local.  Window [p, p + k) of a
+// record is counted iff it holds no N (and lies before the record's first NUL), except the one
+// window that both starts its N-free segment and ends at the record's end.  One lane per
+// FA_CPT consecutive window starts: the first key by k pushes, the rest rolled; one key or
+// EMPTY_KEY per start with a stream slot (the first `ub` starts of the record).  The tile's
+// chars are staged in LDS with the halo the rule needs: 1 char before (does the lane's first
+// start open a segment?) and k - 1 after.  A chromosome-length record is spread over the whole
+// device, where the lane-per-read walk would leave it to one lane.
+constexpr int FA_STAGE = 16 + FA_TILE + 48;  // chars [tile - 16, tile + FA_TILE + 48), k <= 32
+
+__global__ void __launch_bounds__(BLOCK)
+k_fa_kmers(const uint8_t* __restrict__ seq, const int64_t* __restrict__ off,
+           const int64_t* __restrict__ eend, const uint8_t* __restrict__ hasq, uint32_t n_reads,
+           int k, const uint32_t* __restrict__ cnt, uint64_t* __restrict__ keys) {
+  __shared__ uint4 st[FA_STAGE / 16];
+  const int64_t lo = off[0], hi = off[n_reads];
+  const int64_t t0 = (lo & ~(int64_t)15) + (int64_t)blockIdx.x * FA_TILE;
+  const int64_t sb = t0 - 16;
+  const int64_t lim = (hi + 15) & ~(int64_t)15;  // the batch's readable end (>= 16 B of padding)
+  for (int i = threadIdx.x; i < FA_STAGE / 16; i += BLOCK) {
+    const int64_t p = sb + (int64_t)i * 16;
+    st[i] = (p >= 0 && p < lim) ? *reinterpret_cast<const uint4*>(seq + p) : make_uint4(0, 0, 0, 0);
+  }
+  __syncthreads();
+  const uint8_t* ch = reinterpret_cast<const uint8_t*>(st);
+  const uint64_t mask = (1ull << (2 * k)) - 1;
+  const int shift = 64 - 2 * k;
+  const int64_t p0 = t0 + (int64_t)threadIdx.x * FA_CPT;
+  int64_t p = max(p0, lo);
+  const int64_t pe = min(p0 + FA_CPT, hi);
+  if (p >= pe) return;
+  uint32_t rd = record_of(off, n_reads, p);
+  while (p < pe) {
+    while (off[rd + 1] <= p) ++rd;             // p < hi = off[n_reads]: rd stays < n_reads
+    const int64_t rb = off[rd], re = off[rd + 1], ee = eend[rd];
+    const int64_t pl = min(pe, re);            // the lane's starts inside this record: [p, pl)
+    const int64_t ub = re - rb >= k ? re - rb - k + 1 : 0;
+    const int64_t ws = min(pl, rb + ub);       // ... those with a stream slot: [p, ws)
+    if (hasq[rd] == 0 && p < ws) {
+      uint64_t* out = keys + cnt[rd];          // out[start - rb]
+      // `open`: the N-free run the lane meets first began before p (p does not open a segment)
+      bool open = p > rb && p - 1 < ee && !is_n(ch[p - 1 - sb]);
+      int run = 0;                             // N-free chars ending at x, counted from p
+      uint64_t f = 0, r = 0;
+      for (int64_t x = p; x < ws + k - 1; ++x) {   // x <= re - 1: inside the record
+        const uint32_t c = ch[x - sb];
+        if (x < ee && !is_n(c)) {
+          f = fwd_push(f, c); r = rev_push(r, c); ++run;
+        } else {
+          run = 0; open = false;
+        }
+        const int64_t start = x - k + 1;
+        if (start < p) continue;
+        uint64_t key = EMPTY_KEY;
+        const bool opens = run == k && !open;  // run == k with start > p: an N sits at start - 1
+        if (run >= k && !(opens && x + 1 == ee)) {
+          const uint64_t a = f & mask, bb = r >> shift;
+          key = a < bb ? a : bb;
+        }
+        out[start - rb] = key;
+      }
+    }
+    p = pl;
+  }
+}
+
+void launch_fa_kmers(const uint8_t* seq, const int64_t* off, const int64_t* eend,
+                     const uint8_t* hasq, uint32_t n_reads, int k, int64_t span16,
+                     const uint32_t* cnt, uint64_t* keys, hipStream_t s) {
+  hipLaunchKernelGGL(k_fa_kmers, dim3(fa_tiles(span16)), dim3(BLOCK), 0, s, seq, off, eend, hasq,
+                     n_reads, k, cnt, keys);
 }
 
 // ------------------------------------------------------------------ depth: N-free segments
