@@ -315,7 +315,9 @@ int kmhg_reads_free(kmhg_reads *r);
 /* Count reads already read (same params as kmhg_sh_count_fastq; max_reads is not applied). */
 int kmhg_sh_count_reads(kmhg_index **sh, const kmhg_reads *r, const int32_t params[8]);
 /* Device-resident packed reads on `stream`: d_seq / d_qual 16-byte aligned with >= 16 readable
- * bytes past the last read, d_offsets[n_reads + 1] (int64), d_has_qual[n_reads]. */
+ * bytes past the last read, d_offsets[n_reads + 1] (int64, absolute: d_offsets[0] need not be
+ * 0), d_has_qual[n_reads].  Every record is walked as given, down to length 0: the <= k filter
+ * belongs to the file reader, so a record of exactly k bases the iterator accepts counts once. */
 int kmhg_sh_count_reads_device(kmhg_index **sh, const void *d_seq, const void *d_qual,
                                const int64_t *d_offsets, const uint8_t *d_has_qual,
                                int64_t n_reads, const int32_t params[8], void *stream);
@@ -387,7 +389,9 @@ int kmhg_sh_spectrum(kmhg_index *sh, int max_count, const int32_t *comb,
 int kmhg_sh1_count_fastq(kmhg_index **sh, const char *path, const int32_t params[6]);
 /* Reads already read (max_read_n is not applied) and device-resident packed reads, with the
  * buffer contract of kmhg_sh_count_reads_device.  Records are routed by has_qual: those with
- * qualities to a lane-per-read walk, those without to a position-parallel kernel. */
+ * qualities to a lane-per-read walk, those without to a position-parallel kernel.  The device
+ * entry walks every record as given: the <= k filter belongs to the reader, and this walk counts
+ * nothing in a record of length <= k anyway (its only init window ends the record). */
 int kmhg_sh1_count_reads(kmhg_index **sh, const kmhg_reads *r, const int32_t params[6]);
 int kmhg_sh1_count_reads_device(kmhg_index **sh, const void *d_seq, const void *d_qual,
                                 const int64_t *d_offsets, const uint8_t *d_has_qual,

@@ -43,7 +43,7 @@
 // KMHG_ROW_ORDER_SORT, KMHG_SLICE_POISON, KMHG_TEST_REPLICA), which choose
 // between equivalent paths and change no result; fault injection (KMHG_TEST_DISORDER); and the
 // A/B-only switches (KMHG_D2H, KMHG_D2H_HUGE, KMHG_HOST_RUNS, KMHG_HOST_PAIRS, KMHG_HOST_POOL,
-// KMHG_COUNT_BID, KMHG_RK_CAP, KMHG_POOL_DEPTH, KMHG_POOL_BESTFIT, KMHG_POOL_TRACE).
+// KMHG_COUNT_BID, KMHG_RK_CAP, KMHG_SH_SPAN, KMHG_POOL_DEPTH, KMHG_POOL_BESTFIT, KMHG_POOL_TRACE).
 namespace kmhg {
 inline const char* test_build_knob(const char* name) {
 #ifdef KMHG_TEST_BUILD
@@ -2021,11 +2021,26 @@ struct ReadsHost {
 // their u32 sum cannot wrap below this.
 constexpr uint64_t SH_SPAN_MAX = (uint64_t)UINT32_MAX;
 
+// The split point of sh_count_reads_host.  KMHG_SH_SPAN (test build) lowers it, so that the
+// sub-range calls -- offsets that do not start at 0 -- run at test sizes.
+static uint64_t sh_host_span_max() {
+  if (const char* e = test_build_knob("KMHG_SH_SPAN")) {
+    const uint64_t v = std::strtoull(e, nullptr, 10);
+    if (v > 0 && v < SH_SPAN_MAX) return v;
+  }
+  return SH_SPAN_MAX;
+}
+
 void sh_count_reads_host(kmhg_index* idx, const ReadsHost& r, const ReadWalk& walk,
                          hipStream_t s) {
   const size_t n = r.n();
   if (!n) return;
   if (n >= (size_t)UINT32_MAX) fail(KMHG_EOVERFLOW, "more than 2^32-1 reads in one batch");
+  const uint64_t span_max = sh_host_span_max();
+  // refused before anything is counted: a failing call leaves the index as it was
+  for (size_t i = 0; i < n; ++i)
+    if ((uint64_t)(r.off[i + 1] - r.off[i]) >= span_max)
+      fail(KMHG_EOVERFLOW, "a read of 2^32 or more bases");
   const size_t nb = r.seq.size();
   DBuf<uint8_t> dseq(nb + 16, s), dqual(nb + 16, s), dhq(n, s);
   DBuf<int64_t> doff(n + 1, s);
@@ -2037,9 +2052,7 @@ void sh_count_reads_host(kmhg_index* idx, const ReadsHost& r, const ReadWalk& wa
   // < SH_SPAN_MAX bases (offsets stay absolute, so a batch is a sub-range of the reads)
   for (size_t i0 = 0; i0 < n;) {
     size_t i1 = i0 + 1;
-    while (i1 < n && (uint64_t)(r.off[i1 + 1] - r.off[i0]) < SH_SPAN_MAX) ++i1;
-    const uint64_t span = (uint64_t)(r.off[i1] - r.off[i0]);
-    if (span >= SH_SPAN_MAX) fail(KMHG_EOVERFLOW, "a read of 2^32 or more bases");
+    while (i1 < n && (uint64_t)(r.off[i1 + 1] - r.off[i0]) < span_max) ++i1;
     sh_count_reads_device(idx, dseq.p, dqual.p, doff.p + i0, dhq.p + i0, (uint32_t)(i1 - i0),
                           walk, s);
     i0 = i1;

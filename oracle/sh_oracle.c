@@ -107,7 +107,9 @@ long orc_read_kmers(const unsigned char *seq, const unsigned char *qual, long le
   static double qll[256];
   static int ready = 0;
   if (!ready) { orc_qll(qll); ready = 1; }
-  if (k < 1 || k > 31 || len <= k) return 0;
+  /* every string is walked as given: a read of exactly k bases yields its one window, as the
+   * reference's iterator does (the <= k filter is the reader's, src/kmer_reader.c:59) */
+  if (k < 1 || k > 31 || len < k) return 0;
   orc_it it = {seq, qual, len, 0, k, 0, 0, 0, 0, 0, qll};
   it.min_ll = qll[(unsigned char)('!' + (unsigned char)min_q_param)];
   const uint64_t mask = ((uint64_t)1 << (2 * k)) - 1;

@@ -31,7 +31,8 @@ def test_product_library_reads_no_test_only_knob():
     test_lib = os.path.join(os.path.dirname(_lib.LIB_PATH), "libkmhgpu_test.so")
     prod = open(os.path.join(os.path.dirname(_lib.LIB_PATH), "libkmhgpu.so"), "rb").read()
     test = open(test_lib, "rb").read()
-    for knob in (b"KMHG_TEST_DISORDER", b"KMHG_COUNT_BID", b"KMHG_RK_CAP", b"KMHG_D2H\0"):
+    for knob in (b"KMHG_TEST_DISORDER", b"KMHG_COUNT_BID", b"KMHG_RK_CAP", b"KMHG_SH_SPAN",
+                 b"KMHG_D2H\0"):
         assert knob not in prod, knob
         assert knob in test, knob
     out = subprocess.run(["nm", "-D", "--defined-only", test_lib], capture_output=True,
