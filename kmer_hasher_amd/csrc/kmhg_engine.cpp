@@ -28,6 +28,7 @@
 #include "kmhg_kernels.h"
 #include "kmhg_plan.h"
 #include "kmhg_hostwork.h"
+#include "kmhg_reads.h"
 #include "kmhg_parts_read.h"
 #include "kmhg_fastx.h"
 #include "kmhg_khash.h"
@@ -43,7 +44,8 @@
 // KMHG_ROW_ORDER_SORT, KMHG_SLICE_POISON, KMHG_TEST_REPLICA), which choose
 // between equivalent paths and change no result; fault injection (KMHG_TEST_DISORDER); and the
 // A/B-only switches (KMHG_D2H, KMHG_D2H_HUGE, KMHG_HOST_RUNS, KMHG_HOST_PAIRS, KMHG_HOST_POOL,
-// KMHG_COUNT_BID, KMHG_RK_CAP, KMHG_SH_SPAN, KMHG_POOL_DEPTH, KMHG_POOL_BESTFIT, KMHG_POOL_TRACE).
+// KMHG_COUNT_BID, KMHG_RK_CAP, KMHG_SH_SPAN (the span_max given to read_batches, kmhg_reads.h),
+// KMHG_POOL_DEPTH, KMHG_POOL_BESTFIT, KMHG_POOL_TRACE).
 namespace kmhg {
 inline const char* test_build_knob(const char* name) {
 #ifdef KMHG_TEST_BUILD
@@ -1813,10 +1815,11 @@ const uint32_t* row_order_of(const kmhg_index* idx) {
 // ---------------------------------------------------------------------------- read counting
 // count.kmers.fq.sh.rp / seq.kmer.depth.sh / kmer.spec.sh.n (kmhg_sh.hip).  The suffix_hash_n
 // of the reference is a counts index of canonical k-mers (canonical = true, sources = counts_n).
+// The host side -- a call's parameters (ReadCall), the packed host reads and their reader, the
+// split into device batches, the quality table's formula -- is kmhg_reads.h (no HIP); here are
+// the device batches, the uploads and the launch sequences.
 
-// q_to_ll (src/Q_to_log_likelihood.h): -708 below '"', else log(1 - 10^(-(q-33)/10)) printed
-// to 15 significant digits -- exactly the doubles the reference's table holds (checked against
-// it by tests/golden/make_sh_golden.py), uploaded once per device.
+// q_to_ll's table (qll_host, kmhg_reads.h), uploaded once per device.
 const double* qll_device(hipStream_t s) {
   static std::mutex mu;
   static std::map<int, double*> tables;
@@ -1826,24 +1829,12 @@ const double* qll_device(hipStream_t s) {
   auto it = tables.find(dev);
   if (it != tables.end()) return it->second;
   double h[256];
-  for (int q = 0; q < 256; ++q) {
-    if (q < 34) { h[q] = -708.0; continue; }
-    char buf[64];
-    snprintf(buf, sizeof buf, "%.15g", std::log(1.0 - std::pow(10.0, -(double)(q - 33) / 10.0)));
-    h[q] = std::strtod(buf, nullptr);
-  }
+  for (int q = 0; q < 256; ++q) h[q] = qll_host(q);
   double* d = static_cast<double*>(DevicePool::get().alloc(sizeof h));
   HIPC(hipMemcpyAsync(d, h, sizeof h, hipMemcpyHostToDevice, s));
   HIPC(hipStreamSynchronize(s));
   tables[dev] = d;
   return d;
-}
-
-double qll_host(int q) {   // the same table on the host (the iterator's threshold)
-  if (q < 34) return -708.0;
-  char buf[64];
-  snprintf(buf, sizeof buf, "%.15g", std::log(1.0 - std::pow(10.0, -(double)(q - 33) / 10.0)));
-  return std::strtod(buf, nullptr);
 }
 
 // The count-only partitioned build of a key stream at `spread` (0: from its HLL estimate),
@@ -1885,15 +1876,6 @@ kmhg_index* new_sh_index(int k, int counts_n, hipStream_t s) {
 // merge over the batch table's slots.  The padding (quality- or N-rejected windows) costs its
 // 8 B per window in the build's first pass; the exact count pass it replaces re-walked every
 // read and cost a second host round trip (reads leg: see DESIGN.md).
-// Which of the reference's two read walks a batch is counted with: count.kmers.fq.sh.rp's
-// log-likelihood iterator (min_ll) or count.kmers.fq.sh's character threshold (sh1, mq).
-struct ReadWalk {
-  bool sh1 = false;
-  double min_ll = 0;
-  int mq = 0;
-  uint32_t source = 0;
-};
-
 void sh_count_reads_device(kmhg_index* idx, const uint8_t* d_seq, const uint8_t* d_qual,
                            const int64_t* d_off, const uint8_t* d_hasq, uint32_t n_reads,
                            const ReadWalk& walk, hipStream_t s) {
@@ -2001,26 +1983,6 @@ void sh_count_reads_device(kmhg_index* idx, const uint8_t* d_seq, const uint8_t*
   merge_batch(idx, B.get(), source, 0, s);
 }
 
-// Host reads packed for the GPU: bases and qualities concatenated, read r = [off[r], off[r+1]).
-struct ReadsHost {
-  std::vector<uint8_t> seq, qual, hasq;
-  std::vector<int64_t> off{0};
-  int64_t records = 0;                           // records consumed, short ones included
-  void clear() { seq.clear(); qual.clear(); hasq.clear(); off.assign(1, 0); }
-  void add(const std::string& sq, const std::string& ql, bool hq) {
-    seq.insert(seq.end(), sq.begin(), sq.end());
-    if (hq) qual.insert(qual.end(), ql.begin(), ql.end());
-    else qual.resize(seq.size(), 0);
-    hasq.push_back(hq ? 1 : 0);
-    off.push_back((int64_t)seq.size());
-  }
-  size_t n() const { return hasq.size(); }
-};
-
-// Largest base span of one device batch: every per-read window bound is <= its read length, so
-// their u32 sum cannot wrap below this.
-constexpr uint64_t SH_SPAN_MAX = (uint64_t)UINT32_MAX;
-
 // The split point of sh_count_reads_host.  KMHG_SH_SPAN (test build) lowers it, so that the
 // sub-range calls -- offsets that do not start at 0 -- run at test sizes.
 static uint64_t sh_host_span_max() {
@@ -2031,16 +1993,15 @@ static uint64_t sh_host_span_max() {
   return SH_SPAN_MAX;
 }
 
+// Packed host reads uploaded once and counted in read_batches' device batches (the device pass
+// sizes its key stream by per-read window bounds summed in u32); idx->L gains their bases.
 void sh_count_reads_host(kmhg_index* idx, const ReadsHost& r, const ReadWalk& walk,
                          hipStream_t s) {
   const size_t n = r.n();
+  std::vector<std::pair<size_t, size_t>> batches;
+  const Refusal bad = read_batches(r.off.data(), n, sh_host_span_max(), batches);
+  if (bad.err) fail(bad.err, bad.msg);
   if (!n) return;
-  if (n >= (size_t)UINT32_MAX) fail(KMHG_EOVERFLOW, "more than 2^32-1 reads in one batch");
-  const uint64_t span_max = sh_host_span_max();
-  // refused before anything is counted: a failing call leaves the index as it was
-  for (size_t i = 0; i < n; ++i)
-    if ((uint64_t)(r.off[i + 1] - r.off[i]) >= span_max)
-      fail(KMHG_EOVERFLOW, "a read of 2^32 or more bases");
   const size_t nb = r.seq.size();
   DBuf<uint8_t> dseq(nb + 16, s), dqual(nb + 16, s), dhq(n, s);
   DBuf<int64_t> doff(n + 1, s);
@@ -2048,41 +2009,11 @@ void sh_count_reads_host(kmhg_index* idx, const ReadsHost& r, const ReadWalk& wa
   HIPC(hipMemcpyAsync(dqual.p, r.qual.data(), nb, hipMemcpyHostToDevice, s));
   HIPC(hipMemcpyAsync(dhq.p, r.hasq.data(), n, hipMemcpyHostToDevice, s));
   HIPC(hipMemcpyAsync(doff.p, r.off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-  // the device pass sizes its key stream by per-read window bounds summed in u32: batches of
-  // < SH_SPAN_MAX bases (offsets stay absolute, so a batch is a sub-range of the reads)
-  for (size_t i0 = 0; i0 < n;) {
-    size_t i1 = i0 + 1;
-    while (i1 < n && (uint64_t)(r.off[i1 + 1] - r.off[i0]) < span_max) ++i1;
-    sh_count_reads_device(idx, dseq.p, dqual.p, doff.p + i0, dhq.p + i0, (uint32_t)(i1 - i0),
-                          walk, s);
-    i0 = i1;
-  }
+  for (const auto& b : batches)
+    sh_count_reads_device(idx, dseq.p, dqual.p, doff.p + b.first, dhq.p + b.first,
+                          (uint32_t)(b.second - b.first), walk, s);
   HIPC(hipStreamSynchronize(s));                 // the host arrays are reused
-}
-
-// kmer_reader_read's loop (src/kmer_reader.c:51-73): records up to max_reads, those longer
-// than k kept, qualities used when the record has them.  Batches of SH_BATCH bases.
-constexpr size_t SH_BATCH = (size_t)256 << 20;
-
-int64_t read_fastx(const char* path, uint64_t max_reads, int k, ReadsHost& r,
-                   const std::function<void(ReadsHost&)>& flush) {
-  FastxReader rd(path);
-  if (!rd.ok()) {   // gzopen failed: the reference's reader then reads nothing
-    fprintf(stderr, "kmhg: unable to open %s: nothing counted\n", path);
-    return 0;
-  }
-  std::string sq, ql;
-  bool hq = false;
-  uint64_t read_n = 0;
-  int l;
-  while ((l = rd.read(sq, ql, hq)) >= 0 && read_n < max_reads) {
-    ++read_n;
-    ++r.records;
-    if (l <= k) continue;
-    r.add(sq, ql, hq);
-    if (r.seq.size() >= SH_BATCH && flush) { flush(r); r.clear(); }
-  }
-  return (int64_t)read_n;
+  idx->L += (int64_t)nb;
 }
 
 void sh_depth_device(kmhg_index* idx, const uint8_t* d_seq, int64_t L, int k, int32_t* d_out,
@@ -2824,96 +2755,108 @@ int kmhg_count_device(kmhg_index** idx, const void* d_seq, size_t L, int k, int 
 }
 
 // ---------------------------------------------------------------- suffix hash (read counting)
-// count_kmers_fastq_sh_rp (src/kmer_hash.c:810-857): argument checks in the reference's order
-// and with its texts; the remaining deviations are undefined-behaviour paths of the reference.
-static void check_sh_params(const int32_t* p) {
-  const int k = p[0];
-  const uint32_t source_n = (uint32_t)p[6], source_i = (uint32_t)p[7];
-  if (k < 1 || k > 32) fail(KMHG_EINVAL, "k must be a positive integer less than 1+MAX_K");
-  if (source_n > 4 || source_n < 1) fail(KMHG_EINVAL, "Source_n must be in the range 1 - 4");
-  if (source_i >= source_n) fail(KMHG_EINVAL, "source_i must be less than source_n");
-  // k = 32: the reference's (1 << 2k) - 1 masks shift by 64 (undefined); prefix_bits > 2k with
-  // k < 16 makes its suffix/prefix split underflow (src/kmer_reader.c:84-92)
-  if (k == 32) fail(KMHG_EINVAL, "k must be at most 31 for the suffix hash");
-  uint32_t pb = (uint32_t)p[1];
-  if (pb > 36) pb = 36;
-  if (2 * (uint32_t)k < 32 && pb > 2 * (uint32_t)k)
-    fail(KMHG_EINVAL, "prefix_bits must not exceed 2k");
-}
-
+// count_kmers_fastq_sh_rp (src/kmer_hash.c:810-857) and count_kmers_fastq_sh (:715-806), whose
+// suffix_hash (one count per canonical k-mer) is a suffix hash of one source with `single` set
+// (info.kind = 3); the two pointer kinds refuse each other as the reference's tags do.  A call's
+// parameter vector is decoded by read_call_rp / read_call_sh1 (kmhg_reads.h: a ReadCall); one
+// body per input kind then serves both.
 struct kmhg_reads {
   ReadsHost r;
 };
 
-// A device batch's key stream is sized by per-read window bounds (each <= the read's length)
-// summed in u32: a batch spanning 2^32 or more bases could wrap that sum (two int64 reads).
-static void check_batch_span(const int64_t* d_offsets, int64_t n_reads, hipStream_t s) {
-  if (n_reads <= 0) return;
-  int64_t ends[2] = {0, 0};
-  HIPC(hipMemcpyAsync(&ends[0], d_offsets, 8, hipMemcpyDeviceToHost, s));
-  HIPC(hipMemcpyAsync(&ends[1], d_offsets + n_reads, 8, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  if (ends[1] < ends[0] || (uint64_t)(ends[1] - ends[0]) >= SH_SPAN_MAX)
-    fail(KMHG_EINVAL, "a read batch must span fewer than 2^32 bases: split it");
+// A call's first refusals, in each entry's order: .rp looks at the kind of a given pointer before
+// its parameters, the single suffix hash after them (ReadTarget).
+static void check_read_call(const kmhg_index* given, const ReadCall& call) {
+  if (given && !call.single) check_sh(given);
+  if (call.err) fail(call.err, call.msg);
 }
 
-// The reads of r longer than k (r itself when all are): reads no longer than k were dropped
-// when r was read with a smaller k.
-static const ReadsHost* reads_longer_than(const ReadsHost& r, int k, ReadsHost& keep) {
-  bool all_long = true;
-  for (size_t i = 0; i < r.n() && all_long; ++i) all_long = r.off[i + 1] - r.off[i] > k;
-  if (all_long) return &r;
-  for (size_t i = 0; i < r.n(); ++i) {
-    const int64_t a = r.off[i], b = r.off[i + 1];
-    if (b - a <= k) continue;
-    keep.add(std::string((const char*)r.seq.data() + a, (size_t)(b - a)),
-             std::string((const char*)r.qual.data() + a, (size_t)(b - a)), r.hasq[i] != 0);
+// The suffix hash a call counts into: the given one, or a fresh one that *sh receives only once
+// the count has succeeded (publish).  c == nullptr: count nothing -- into an existing suffix
+// hash the reference's .rp checks k and source (src/kmer_reader.c:118-126), and a mismatch
+// prints a message and counts nothing.  A single suffix hash refuses instead.
+namespace {
+struct ReadTarget {
+  kmhg_index* c = nullptr;
+  std::unique_ptr<kmhg_index> fresh;
+  ReadTarget(kmhg_index* given, const ReadCall& call, hipStream_t s) {
+    if (!given) {
+      fresh.reset(new_sh_index(call.k, (int)call.sources, s));
+      fresh->single = call.single;
+      c = fresh.get();
+    } else if (call.single) {
+      if (!given->canonical || !given->single)
+        fail(KMHG_EINVAL, "Unable to extract suffix_hash from external pointer");
+      if (given->k != call.k) fail(KMHG_EINVAL, "k differs from the k of the suffix hash");
+      c = given;
+    } else if ((int)given->k != call.k) {
+      fprintf(stderr, "Incompatible arguments: k and total bit numbers do not add up\n");
+    } else if (call.walk.source >= given->sources) {
+      fprintf(stderr, "Value of source is too large\n");
+    } else {
+      c = given;
+    }
   }
-  return &keep;
+  void publish(kmhg_index** sh) { if (fresh) *sh = fresh.release(); }
+};
+}  // namespace
+
+static void count_fastq(kmhg_index** sh, const char* path, const ReadCall& call) {
+  check_read_call(*sh, call);
+  hipStream_t s = lib_stream();
+  ReadTarget t(*sh, call, s);
+  if (!t.c) return;
+  DeviceGuard g(t.c->device);
+  ReadsHost r;
+  const auto count = [&](ReadsHost& b) { sh_count_reads_host(t.c, b, call.walk, s); };
+  read_fastx(path, call.max_reads, call.k, r, count);
+  count(r);
+  t.publish(sh);
 }
 
-// Into an existing suffix hash the reference checks k and source (src/kmer_reader.c:118-126):
-// a mismatch prints a message and counts nothing.
-static bool sh_accepts(const kmhg_index* sh, int k, uint32_t source) {
-  if ((int)sh->k != k) {
-    fprintf(stderr, "Incompatible arguments: k and total bit numbers do not add up\n");
-    return false;
+static void count_reads(kmhg_index** sh, const kmhg_reads* r, const ReadCall& call) {
+  check_read_call(*sh, call);
+  hipStream_t s = lib_stream();
+  ReadTarget t(*sh, call, s);
+  if (!t.c) return;
+  DeviceGuard g(t.c->device);
+  ReadsHost keep;
+  sh_count_reads_host(t.c, *reads_longer_than(r->r, call.k, keep), call.walk, s);
+  t.publish(sh);
+}
+
+// Device-resident packed reads.  A device batch's key stream is sized by per-read window bounds
+// (each <= the read's length) summed in u32: a batch spanning 2^32 or more bases could wrap that
+// sum (batch_span_ok, from two int64 reads).
+static void count_reads_device(kmhg_index** sh, const void* d_seq, const void* d_qual,
+                               const int64_t* d_offsets, const uint8_t* d_has_qual,
+                               int64_t n_reads, const ReadCall& call, hipStream_t s) {
+  if (n_reads > 0 && (!d_seq || !d_qual || !d_offsets || !d_has_qual))
+    fail(KMHG_EINVAL, "null argument");
+  check_read_call(*sh, call);
+  if (n_reads < 0 || n_reads >= (int64_t)UINT32_MAX) fail(KMHG_EINVAL, "bad read count");
+  if ((reinterpret_cast<uintptr_t>(d_seq) | reinterpret_cast<uintptr_t>(d_qual)) & 15)
+    fail(KMHG_EINVAL, "read bases and qualities must be 16-byte aligned");
+  ReadTarget t(*sh, call, s);
+  if (!t.c) return;
+  DeviceGuard g(t.c->device);
+  if (n_reads > 0) {
+    int64_t ends[2] = {0, 0};
+    HIPC(hipMemcpyAsync(&ends[0], d_offsets, 8, hipMemcpyDeviceToHost, s));
+    HIPC(hipMemcpyAsync(&ends[1], d_offsets + n_reads, 8, hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    if (!batch_span_ok(ends[0], ends[1]))
+      fail(KMHG_EINVAL, "a read batch must span fewer than 2^32 bases: split it");
   }
-  if (source >= sh->sources) {
-    fprintf(stderr, "Value of source is too large\n");
-    return false;
-  }
-  return true;
+  sh_count_reads_device(t.c, (const uint8_t*)d_seq, (const uint8_t*)d_qual, d_offsets,
+                        d_has_qual, (uint32_t)n_reads, call.walk, s);
+  t.publish(sh);
 }
 
 int kmhg_sh_count_fastq(kmhg_index** sh, const char* path, const int32_t params[8]) {
   return guarded([&] {
     if (!sh || !path || !params) fail(KMHG_EINVAL, "null argument");
-    if (*sh) check_sh(*sh);
-    check_sh_params(params);
-    const int k = params[0];
-    const ReadWalk walk{false, qll_host((unsigned char)('!' + (unsigned char)params[2])), 0,
-                        (uint32_t)params[7]};
-    const uint64_t max_reads = (uint64_t)(int64_t)params[4];   // (size_t) of an int
-    const uint32_t source = (uint32_t)params[7];
-    hipStream_t s = lib_stream();
-    std::unique_ptr<kmhg_index> fresh;
-    kmhg_index* c = *sh;
-    if (!c) {
-      fresh.reset(new_sh_index(k, params[6], s));
-      c = fresh.get();
-    } else if (!sh_accepts(c, k, source)) {
-      return;
-    }
-    DeviceGuard g(c->device);
-    ReadsHost r;
-    read_fastx(path, max_reads, k, r, [&](ReadsHost& b) {
-      sh_count_reads_host(c, b, walk, s);
-      c->L += (int64_t)b.seq.size();
-    });
-    sh_count_reads_host(c, r, walk, s);
-    c->L += (int64_t)r.seq.size();
-    if (fresh) *sh = fresh.release();
+    count_fastq(sh, path, read_call_rp(params));
   });
 }
 
@@ -2956,27 +2899,7 @@ int kmhg_reads_free(kmhg_reads* r) {
 int kmhg_sh_count_reads(kmhg_index** sh, const kmhg_reads* r, const int32_t params[8]) {
   return guarded([&] {
     if (!sh || !r || !params) fail(KMHG_EINVAL, "null argument");
-    if (*sh) check_sh(*sh);
-    check_sh_params(params);
-    const int k = params[0];
-    const ReadWalk walk{false, qll_host((unsigned char)('!' + (unsigned char)params[2])), 0,
-                        (uint32_t)params[7]};
-    const uint32_t source = walk.source;
-    hipStream_t s = lib_stream();
-    std::unique_ptr<kmhg_index> fresh;
-    kmhg_index* c = *sh;
-    if (!c) {
-      fresh.reset(new_sh_index(k, params[6], s));
-      c = fresh.get();
-    } else if (!sh_accepts(c, k, source)) {
-      return;
-    }
-    DeviceGuard g(c->device);
-    ReadsHost keep;
-    const ReadsHost* use = reads_longer_than(r->r, k, keep);
-    sh_count_reads_host(c, *use, walk, s);
-    c->L += (int64_t)use->seq.size();
-    if (fresh) *sh = fresh.release();
+    count_reads(sh, r, read_call_rp(params));
   });
 }
 
@@ -2984,106 +2907,25 @@ int kmhg_sh_count_reads_device(kmhg_index** sh, const void* d_seq, const void* d
                                const int64_t* d_offsets, const uint8_t* d_has_qual,
                                int64_t n_reads, const int32_t params[8], void* stream) {
   return guarded([&] {
-    if (!sh || !params || (n_reads > 0 && (!d_seq || !d_qual || !d_offsets || !d_has_qual)))
-      fail(KMHG_EINVAL, "null argument");
-    if (*sh) check_sh(*sh);
-    check_sh_params(params);
-    if (n_reads < 0 || n_reads >= (int64_t)UINT32_MAX) fail(KMHG_EINVAL, "bad read count");
-    if ((reinterpret_cast<uintptr_t>(d_seq) | reinterpret_cast<uintptr_t>(d_qual)) & 15)
-      fail(KMHG_EINVAL, "read bases and qualities must be 16-byte aligned");
-    const int k = params[0];
-    const ReadWalk walk{false, qll_host((unsigned char)('!' + (unsigned char)params[2])), 0,
-                        (uint32_t)params[7]};
-    const uint32_t source = walk.source;
-    hipStream_t s = (hipStream_t)stream;
-    std::unique_ptr<kmhg_index> fresh;
-    kmhg_index* c = *sh;
-    if (!c) {
-      fresh.reset(new_sh_index(k, params[6], s));
-      c = fresh.get();
-    } else if (!sh_accepts(c, k, source)) {
-      return;
-    }
-    DeviceGuard g(c->device);
-    check_batch_span(d_offsets, n_reads, s);
-    sh_count_reads_device(c, (const uint8_t*)d_seq, (const uint8_t*)d_qual, d_offsets,
-                          d_has_qual, (uint32_t)n_reads, walk, s);
-    if (fresh) *sh = fresh.release();
+    if (!sh || !params) fail(KMHG_EINVAL, "null argument");
+    count_reads_device(sh, d_seq, d_qual, d_offsets, d_has_qual, n_reads, read_call_rp(params),
+                       (hipStream_t)stream);
   });
 }
 
-// ---------------------------------------------------------------- single suffix hash
-// count_kmers_fastq_sh (src/kmer_hash.c:715-806) and kmer_spectrum_suffix_hash (:993-1008): the
-// reference's suffix_hash (one count per canonical k-mer) is a suffix hash of one source with
-// `single` set (info.kind = 3); the two pointer kinds refuse each other as the reference's tags do.
-// params = (k, report_n, prefix_bits, max_memory, min_quality, max_read_n); the deviations on the
-// reference's undefined paths are listed in kmhgpu.h.
-static void check_sh1_params(const int32_t* p) {
-  const int k = p[0];
-  if (k < 1 || k > 32) fail(KMHG_EINVAL, "k must be a positive integer less than 1+MAX_K");
-  if (k == 32) fail(KMHG_EINVAL, "k must be at most 31 for the suffix hash");
-  const uint32_t prefix_bits = (uint32_t)p[2];
-  const uint32_t suffix_bits = 2 * (uint32_t)k - prefix_bits;      // wraps when negative
-  if (suffix_bits > 32) fail(KMHG_EINVAL, "suffix bits (2k - prefix_bits) must be in 0 .. 32");
-  const uint64_t max_memory = (1ull << 30) * (uint64_t)(int64_t)p[3];
-  if (prefix_bits > 60 || (8ull << prefix_bits) > max_memory)
-    fail(KMHG_EINVAL, "max_memory is too small for the prefix array of the suffix hash");
-}
-
-static kmhg_index* sh1_target(kmhg_index* given, int k, hipStream_t s,
-                              std::unique_ptr<kmhg_index>& fresh) {
-  if (!given) {
-    fresh.reset(new_sh_index(k, 1, s));
-    fresh->single = true;
-    return fresh.get();
-  }
-  if (!given->canonical || !given->single)
-    fail(KMHG_EINVAL, "Unable to extract suffix_hash from external pointer");
-  if (given->k != k) fail(KMHG_EINVAL, "k differs from the k of the suffix hash");
-  return given;
-}
-
-static ReadWalk sh1_walk(const int32_t* params) {
-  // char min_quality = (char)params[4] + '!', compared as C char
-  return ReadWalk{true, 0.0, (int)(int8_t)(uint8_t)(params[4] + '!'), 0u};
-}
-
+// The single suffix hash: params = (k, report_n, prefix_bits, max_memory, min_quality,
+// max_read_n); the deviations on the reference's undefined paths are listed in kmhgpu.h.
 int kmhg_sh1_count_fastq(kmhg_index** sh, const char* path, const int32_t params[6]) {
   return guarded([&] {
     if (!sh || !path || !params) fail(KMHG_EINVAL, "null argument");
-    check_sh1_params(params);
-    const int k = params[0];
-    const ReadWalk walk = sh1_walk(params);
-    const uint64_t max_reads = (uint64_t)(int64_t)params[5];   // (size_t) of an int
-    hipStream_t s = lib_stream();
-    std::unique_ptr<kmhg_index> fresh;
-    kmhg_index* c = sh1_target(*sh, k, s, fresh);
-    DeviceGuard g(c->device);
-    ReadsHost r;
-    read_fastx(path, max_reads, k, r, [&](ReadsHost& b) {
-      sh_count_reads_host(c, b, walk, s);
-      c->L += (int64_t)b.seq.size();
-    });
-    sh_count_reads_host(c, r, walk, s);
-    c->L += (int64_t)r.seq.size();
-    if (fresh) *sh = fresh.release();
+    count_fastq(sh, path, read_call_sh1(params));
   });
 }
 
 int kmhg_sh1_count_reads(kmhg_index** sh, const kmhg_reads* r, const int32_t params[6]) {
   return guarded([&] {
     if (!sh || !r || !params) fail(KMHG_EINVAL, "null argument");
-    check_sh1_params(params);
-    const int k = params[0];
-    hipStream_t s = lib_stream();
-    std::unique_ptr<kmhg_index> fresh;
-    kmhg_index* c = sh1_target(*sh, k, s, fresh);
-    DeviceGuard g(c->device);
-    ReadsHost keep;
-    const ReadsHost* use = reads_longer_than(r->r, k, keep);
-    sh_count_reads_host(c, *use, sh1_walk(params), s);
-    c->L += (int64_t)use->seq.size();
-    if (fresh) *sh = fresh.release();
+    count_reads(sh, r, read_call_sh1(params));
   });
 }
 
@@ -3091,21 +2933,30 @@ int kmhg_sh1_count_reads_device(kmhg_index** sh, const void* d_seq, const void* 
                                 const int64_t* d_offsets, const uint8_t* d_has_qual,
                                 int64_t n_reads, const int32_t params[6], void* stream) {
   return guarded([&] {
-    if (!sh || !params || (n_reads > 0 && (!d_seq || !d_qual || !d_offsets || !d_has_qual)))
-      fail(KMHG_EINVAL, "null argument");
-    check_sh1_params(params);
-    if (n_reads < 0 || n_reads >= (int64_t)UINT32_MAX) fail(KMHG_EINVAL, "bad read count");
-    if ((reinterpret_cast<uintptr_t>(d_seq) | reinterpret_cast<uintptr_t>(d_qual)) & 15)
-      fail(KMHG_EINVAL, "read bases and qualities must be 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    std::unique_ptr<kmhg_index> fresh;
-    kmhg_index* c = sh1_target(*sh, params[0], s, fresh);
-    DeviceGuard g(c->device);
-    check_batch_span(d_offsets, n_reads, s);
-    sh_count_reads_device(c, (const uint8_t*)d_seq, (const uint8_t*)d_qual, d_offsets,
-                          d_has_qual, (uint32_t)n_reads, sh1_walk(params), s);
-    if (fresh) *sh = fresh.release();
+    if (!sh || !params) fail(KMHG_EINVAL, "null argument");
+    count_reads_device(sh, d_seq, d_qual, d_offsets, d_has_qual, n_reads, read_call_sh1(params),
+                       (hipStream_t)stream);
   });
+}
+
+// k_spectrum over sh's rows into counts (nbins doubles, zeroed by the caller): args holds comb_n
+// combinations, their comb_n inner flags and one source_min per source.
+static void spectrum_bins(kmhg_index* sh, uint32_t max_count, const std::vector<uint32_t>& args,
+                          uint32_t comb_n, size_t nbins, double* counts) {
+  DeviceGuard g(sh->device);
+  hipStream_t s = lib_stream();
+  finish_build(sh);
+  if (!sh->U) return;
+  DBuf<uint32_t> dargs(args.size(), s), bins(nbins, s);
+  HIPC(hipMemcpyAsync(dargs.p, args.data(), args.size() * 4, hipMemcpyHostToDevice, s));
+  HIPC(hipMemsetAsync(bins.p, 0, nbins * 4, s));
+  LAUNCH("k_spectrum", s,
+         launch_spectrum(sh->positions.p, sh->U, sh->sources, max_count, dargs.p, dargs.p + comb_n,
+                         comb_n, dargs.p + 2 * comb_n, bins.p, s));
+  std::vector<uint32_t> h(nbins);
+  HIPC(hipMemcpyAsync(h.data(), bins.p, nbins * 4, hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  for (size_t i = 0; i < nbins; ++i) counts[i] = (double)h[i];
 }
 
 // sh_count_spectrum (src/suffix_hash.c:112-129): counts[min(count, max_count)] += 1 per k-mer.
@@ -3119,21 +2970,7 @@ int kmhg_sh1_spectrum(kmhg_index* sh, int max_count, double* counts) {
     if (!counts) fail(KMHG_EINVAL, "null argument");
     const size_t nbins = (size_t)max_count + 1;
     std::fill(counts, counts + nbins, 0.0);
-    DeviceGuard g(sh->device);
-    hipStream_t s = lib_stream();
-    finish_build(sh);
-    if (!sh->U) return;
-    const uint32_t args[3] = {1u, 0u, 0u};               // comb, inner, source_min
-    DBuf<uint32_t> dargs(3, s), bins(nbins, s);
-    HIPC(hipMemcpyAsync(dargs.p, args, sizeof args, hipMemcpyHostToDevice, s));
-    HIPC(hipMemsetAsync(bins.p, 0, nbins * 4, s));
-    LAUNCH("k_spectrum", s,
-           launch_spectrum(sh->positions.p, sh->U, 1, (uint32_t)max_count, dargs.p, dargs.p + 1, 1,
-                           dargs.p + 2, bins.p, s));
-    std::vector<uint32_t> h(nbins);
-    HIPC(hipMemcpyAsync(h.data(), bins.p, nbins * 4, hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));
-    for (size_t i = 0; i < nbins; ++i) counts[i] = (double)h[i];
+    spectrum_bins(sh, (uint32_t)max_count, {1u, 0u, 0u}, 1, nbins, counts);
   });
 }
 
@@ -3192,36 +3029,19 @@ int kmhg_sh_spectrum(kmhg_index* sh, int max_count, const int32_t* comb,
     const uint32_t S = sh->sources;
     const size_t nbins = (size_t)(max_count + 1) * (size_t)comb_n * S;
     std::fill(counts, counts + nbins, 0.0);
-    int st = 1;
-    for (int i = 0; i < comb_n && st == 1; ++i) {
-      if ((uint32_t)comb_inner[i] > 1) st = -3;
-      else if ((uint32_t)comb[i] >= (1u << S)) st = -4;
-    }
+    const int st = spectrum_status(comb, comb_inner, comb_n, S);
     if (status) *status = st;
     if (st != 1) {
       fprintf(stderr, "sh_count_spectrum_nc returned an error: %d\n", st);
       return;
     }
-    DeviceGuard g(sh->device);
-    hipStream_t s = lib_stream();
-    finish_build(sh);
-    if (!sh->U) return;
     std::vector<uint32_t> args((size_t)2 * comb_n + S);
     for (int i = 0; i < comb_n; ++i) {
       args[i] = (uint32_t)comb[i];
       args[comb_n + i] = (uint32_t)comb_inner[i];
     }
     for (uint32_t j = 0; j < S; ++j) args[2 * comb_n + j] = (uint32_t)source_min[j];
-    DBuf<uint32_t> dargs(args.size(), s), bins(nbins, s);
-    HIPC(hipMemcpyAsync(dargs.p, args.data(), args.size() * 4, hipMemcpyHostToDevice, s));
-    HIPC(hipMemsetAsync(bins.p, 0, nbins * 4, s));
-    LAUNCH("k_spectrum", s,
-           launch_spectrum(sh->positions.p, sh->U, S, (uint32_t)max_count, dargs.p,
-                           dargs.p + comb_n, (uint32_t)comb_n, dargs.p + 2 * comb_n, bins.p, s));
-    std::vector<uint32_t> h(nbins);
-    HIPC(hipMemcpyAsync(h.data(), bins.p, nbins * 4, hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));
-    for (size_t i = 0; i < nbins; ++i) counts[i] = (double)h[i];
+    spectrum_bins(sh, (uint32_t)max_count, args, (uint32_t)comb_n, nbins, counts);
   });
 }
 

@@ -4,8 +4,8 @@
 // tests/test_asan_host.py (CPU only).  What runs here is exactly the source the product and the
 // checker compile: kmhg_fastx.h (the FASTA/FASTQ reader that parses untrusted input),
 // kmhg_khash.h (the khash row-order replay), kmhg_plan.h (the partitioned build's plan),
-// kmhg_hostwork.h (the readout's worker pool, stripes and row expansions), oracle/kmer_oracle.c
-// and oracle/sh_oracle.c.  host_check_tsan is this file under ThreadSanitizer
+// kmhg_hostwork.h (the readout's worker pool, stripes and row expansions), kmhg_reads.h (the host
+// side of read counting), oracle/kmer_oracle.c and oracle/sh_oracle.c.  host_check_tsan is this file under ThreadSanitizer
 // (tests/test_host_work.py).
 //
 //   host_check fastx <path> <max_records>   one line per record: R <len> <has_qual> <fnv seq>
@@ -35,6 +35,19 @@
 //   host_check misc span=<address>,<bytes> | class=<bytes> | cap=<windows> | len=<hex bytes> ...
 //                                           huge_span, pool_size_class, table_capacity,
 //                                           effective_len: one line per argument
+// kmhg_reads.h (tests/test_reads_host.py):
+//   host_check read-call rp|sh1 <ints...>   read_call_rp / read_call_sh1 of the 8 / 6 parameters:
+//                                           "err=<code> msg=<text>" or the decoded fields
+//   host_check read-batches <span_max> <file of read lengths>   read_batches: "err=.. msg=.." or
+//                                           one "i0 i1" line per range
+//   host_check reads-longer <k> <fastx>     read_fastx at k = 0, then reads_longer_than(k): same
+//                                           (1: the object itself came back), n, off, hasq and FNV
+//                                           sums of seq and qual
+//   host_check read-fastx <fastx> <k> <max_reads> <batch>   read_fastx flushing from <batch>
+//                                           bases on: "B <reads> <bases>" per flush, then "T" with
+//                                           the return value, the records, and every kept read's
+//                                           length and has_qual with FNV sums over all batches
+//   host_check spectrum-status <S> <comb,...> <comb_inner,...>   spectrum_status
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
@@ -50,6 +63,7 @@
 #include "../../kmer_hasher_amd/csrc/kmhg_khash.h"
 #include "../../kmer_hasher_amd/csrc/kmhg_plan.h"
 #include "../../kmer_hasher_amd/csrc/kmhg_hostwork.h"
+#include "../../kmer_hasher_amd/csrc/kmhg_reads.h"
 
 extern "C" {
 long orc_windows(const char* seq, long L, int k, uint64_t* keys, int32_t* s, int32_t* e);
@@ -378,6 +392,94 @@ static int cmd_misc(int argc, char** argv) {
   return 0;
 }
 
+// ---------------------------------------------------------------------------- kmhg_reads.h
+// integers of argv[from ..), or of a comma-separated list, heap-allocated at their exact number
+static std::vector<int32_t> ints_of(int argc, char** argv, int from) {
+  std::vector<int32_t> v;
+  for (int i = from; i < argc; ++i) v.push_back((int32_t)strtoll(argv[i], nullptr, 10));
+  return v;
+}
+static std::vector<int32_t> ints_of(const char* csv) {
+  std::vector<int32_t> v;
+  std::istringstream is(csv);
+  for (std::string w; std::getline(is, w, ',');) v.push_back((int32_t)strtoll(w.c_str(), nullptr, 10));
+  return v;
+}
+
+static int cmd_read_call(int argc, char** argv) {
+  const bool sh1 = std::string(argv[2]) == "sh1";
+  const std::vector<int32_t> p = ints_of(argc, argv, 3);
+  if (p.size() != (sh1 ? 6u : 8u)) return 2;
+  const kmhg::ReadCall c = sh1 ? kmhg::read_call_sh1(p.data()) : kmhg::read_call_rp(p.data());
+  if (c.err) { printf("err=%d msg=%s\n", c.err, c.msg); return 0; }
+  printf("err=0 k=%d sources=%u single=%d sh1=%d min_ll=%.17g mq=%d source=%u max_reads=%" PRIu64
+         "\n", c.k, c.sources, c.single ? 1 : 0, c.walk.sh1 ? 1 : 0, c.walk.min_ll, c.walk.mq,
+         c.walk.source, c.max_reads);
+  return 0;
+}
+
+static int cmd_read_batches(uint64_t span_max, const char* path) {
+  std::ifstream f(path);
+  if (!f) { perror(path); return 2; }
+  std::vector<int64_t> off{0};
+  for (int64_t l; f >> l;) off.push_back(off.back() + l);
+  off.shrink_to_fit();
+  std::vector<std::pair<size_t, size_t>> out;
+  const kmhg::Refusal bad = kmhg::read_batches(off.data(), off.size() - 1, span_max, out);
+  if (bad.err) printf("err=%d msg=%s\n", bad.err, bad.msg);
+  for (auto& b : out) printf("%zu %zu\n", b.first, b.second);
+  return 0;
+}
+
+static void print_reads(const kmhg::ReadsHost& r) {
+  printf("n=%zu off=", r.n());
+  for (size_t i = 0; i < r.off.size(); ++i) printf("%s%" PRId64, i ? "," : "", r.off[i]);
+  printf(" hasq=");
+  for (uint8_t h : r.hasq) printf("%d", h);
+  printf(" seq=%016" PRIx64 " qual=%016" PRIx64 "\n", fnv(r.seq.data(), r.seq.size()),
+         fnv(r.qual.data(), r.qual.size()));
+}
+
+static int cmd_reads_longer(int k, const char* path) {
+  kmhg::ReadsHost r, keep;
+  kmhg::read_fastx(path, UINT64_MAX, 0, r, nullptr);
+  const kmhg::ReadsHost* use = kmhg::reads_longer_than(r, k, keep);
+  printf("same=%d ", use == &r ? 1 : 0);
+  print_reads(*use);
+  return 0;
+}
+
+static int cmd_read_fastx(const char* path, int k, uint64_t max_reads, size_t batch) {
+  kmhg::ReadsHost r;
+  std::vector<int64_t> lens;
+  std::string hasq;
+  uint64_t hs = fnv(nullptr, 0), hq = hs;
+  const auto take = [&](kmhg::ReadsHost& b) {
+    for (size_t i = 0; i < b.n(); ++i) {
+      lens.push_back(b.off[i + 1] - b.off[i]);
+      hasq.push_back(b.hasq[i] ? '1' : '0');
+    }
+    hs = fnv(b.seq.data(), b.seq.size(), hs);
+    hq = fnv(b.qual.data(), b.qual.size(), hq);
+  };
+  const int64_t read_n = kmhg::read_fastx(path, max_reads, k, r, [&](kmhg::ReadsHost& b) {
+    printf("B %zu %zu\n", b.n(), b.seq.size());
+    take(b);
+  }, batch);
+  take(r);
+  printf("T read_n=%" PRId64 " records=%" PRId64 " lens=", read_n, r.records);
+  for (size_t i = 0; i < lens.size(); ++i) printf("%s%" PRId64, i ? "," : "", lens[i]);
+  printf(" hasq=%s seq=%016" PRIx64 " qual=%016" PRIx64 "\n", hasq.c_str(), hs, hq);
+  return 0;
+}
+
+static int cmd_spectrum_status(uint32_t S, const char* comb_csv, const char* inner_csv) {
+  const std::vector<int32_t> comb = ints_of(comb_csv), inner = ints_of(inner_csv);
+  if (comb.size() != inner.size()) return 2;
+  printf("%d\n", kmhg::spectrum_status(comb.data(), inner.data(), (int)comb.size(), S));
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 3) { fprintf(stderr, "usage: see the file header\n"); return 2; }
   const std::string c = argv[1];
@@ -394,6 +496,14 @@ int main(int argc, char** argv) {
   if (c == "pair-start" && argc == 3) return cmd_pair_start(argv[2]);
   if (c == "pool" && argc == 6)
     return cmd_pool(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]) != 0);
+  if (c == "read-call" && argc >= 4) return cmd_read_call(argc, argv);
+  if (c == "read-batches" && argc == 4) return cmd_read_batches(strtoull(argv[2], nullptr, 10), argv[3]);
+  if (c == "reads-longer" && argc == 4) return cmd_reads_longer(atoi(argv[2]), argv[3]);
+  if (c == "read-fastx" && argc == 6)
+    return cmd_read_fastx(argv[2], atoi(argv[3]), strtoull(argv[4], nullptr, 10),
+                          (size_t)strtoull(argv[5], nullptr, 10));
+  if (c == "spectrum-status" && argc == 5)
+    return cmd_spectrum_status((uint32_t)atoi(argv[2]), argv[3], argv[4]);
   if (c == "fastx" && argc == 4) return cmd_fastx(argv[2], atol(argv[3]));
   if (c == "khash" && argc == 4) return cmd_khash(atol(argv[2]), strtoull(argv[3], nullptr, 10));
   if (c == "index" && argc == 4) return cmd_index(argv[2], atoi(argv[3]));
