@@ -1,7 +1,8 @@
 // kmhg_engine.cpp -- host orchestrator of the MI355X k-mer position index + the C-ABI.
 //
 // Runtime pieces (native, as the reference's C core is native):
-//   * DevicePool   caching device allocator (size-classed free lists per device)
+//   * DevicePool   caching device allocator: BlockPool (kmhg_pool.h, all of its bookkeeping)
+//                  over the HipDev backend below
 //   * Timing       per-kernel HIP-event pairs on the launch stream (kmhg_timing_*)
 //   * Index/Query  build -> query -> readout pipelines over kmhg_kernels.hip
 // Reference entry points each C function replaces are listed in include/kmhgpu.h.
@@ -28,6 +29,7 @@
 #include "kmhg_kernels.h"
 #include "kmhg_plan.h"
 #include "kmhg_hostwork.h"
+#include "kmhg_pool.h"
 #include "kmhg_reads.h"
 #include "kmhg_parts_read.h"
 #include "kmhg_fastx.h"
@@ -45,7 +47,8 @@
 // between equivalent paths and change no result; fault injection (KMHG_TEST_DISORDER); and the
 // A/B-only switches (KMHG_D2H, KMHG_D2H_HUGE, KMHG_HOST_RUNS, KMHG_HOST_PAIRS, KMHG_HOST_POOL,
 // KMHG_COUNT_BID, KMHG_RK_CAP, KMHG_SH_SPAN (the span_max given to read_batches, kmhg_reads.h),
-// KMHG_POOL_DEPTH, KMHG_POOL_BESTFIT, KMHG_POOL_TRACE).
+// KMHG_POOL_DEPTH, KMHG_POOL_BESTFIT, KMHG_POOL_TRACE (the pool's: PoolKnobs, kmhg_pool.h, filled
+// once by HipDev::knobs below)).
 namespace kmhg {
 inline const char* test_build_knob(const char* name) {
 #ifdef KMHG_TEST_BUILD
@@ -95,241 +98,44 @@ int guarded(F&& f) {
 }
 
 // ============================================================================ device pool
-// Caching allocator: blocks are kept per (device, rounded size) and reused, so repeated builds
-// and queries (bench steps, many queries against one index) pay hipMalloc once.
-// Stream-ordered releases inside one host call (one build, query, ...) share ONE event: every
-// ordered release on the group's stream is deferred to the group's end, where a single event is
-// recorded for all of them.  (Each event record is a marker packet the command processor
-// drains the stream for; a build used to record ~14 of them back to back.)
-struct ReleaseGroup;
-thread_local ReleaseGroup* tl_release_group = nullptr;
-
-class DevicePool {
- public:
-  static DevicePool& get() {
-    static DevicePool p;
-    return p;
+// BlockPool (kmhg_pool.h) over HIP.  Events carry no timing; an out-of-memory answer is cleared
+// from the runtime's last-error slot, since the pool trims its cache and asks again.
+struct HipDev {
+  static PoolKnobs knobs() {          // test build: KMHG_POOL_DEPTH / _BESTFIT / _TRACE
+    PoolKnobs kn;
+    if (const char* e = test_build_knob("KMHG_POOL_DEPTH"))
+      kn.depth = (size_t)std::max(1, std::min(8, std::atoi(e)));
+    if (const char* e = test_build_knob("KMHG_POOL_BESTFIT")) kn.best_fit = e[0] != '0';
+    kn.trace = test_build_knob("KMHG_POOL_TRACE") != nullptr;
+    return kn;
   }
-  void* alloc(size_t bytes) {
-    if (bytes == 0) bytes = 256;
-    size_t sz = pool_size_class(bytes);
-    int dev = 0;
-    HIPC(hipGetDevice(&dev));
-    {
-      std::unique_lock<std::mutex> g(mu_);
-      poll_pending();
-      auto& fl = free_[{dev, sz}];
-      if (!fl.empty()) {
-        void* p = fl.back();
-        fl.pop_back();
-        cached_ -= sz;
-        live_[p] = {dev, sz};
-        return p;
-      }
-      // a block of this size still in use by queued work: wait for it rather than grow the
-      // pool -- the back-pressure that bounds how far asynchronous builds run ahead.  Up to
-      // DEPTH blocks of a size class exist before a request waits.  (Depth 2, so that the host
-      // enqueues build i + 1 while build i runs, measured no faster at 10 / 100 / 500 Mbp:
-      // the gaps between a build's kernels are the device's, not the host's enqueue.)
-      static const size_t depth = [] {            // KMHG_POOL_DEPTH (test build): 1..8
-        const char* e = test_build_knob("KMHG_POOL_DEPTH");
-        return e ? (size_t)std::max(1, std::min(8, std::atoi(e))) : POOL_DEPTH;
-      }();
-      for (size_t i = 0; i < pending_.size() && count_[{dev, sz}] >= depth; ++i) {
-        if (pending_[i].key != std::make_pair(dev, sz)) continue;
-        Pending pd = pending_[i];
-        pending_.erase(pending_.begin() + (long)i);
-        g.unlock();
-        (void)hipEventSynchronize(pd.ev);
-        g.lock();
-        if (pd.owns_ev) events_.push_back(pd.ev);
-        live_[pd.p] = pd.key;
-        return pd.p;
-      }
-      // a large request with no block of its own size: the smallest idle cached block of at
-      // most 1.5x its size serves it (it keeps its own size class and returns to it).  A
-      // hipMalloc of GBs costs ~0.1 ms per GB: the first 500 Mbp query of a process reuses the
-      // build's freed 6 GB stream buffers for its records and rows (2 of its 3 GB-sized
-      // buffers) instead of allocating 10 GB.
-      static const bool best_fit = [] {           // KMHG_POOL_BESTFIT=0 (test build): off
-        const char* e = test_build_knob("KMHG_POOL_BESTFIT");
-        return !(e && e[0] == '0');
-      }();
-      if (best_fit && sz >= BEST_FIT_MIN) {
-        auto it = free_.lower_bound({dev, sz});
-        for (; it != free_.end() && it->first.first == dev && it->first.second <= sz + sz / 2;
-             ++it) {
-          if (it->second.empty()) continue;
-          void* p = it->second.back();
-          it->second.pop_back();
-          cached_ -= it->first.second;
-          live_[p] = it->first;
-          return p;
-        }
-      }
-    }
-    void* p = nullptr;
-    static const bool trace = test_build_knob("KMHG_POOL_TRACE") != nullptr;   // test build
-    if (trace) std::fprintf(stderr, "kmhg pool: hipMalloc %zu B on device %d\n", sz, dev);
-    hipError_t e = hipMalloc(&p, sz);
-    if (e == hipErrorOutOfMemory) {   // release the cache and retry once
-      (void)hipGetLastError();
-      trim();
-      e = hipMalloc(&p, sz);
-    }
-    hip_check(e, "hipMalloc");
-    std::lock_guard<std::mutex> g(mu_);
-    live_[p] = {dev, sz};
-    ++count_[{dev, sz}];
-    return p;
+  int current() { int dev = 0; HIPC(hipGetDevice(&dev)); return dev; }
+  void use(int dev) { (void)hipSetDevice(dev); }
+  PoolAlloc alloc(size_t sz, void** p, std::string* text) {
+    const hipError_t e = hipMalloc(p, sz);
+    if (e == hipSuccess) return PoolAlloc::ok;
+    if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return PoolAlloc::oom; }
+    *text = hipGetErrorString(e);
+    return PoolAlloc::error;
   }
-  // Stream-ordered release: the block returns to the free list once the work queued on
-  // `stream` up to now has completed (an event is recorded and polled on later allocations).
-  void release(void* p, hipStream_t stream = nullptr, bool ordered = false);
-  // the group's blocks: one event recorded on `stream` for all of them
-  void release_batch(const std::vector<void*>& ps, hipStream_t stream) {
-    if (ps.empty()) return;
-    hipEvent_t ev = recorded_event(stream);
-    std::lock_guard<std::mutex> g(mu_);
-    size_t owner = SIZE_MAX;            // the last entry actually queued recycles the event
-    for (size_t i = 0; i < ps.size(); ++i) {
-      auto it = live_.find(ps[i]);
-      if (it == live_.end()) continue;
-      if (ev) {
-        owner = pending_.size();
-        pending_.push_back({ps[i], it->second, ev, false});
-      } else {
-        free_[it->second].push_back(ps[i]);
-        cached_ += it->second.second;
-      }
-      live_.erase(it);
-    }
-    if (ev) {
-      if (owner != SIZE_MAX) pending_[owner].owns_ev = true;
-      else events_.push_back(ev);       // nothing queued: the event goes straight back
-    }
-  }
-  // blocks no queued work uses any more (their stream was synchronized)
-  void release_now(const std::vector<void*>& ps) {
-    std::lock_guard<std::mutex> g(mu_);
-    for (void* p : ps) {
-      auto it = live_.find(p);
-      if (it == live_.end()) continue;
-      free_[it->second].push_back(p);
-      cached_ += it->second.second;
-      live_.erase(it);
-    }
-  }
-  void release_one(void* p, hipStream_t stream, bool ordered) {
-    if (!p) return;
-    hipEvent_t ev = ordered ? recorded_event(stream) : nullptr;
-    std::lock_guard<std::mutex> g(mu_);
-    auto it = live_.find(p);
-    if (it == live_.end()) return;
-    if (ev) {
-      pending_.push_back({p, it->second, ev, true});
-    } else {
-      free_[it->second].push_back(p);
-      cached_ += it->second.second;
-    }
-    live_.erase(it);
-  }
-  void trim() {
-    std::lock_guard<std::mutex> g(mu_);
-    for (auto& pd : pending_) {
-      (void)hipEventSynchronize(pd.ev);
-      if (pd.owns_ev) events_.push_back(pd.ev);
-      free_[pd.key].push_back(pd.p);
-    }
-    pending_.clear();
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    for (auto& kv : free_) {
-      (void)hipSetDevice(kv.first.first);
-      for (void* p : kv.second) (void)hipFree(p);
-      count_[kv.first] -= std::min(count_[kv.first], kv.second.size());
-      kv.second.clear();
-    }
-    (void)hipSetDevice(cur);
-    cached_ = 0;
-  }
-  int64_t cached() {
-    std::lock_guard<std::mutex> g(mu_);
-    return (int64_t)cached_;
-  }
-
- private:
-  // owns_ev: the one entry of a batch that recycles the shared event.  An entry polled after
-  // its batch's event was recycled and recorded again only waits for later work (safe).
-  struct Pending { void* p; std::pair<int, size_t> key; hipEvent_t ev; bool owns_ev; };
-  // An event (recycled if one is idle) recorded on `stream`; where none can be made or recorded,
-  // the stream is synchronized instead and nullptr returned.  Takes mu_ itself: call unlocked.
-  hipEvent_t recorded_event(hipStream_t stream) {
+  void free(void* p) { (void)hipFree(p); }
+  void* event() {
     hipEvent_t ev = nullptr;
-    {
-      std::lock_guard<std::mutex> g(mu_);
-      if (!events_.empty()) { ev = events_.back(); events_.pop_back(); }
-    }
-    if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) ev = nullptr;
-    if (!ev || hipEventRecord(ev, stream) != hipSuccess) {
-      (void)hipStreamSynchronize(stream);
-      if (ev) { std::lock_guard<std::mutex> g(mu_); events_.push_back(ev); }
-      ev = nullptr;
-    }
-    return ev;
+    return hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess ? ev : nullptr;
   }
-  void poll_pending() {
-    for (size_t i = 0; i < pending_.size();) {
-      if (hipEventQuery(pending_[i].ev) == hipSuccess) {
-        if (pending_[i].owns_ev)
-          events_.push_back(pending_[i].ev);        // recycled: no create/destroy per release
-        free_[pending_[i].key].push_back(pending_[i].p);
-        cached_ += pending_[i].key.second;
-        pending_[i] = pending_.back();
-        pending_.pop_back();
-      } else {
-        ++i;
-      }
-    }
+  bool record(void* ev, void* s) {
+    return hipEventRecord(static_cast<hipEvent_t>(ev), static_cast<hipStream_t>(s)) == hipSuccess;
   }
-  static constexpr size_t BEST_FIT_MIN = (size_t)256 << 20;
-  static constexpr size_t POOL_DEPTH = 1;   // depth 2 measured: no gain
-  std::mutex mu_;
-  std::map<std::pair<int, size_t>, std::vector<void*>> free_;
-  std::map<std::pair<int, size_t>, size_t> count_;   // blocks of each size class (any state)
-  std::map<void*, std::pair<int, size_t>> live_;
-  std::vector<Pending> pending_;
-  std::vector<hipEvent_t> events_;
-  size_t cached_ = 0;
+  bool done(void* ev) { return hipEventQuery(static_cast<hipEvent_t>(ev)) == hipSuccess; }
+  void wait_event(void* ev) { (void)hipEventSynchronize(static_cast<hipEvent_t>(ev)); }
+  void wait_stream(void* s) { (void)hipStreamSynchronize(static_cast<hipStream_t>(s)); }
+  [[noreturn]] void alloc_failed(PoolAlloc st, const std::string& text) {
+    if (st == PoolAlloc::oom) fail(KMHG_ENOMEM, "hipMalloc: out of device memory");
+    fail(KMHG_EDEVICE, "hipMalloc: " + text);
+  }
 };
-
-struct ReleaseGroup {
-  hipStream_t s;
-  std::vector<void*> ps;
-  ReleaseGroup* prev;
-  // set after a synchronize of `s` with no launch behind it: the blocks go straight back to the
-  // pool, no event (a synchronous call's last step)
-  bool synced = false;
-  explicit ReleaseGroup(hipStream_t stream) : s(stream), prev(tl_release_group) {
-    tl_release_group = this;
-  }
-  ~ReleaseGroup() {
-    tl_release_group = prev;
-    if (synced) DevicePool::get().release_now(ps);
-    else DevicePool::get().release_batch(ps, s);
-  }
-  ReleaseGroup(const ReleaseGroup&) = delete;
-  ReleaseGroup& operator=(const ReleaseGroup&) = delete;
-};
-
-void DevicePool::release(void* p, hipStream_t stream, bool ordered) {
-  if (!p) return;
-  if (ordered && tl_release_group && tl_release_group->s == stream) {
-    tl_release_group->ps.push_back(p);          // deferred to the group's one event
-    return;
-  }
-  release_one(p, stream, ordered);
-}
+using DevicePool = BlockPool<HipDev>;
+using ReleaseGroup = ReleaseGroupT<HipDev>;
 
 // RAII device buffer from the pool.  A buffer bound to a stream is released stream-ordered
 // (kernels still queued on that stream may use it after the C++ object dies).

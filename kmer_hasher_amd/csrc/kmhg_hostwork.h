@@ -2,8 +2,8 @@
 //
 // What the engine's host-pointer entry points do on CPU threads once the bytes have left the
 // device: the worker pool, the striping of a range over it, the expansion of diagonal runs and of
-// pair lists into rows, and the small pure helpers around them (huge-page spans, the device pool's
-// size classes, table capacity, a C string's length).  Nothing here reads the environment: the
+// pair lists into rows, and the small pure helpers around them (huge-page spans, table capacity, a
+// C string's length).  Nothing here reads the environment: the
 // engine passes every choice in.  tools/asan/host_check runs all of it under ASan + UBSan and
 // under ThreadSanitizer at shapes of a few rows (tests/test_host_work.py).
 #pragma once
@@ -263,17 +263,6 @@ inline Span huge_span(const void* dst, size_t bytes) {
   const uintptr_t m = ~(uintptr_t)(HUGE_SPAN - 1), d = reinterpret_cast<uintptr_t>(dst);
   const uintptr_t a = (d + HUGE_SPAN - 1) & m, b = (d + bytes) & m;
   return b > a ? Span{a, (size_t)(b - a)} : Span{0, 0};
-}
-
-// The device pool's size class of a request.
-inline size_t pool_size_class(size_t b) {
-  if (b <= (1u << 20)) {           // small: power of two >= 256 B
-    size_t r = 256;
-    while (r < b) r <<= 1;
-    return r;
-  }
-  const size_t g = 2u << 20;       // large: 2 MiB granules
-  return (b + g - 1) / g * g;
 }
 
 // The hash table is sized from the number of windows (an upper bound on distinct k-mers) for a

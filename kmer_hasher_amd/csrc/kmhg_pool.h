@@ -1,0 +1,291 @@
+// kmhg_pool.h -- the device block pool's bookkeeping (host only: no HIP, any C++17 compiler).
+//
+// Caching allocator: blocks are kept per (device, size class) and reused, so repeated builds and
+// queries (bench steps, many queries against one index) pay the device allocation once.
+// Stream-ordered releases inside one host call (one build, query, ...) share ONE event: every
+// ordered release on the group's stream is deferred to the group's end, where a single event is
+// recorded for all of them.  (Each event record is a marker packet the command processor drains
+// the stream for; a build used to record ~14 of them back to back.)
+//
+// The device sits behind `Dev`, a small backend whose stream and event handles are opaque
+// pointers (the engine's HipDev; a fake of malloc'ed blocks and scripted events in
+// tools/asan/host_check).  A Dev provides
+//   int  current()                          the calling thread's device
+//   void use(int dev)                       make `dev` current
+//   PoolAlloc alloc(size_t sz, void** p, std::string* text)   ok / oom / error with its text
+//   void free(void* p)                      a block of the current device
+//   void* event()                           a new event, nullptr where none can be made
+//   bool record(void* ev, void* stream)     false where it cannot be recorded
+//   bool done(void* ev)                     has the work recorded before it completed?
+//   void wait_event(void* ev), void wait_stream(void* stream)
+//   [[noreturn]] void alloc_failed(PoolAlloc, const std::string& text)    the caller's error
+//   static PoolKnobs knobs()                (only for BlockPool::get())
+// All control flow is here; nothing here reads the environment.  tools/asan/host_check runs the
+// pool under ASan + UBSan against literal scenarios and host_check_tsan runs it from four threads
+// (tests/test_pool_host.py).
+#pragma once
+#include <stdint.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <map>
+#include <mutex>
+#include <string>
+#include <utility>
+#include <vector>
+
+namespace kmhg {
+
+// The pool's size class of a request.
+inline size_t pool_size_class(size_t b) {
+  if (b <= (1u << 20)) {           // small: power of two >= 256 B
+    size_t r = 256;
+    while (r < b) r <<= 1;
+    return r;
+  }
+  const size_t g = 2u << 20;       // large: 2 MiB granules
+  return (b + g - 1) / g * g;
+}
+
+// The test build's switches of the pool (defaults = the product).
+struct PoolKnobs {
+  size_t depth = 1;       // KMHG_POOL_DEPTH, 1..8: blocks of a class before a request waits for
+                          // one (depth 2 measured: no gain)
+  bool best_fit = true;   // KMHG_POOL_BESTFIT=0: off
+  bool trace = false;     // KMHG_POOL_TRACE: a stderr line per device allocation
+};
+
+enum class PoolAlloc { ok, oom, error };
+
+template <class Dev>
+struct ReleaseGroupT;
+
+template <class Dev>
+class BlockPool {
+ public:
+  using Key = std::pair<int, size_t>;          // (device, size class)
+  struct Block { void* p; Key key; void* ev; bool owns_ev; };
+  struct Snapshot {                            // for tests: every block the pool knows, by state
+    std::vector<Block> live, free, pending;
+    size_t idle_events, cached;
+  };
+
+  explicit BlockPool(PoolKnobs kn = {}, Dev dev = {}) : kn_(kn), dev_(dev) {}
+  BlockPool(const BlockPool&) = delete;
+  BlockPool& operator=(const BlockPool&) = delete;
+  static BlockPool& get() {
+    static BlockPool p(Dev::knobs());
+    return p;
+  }
+
+  void* alloc(size_t bytes) {
+    if (bytes == 0) bytes = 256;
+    const Key key{dev_.current(), pool_size_class(bytes)};
+    const size_t sz = key.second;
+    {
+      std::unique_lock<std::mutex> g(mu_);
+      poll_pending();
+      auto fl = free_.find(key);
+      if (fl != free_.end() && !fl->second.empty()) return take(fl);
+      // a block of this size still in use by queued work: wait for it rather than grow the
+      // pool -- the back-pressure that bounds how far asynchronous builds run ahead.  Up to
+      // depth blocks of a size class exist before a request waits.  (Depth 2, so that the host
+      // enqueues build i + 1 while build i runs, measured no faster at 10 / 100 / 500 Mbp:
+      // the gaps between a build's kernels are the device's, not the host's enqueue.)
+      auto n = count_.find(key);
+      if (n != count_.end() && n->second >= kn_.depth) {
+        for (size_t i = 0; i < pending_.size(); ++i) {
+          if (pending_[i].key != key) continue;
+          const Block pd = pending_[i];
+          pending_.erase(pending_.begin() + (long)i);
+          g.unlock();
+          dev_.wait_event(pd.ev);
+          g.lock();
+          if (pd.owns_ev) events_.push_back(pd.ev);
+          live_[pd.p] = pd.key;
+          return pd.p;
+        }
+      }
+      // a large request with no block of its own size: the smallest idle cached block of at
+      // most 1.5x its size serves it (it keeps its own size class and returns to it).  A
+      // device allocation of GBs costs ~0.1 ms per GB: the first 500 Mbp query of a process
+      // reuses the build's freed 6 GB stream buffers for its records and rows (2 of its 3
+      // GB-sized buffers) instead of allocating 10 GB.
+      if (kn_.best_fit && sz >= BEST_FIT_MIN) {
+        for (auto it = free_.lower_bound(key);
+             it != free_.end() && it->first.first == key.first && it->first.second <= sz + sz / 2;
+             ++it)
+          if (!it->second.empty()) return take(it);
+      }
+    }
+    if (kn_.trace)
+      std::fprintf(stderr, "kmhg pool: hipMalloc %zu B on device %d\n", sz, key.first);
+    void* p = nullptr;
+    std::string text;
+    PoolAlloc st = dev_.alloc(sz, &p, &text);
+    if (st == PoolAlloc::oom) {   // release the cache and retry once
+      trim();
+      st = dev_.alloc(sz, &p, &text);
+    }
+    if (st != PoolAlloc::ok) dev_.alloc_failed(st, text);
+    std::lock_guard<std::mutex> g(mu_);
+    live_[p] = key;
+    ++count_[key];
+    return p;
+  }
+
+  // An unordered release returns the block at once.  A stream-ordered one returns it once the
+  // work queued on `stream` up to now has completed (an event is recorded and polled on later
+  // allocations); inside the thread's open ReleaseGroup of that stream it waits for the group's
+  // end.  Unknown and null pointers are ignored.
+  void release(void* p, void* stream = nullptr, bool ordered = false) {
+    if (!p) return;
+    ReleaseGroupT<Dev>* rg = ReleaseGroupT<Dev>::open;
+    if (ordered && rg && &rg->pool == this && rg->s == stream) {
+      rg->ps.push_back(p);          // deferred to the group's one event
+      return;
+    }
+    if (ordered) release_behind(&p, 1, stream);
+    else release_now(&p, 1);
+  }
+  // blocks still used by work queued on `stream`: one event recorded for all of them.  Where no
+  // event can be made or recorded, the stream is waited for instead and they go straight back.
+  void release_behind(void* const* ps, size_t n, void* stream) {
+    if (n == 0) return;
+    void* ev = recorded_event(stream);
+    std::lock_guard<std::mutex> g(mu_);
+    const size_t before = pending_.size();
+    for (size_t i = 0; i < n; ++i) retire(ps[i], ev);
+    if (!ev) return;
+    if (pending_.size() > before) pending_.back().owns_ev = true;   // the last one queued
+    else events_.push_back(ev);       // nothing queued: the event goes straight back
+  }
+  // blocks no queued work uses any more (their stream was synchronized)
+  void release_now(void* const* ps, size_t n) {
+    std::lock_guard<std::mutex> g(mu_);
+    for (size_t i = 0; i < n; ++i) retire(ps[i], nullptr);
+  }
+  // Waits for every pending block and frees all cached ones, each on its own device.  Live
+  // blocks are not touched.
+  void trim() {
+    std::lock_guard<std::mutex> g(mu_);
+    for (const Block& pd : pending_) {
+      dev_.wait_event(pd.ev);
+      settle(pd);
+    }
+    pending_.clear();
+    const int cur = dev_.current();
+    for (auto& kv : free_) {
+      dev_.use(kv.first.first);
+      for (void* p : kv.second) dev_.free(p);
+      auto n = count_.find(kv.first);
+      if (n != count_.end()) n->second -= std::min(n->second, kv.second.size());
+      cached_ -= kv.first.second * kv.second.size();
+    }
+    free_.clear();
+    dev_.use(cur);
+  }
+  int64_t cached() {
+    std::lock_guard<std::mutex> g(mu_);
+    return (int64_t)cached_;
+  }
+  Snapshot snapshot() {
+    std::lock_guard<std::mutex> g(mu_);
+    Snapshot s{{}, {}, pending_, events_.size(), cached_};
+    for (auto& kv : live_) s.live.push_back({kv.first, kv.second, nullptr, false});
+    for (auto& kv : free_)
+      for (void* p : kv.second) s.free.push_back({p, kv.first, nullptr, false});
+    return s;
+  }
+
+ private:
+  // Everything below but recorded_event runs with mu_ held.
+  using FreeLists = std::map<Key, std::vector<void*>>;
+  void* take(typename FreeLists::iterator fl) {     // a cached block (its list not empty) -> live
+    void* p = fl->second.back();
+    fl->second.pop_back();
+    cached_ -= fl->first.second;
+    live_[p] = fl->first;
+    return p;
+  }
+  // p leaves live_: behind `ev` into pending_, or with no event straight into its free list
+  void retire(void* p, void* ev) {
+    auto it = live_.find(p);
+    if (it == live_.end()) return;
+    const Block b{p, it->second, ev, false};
+    live_.erase(it);
+    if (ev) pending_.push_back(b);
+    else settle(b);
+  }
+  // a block whose event (if any) has completed returns to its free list; the entry of a batch
+  // that owns the shared event recycles it (no create / destroy per release).  An entry polled
+  // after its batch's event was recycled and recorded again only waits for later work (safe).
+  void settle(const Block& b) {
+    if (b.owns_ev) events_.push_back(b.ev);
+    free_[b.key].push_back(b.p);
+    cached_ += b.key.second;
+  }
+  void poll_pending() {
+    for (size_t i = 0; i < pending_.size();) {
+      if (dev_.done(pending_[i].ev)) {
+        settle(pending_[i]);
+        pending_[i] = pending_.back();
+        pending_.pop_back();
+      } else {
+        ++i;
+      }
+    }
+  }
+  // An event (recycled if one is idle) recorded on `stream`; where none can be made or recorded,
+  // the stream is waited for instead and nullptr returned.  Takes mu_ itself: call unlocked.
+  void* recorded_event(void* stream) {
+    void* ev = nullptr;
+    {
+      std::lock_guard<std::mutex> g(mu_);
+      if (!events_.empty()) { ev = events_.back(); events_.pop_back(); }
+    }
+    if (!ev) ev = dev_.event();
+    if (!ev || !dev_.record(ev, stream)) {
+      dev_.wait_stream(stream);
+      if (ev) { std::lock_guard<std::mutex> g(mu_); events_.push_back(ev); }
+      ev = nullptr;
+    }
+    return ev;
+  }
+
+  static constexpr size_t BEST_FIT_MIN = (size_t)256 << 20;
+  const PoolKnobs kn_;
+  Dev dev_;
+  std::mutex mu_;
+  FreeLists free_;
+  std::map<Key, size_t> count_;      // blocks of each size class (any state)
+  std::map<void*, Key> live_;
+  std::vector<Block> pending_;
+  std::vector<void*> events_;        // idle events
+  size_t cached_ = 0;                // bytes in free_
+};
+
+// The ordered releases of one host call on its stream, collected on the calling thread and
+// returned to the pool together at the scope's end (groups nest; the innermost is the open one).
+template <class Dev>
+struct ReleaseGroupT {
+  static inline thread_local ReleaseGroupT* open = nullptr;
+  BlockPool<Dev>& pool;
+  void* s;
+  std::vector<void*> ps;
+  ReleaseGroupT* prev;
+  // set after a synchronize of `s` with no launch behind it: the blocks go straight back to the
+  // pool, no event (a synchronous call's last step)
+  bool synced = false;
+  ReleaseGroupT(BlockPool<Dev>& pl, void* stream) : pool(pl), s(stream), prev(open) { open = this; }
+  explicit ReleaseGroupT(void* stream) : ReleaseGroupT(BlockPool<Dev>::get(), stream) {}
+  ~ReleaseGroupT() {
+    open = prev;
+    if (synced) pool.release_now(ps.data(), ps.size());
+    else pool.release_behind(ps.data(), ps.size(), s);
+  }
+  ReleaseGroupT(const ReleaseGroupT&) = delete;
+  ReleaseGroupT& operator=(const ReleaseGroupT&) = delete;
+};
+
+}  // namespace kmhg

@@ -5,8 +5,9 @@
 // checker compile: kmhg_fastx.h (the FASTA/FASTQ reader that parses untrusted input),
 // kmhg_khash.h (the khash row-order replay), kmhg_plan.h (the partitioned build's plan),
 // kmhg_hostwork.h (the readout's worker pool, stripes and row expansions), kmhg_reads.h (the host
-// side of read counting), oracle/kmer_oracle.c and oracle/sh_oracle.c.  host_check_tsan is this file under ThreadSanitizer
-// (tests/test_host_work.py).
+// side of read counting), kmhg_pool.h (the device block pool, over a fake device),
+// oracle/kmer_oracle.c and oracle/sh_oracle.c.  host_check_tsan is this file under
+// ThreadSanitizer (tests/test_host_work.py, tests/test_pool_host.py).
 //
 //   host_check fastx <path> <max_records>   one line per record: R <len> <has_qual> <fnv seq>
 //                                           <fnv qual>, then E <last return code>
@@ -33,8 +34,8 @@
 //                                           0 .. max_tasks tasks to HostPool at once; each task
 //                                           adds its index to its job's sum; "ok" if all are right
 //   host_check misc span=<address>,<bytes> | class=<bytes> | cap=<windows> | len=<hex bytes> ...
-//                                           huge_span, pool_size_class, table_capacity,
-//                                           effective_len: one line per argument
+//                                           huge_span, pool_size_class (kmhg_pool.h),
+//                                           table_capacity, effective_len: one line per argument
 // kmhg_reads.h (tests/test_reads_host.py):
 //   host_check read-call rp|sh1 <ints...>   read_call_rp / read_call_sh1 of the 8 / 6 parameters:
 //                                           "err=<code> msg=<text>" or the decoded fields
@@ -48,11 +49,32 @@
 //                                           the return value, the records, and every kept read's
 //                                           length and has_qual with FNV sums over all batches
 //   host_check spectrum-status <S> <comb,...> <comb_inner,...>   spectrum_status
+// kmhg_pool.h (tests/test_pool_host.py): BlockPool over FakeDev, whose blocks are malloc'ed bytes
+// and whose events are the integers 1, 2, ... in the order they were made
+//   host_check pool <script>                one operation per line of the file, one line of state
+//                                           after each (pool_line below).  Operations:
+//                                             knobs <depth> <best_fit 0|1>   (first line only)
+//                                             dev <d>                 the thread's current device
+//                                             alloc <name> <bytes>    the block is called <name>
+//                                             release <name>|null|unknown [<stream>]   with a
+//                                                                     stream: stream-ordered
+//                                             group_begin <stream> | synced | group_end
+//                                             complete <event>        the event has completed
+//                                             fail alloc-oom|alloc-error|event|record <n>   the
+//                                                                     next n such calls fail
+//                                             trim | cached
+//   host_check pool threads <T> <ops>       T threads of <ops> mixed alloc / release / group
+//                                           operations over three classes while another thread
+//                                           completes the events; "ok" if every block is
+//                                           accounted for at the end
 #include <cinttypes>
+#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <map>
+#include <memory>
 #include <set>
 #include <sstream>
 #include <string>
@@ -63,6 +85,7 @@
 #include "../../kmer_hasher_amd/csrc/kmhg_khash.h"
 #include "../../kmer_hasher_amd/csrc/kmhg_plan.h"
 #include "../../kmer_hasher_amd/csrc/kmhg_hostwork.h"
+#include "../../kmer_hasher_amd/csrc/kmhg_pool.h"
 #include "../../kmer_hasher_amd/csrc/kmhg_reads.h"
 
 extern "C" {
@@ -392,6 +415,246 @@ static int cmd_misc(int argc, char** argv) {
   return 0;
 }
 
+// ---------------------------------------------------------------------------- kmhg_pool.h
+// The fake device's state, shared by the copies of FakeDev.  Every call is counted.  An event
+// completes when the script says so; a wait for one that has not completed it (script: there
+// is nobody else to do so), or blocks until complete_all() has (threads).
+struct FakeState {
+  std::mutex mu;
+  std::condition_variable cv;
+  bool blocking = false;
+  std::map<void*, int> ids;            // the blocks handed out and not yet freed
+  std::map<int, int> dev_of;           // by block id: the device it was allocated on
+  std::vector<int> freed;              // ids in the order freed, negated if on another device
+  std::vector<char> done{1};           // by event; [0] is not an event
+  int next_id = 0;
+  long allocs = 0, frees = 0, creates = 0, records = 0, ewaits = 0, swaits = 0;
+  int fail_oom = 0, fail_error = 0, fail_event = 0, fail_record = 0;
+  void complete_all() {
+    std::lock_guard<std::mutex> g(mu);
+    std::fill(done.begin(), done.end(), 1);
+    cv.notify_all();
+  }
+};
+struct FakeFailure { kmhg::PoolAlloc st; std::string text; };
+struct FakeDev {
+  FakeState* f;
+  static inline thread_local int cur = 0;
+  int current() { return cur; }
+  void use(int dev) { cur = dev; }
+  kmhg::PoolAlloc alloc(size_t sz, void** p, std::string* text) {
+    std::lock_guard<std::mutex> g(f->mu);
+    ++f->allocs;
+    if (f->fail_oom > 0) { --f->fail_oom; return kmhg::PoolAlloc::oom; }
+    if (f->fail_error > 0) { --f->fail_error; *text = "fake device error"; return kmhg::PoolAlloc::error; }
+    *p = malloc(std::min<size_t>(sz, 64));
+    f->ids[*p] = ++f->next_id;
+    f->dev_of[f->next_id] = cur;
+    return kmhg::PoolAlloc::ok;
+  }
+  void free(void* p) {
+    std::lock_guard<std::mutex> g(f->mu);
+    ++f->frees;
+    auto it = f->ids.find(p);
+    if (it != f->ids.end()) {
+      f->freed.push_back(f->dev_of[it->second] == cur ? it->second : -it->second);
+      f->ids.erase(it);
+    }
+    ::free(p);                          // a second free of p is ASan's to report
+  }
+  void* event() {
+    std::lock_guard<std::mutex> g(f->mu);
+    ++f->creates;
+    if (f->fail_event > 0) { --f->fail_event; return nullptr; }
+    f->done.push_back(0);
+    return reinterpret_cast<void*>((uintptr_t)(f->done.size() - 1));
+  }
+  bool record(void* ev, void*) {
+    std::lock_guard<std::mutex> g(f->mu);
+    ++f->records;
+    if (f->fail_record > 0) { --f->fail_record; return false; }
+    f->done[(uintptr_t)ev] = 0;
+    return true;
+  }
+  bool done(void* ev) {
+    std::lock_guard<std::mutex> g(f->mu);
+    return f->done[(uintptr_t)ev] != 0;
+  }
+  void wait_event(void* ev) {
+    std::unique_lock<std::mutex> g(f->mu);
+    ++f->ewaits;
+    if (f->blocking) f->cv.wait(g, [&] { return f->done[(uintptr_t)ev] != 0; });
+    else f->done[(uintptr_t)ev] = 1;
+  }
+  void wait_stream(void*) {
+    std::lock_guard<std::mutex> g(f->mu);
+    ++f->swaits;
+  }
+  [[noreturn]] void alloc_failed(kmhg::PoolAlloc st, const std::string& text) {
+    throw FakeFailure{st, text};
+  }
+};
+using FakePool = kmhg::BlockPool<FakeDev>;
+using FakeGroup = kmhg::ReleaseGroupT<FakeDev>;
+
+// "ret=<r> allocs= frees= creates= records= ewaits= swaits= cached= idle= dev= live= free= pending=
+// freed=": the backend's call counts, cached(), the idle events, the current device, and every
+// block by state as <id>:<device>:<class> (pending ones with :<event>:<owns_ev>), sorted by id
+static void pool_line(FakePool& pool, FakeState& f, const std::string& ret) {
+  const FakePool::Snapshot s = pool.snapshot();
+  std::lock_guard<std::mutex> g(f.mu);
+  printf("ret=%s allocs=%ld frees=%ld creates=%ld records=%ld ewaits=%ld swaits=%ld cached=%zu"
+         " idle=%zu dev=%d", ret.c_str(), f.allocs, f.frees, f.creates, f.records, f.ewaits,
+         f.swaits, s.cached, s.idle_events, FakeDev::cur);
+  const auto list = [&](const char* name, const std::vector<FakePool::Block>& v, bool ev) {
+    std::vector<std::string> out;
+    for (const auto& b : v) {
+      char buf[96];
+      int n = snprintf(buf, sizeof buf, "%06d:%d:%zu", f.ids.at(b.p), b.key.first, b.key.second);
+      if (ev) snprintf(buf + n, sizeof buf - (size_t)n, ":%d:%d", (int)(uintptr_t)b.ev, b.owns_ev ? 1 : 0);
+      out.push_back(buf);
+    }
+    std::sort(out.begin(), out.end());
+    printf(" %s=", name);
+    for (size_t i = 0; i < out.size(); ++i)    // (ids zero-padded for the sort, printed plain)
+      printf("%s%s", i ? "," : "", out[i].c_str() + out[i].find_first_not_of('0'));
+  };
+  list("live", s.live, false);
+  list("free", s.free, false);
+  list("pending", s.pending, true);
+  printf(" freed=");
+  for (size_t i = 0; i < f.freed.size(); ++i) printf("%s%d", i ? "," : "", f.freed[i]);
+  printf("\n");
+}
+
+static int cmd_block_pool(const char* path) {
+  std::ifstream in(path);
+  if (!in) { perror(path); return 2; }
+  std::vector<std::vector<std::string>> ops;
+  for (std::string line; std::getline(in, line);) {
+    std::istringstream is(line);
+    std::vector<std::string> a;
+    for (std::string w; is >> w;) a.push_back(w);
+    if (!a.empty()) ops.push_back(a);
+  }
+  kmhg::PoolKnobs kn;
+  size_t at = 0;
+  if (!ops.empty() && ops[0][0] == "knobs" && ops[0].size() == 3) {
+    kn.depth = (size_t)atoi(ops[0][1].c_str());
+    kn.best_fit = ops[0][2] != "0";
+    at = 1;
+  }
+  FakeState f;
+  FakePool pool(kn, FakeDev{&f});
+  std::map<std::string, void*> names;
+  std::vector<std::unique_ptr<FakeGroup>> groups;      // innermost last
+  char unknown = 0;
+  const auto stream = [](const std::string& w) { return reinterpret_cast<void*>((uintptr_t)atoi(w.c_str())); };
+  for (; at < ops.size(); ++at) {
+    const std::vector<std::string>& a = ops[at];
+    const std::string& op = a[0];
+    std::string ret = "-";
+    if (op == "dev" && a.size() == 2) {
+      FakeDev::cur = atoi(a[1].c_str());
+    } else if (op == "alloc" && a.size() == 3) {
+      try {
+        void* p = pool.alloc((size_t)strtoull(a[2].c_str(), nullptr, 10));
+        names[a[1]] = p;
+        std::lock_guard<std::mutex> g(f.mu);
+        ret = std::to_string(f.ids.at(p));
+      } catch (const FakeFailure& e) {
+        ret = e.st == kmhg::PoolAlloc::oom ? "oom" : "error:" + e.text;
+        std::replace(ret.begin(), ret.end(), ' ', '_');
+      }
+    } else if (op == "release" && (a.size() == 2 || a.size() == 3)) {
+      void* p = a[1] == "null" ? nullptr : a[1] == "unknown" ? (void*)&unknown : names.at(a[1]);
+      if (a.size() == 3) pool.release(p, stream(a[2]), true);
+      else pool.release(p);
+    } else if (op == "group_begin" && a.size() == 2) {
+      groups.push_back(std::make_unique<FakeGroup>(pool, stream(a[1])));
+    } else if (op == "synced" && !groups.empty()) {
+      groups.back()->synced = true;
+    } else if (op == "group_end" && !groups.empty()) {
+      groups.pop_back();
+    } else if (op == "complete" && a.size() == 2) {
+      std::lock_guard<std::mutex> g(f.mu);
+      f.done.at((size_t)atoi(a[1].c_str())) = 1;
+    } else if (op == "fail" && a.size() == 3) {
+      int* n = a[1] == "alloc-oom" ? &f.fail_oom : a[1] == "alloc-error" ? &f.fail_error
+               : a[1] == "event" ? &f.fail_event : a[1] == "record" ? &f.fail_record : nullptr;
+      if (!n) return 2;
+      *n = atoi(a[2].c_str());
+    } else if (op == "trim") {
+      pool.trim();
+    } else if (op == "cached") {
+      ret = std::to_string(pool.cached());
+    } else {
+      fprintf(stderr, "bad pool operation: %s\n", op.c_str());
+      return 2;
+    }
+    pool_line(pool, f, ret);
+  }
+  return 0;
+}
+
+static int cmd_block_pool_threads(int T, int nops) {
+  FakeState f;
+  f.blocking = true;
+  FakePool pool(kmhg::PoolKnobs{}, FakeDev{&f});
+  std::atomic<bool> stop{false};
+  std::atomic<int> bad{0};
+  std::thread completer([&] {
+    while (!stop) { f.complete_all(); std::this_thread::yield(); }
+  });
+  const size_t classes[3] = {200, 4096, (3u << 20) + 1};
+  std::vector<std::thread> th;
+  for (int t = 0; t < T; ++t)
+    th.emplace_back([&, t] {
+      uint64_t x = 1234 + (uint64_t)t;
+      FakeDev::cur = t & 1;
+      void* const s = reinterpret_cast<void*>((uintptr_t)(t + 1));
+      void* const other = reinterpret_cast<void*>((uintptr_t)(T + 1));
+      std::vector<char*> held;
+      const auto take = [&] {         // a block is this thread's alone: its first byte says so
+        char* p = static_cast<char*>(pool.alloc(classes[splitmix(x) % 3]));
+        *p = (char)t;
+        held.push_back(p);
+      };
+      const auto give = [&](void* stream, bool ordered) {
+        if (held.empty()) return;
+        const size_t i = splitmix(x) % held.size();
+        if (*held[i] != (char)t) ++bad;
+        pool.release(held[i], stream, ordered);
+        held.erase(held.begin() + (long)i);
+      };
+      for (int i = 0; i < nops; ++i) {
+        const uint64_t r = splitmix(x) % 8;
+        if (held.size() >= 8 || r == 3) give(nullptr, false);
+        else if (r < 3) take();
+        else if (r < 6) give(s, true);
+        else {                        // a group: a few of its stream's, one of another stream's
+          FakeGroup rg(pool, s);
+          take();
+          for (int j = 0; j < 3; ++j) give(s, true);
+          give(other, true);
+          rg.synced = r == 7 && (i & 1);
+        }
+      }
+      while (!held.empty()) give(nullptr, false);
+    });
+  for (auto& t : th) t.join();
+  stop = true;
+  completer.join();
+  f.complete_all();
+  pool.trim();
+  const FakePool::Snapshot s = pool.snapshot();
+  const bool clean = s.live.empty() && s.free.empty() && s.pending.empty() && s.cached == 0 &&
+                     f.ids.empty() && (long)f.freed.size() == f.next_id && !bad;
+  printf("%s blocks=%d live=%zu free=%zu pending=%zu unfreed=%zu bad=%d\n", clean ? "ok" : "bad",
+         f.next_id, s.live.size(), s.free.size(), s.pending.size(), f.ids.size(), bad.load());
+  return clean ? 0 : 1;
+}
+
 // ---------------------------------------------------------------------------- kmhg_reads.h
 // integers of argv[from ..), or of a comma-separated list, heap-allocated at their exact number
 static std::vector<int32_t> ints_of(int argc, char** argv, int from) {
@@ -494,6 +757,9 @@ int main(int argc, char** argv) {
   if (c == "pairs" && argc == 8 && atoi(argv[6]) > 0) return cmd_pairs(argv + 2, atoi(argv[6]), argv[7]);
   if (c == "pairs-split" && argc == 7) return cmd_pairs(argv + 2, 0, argv[6]);
   if (c == "pair-start" && argc == 3) return cmd_pair_start(argv[2]);
+  if (c == "pool" && argc == 3) return cmd_block_pool(argv[2]);
+  if (c == "pool" && argc == 5 && std::string(argv[2]) == "threads")
+    return cmd_block_pool_threads(atoi(argv[3]), atoi(argv[4]));
   if (c == "pool" && argc == 6)
     return cmd_pool(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]) != 0);
   if (c == "read-call" && argc >= 4) return cmd_read_call(argc, argv);
