@@ -1133,11 +1133,6 @@ __device__ __forceinline__ int lds_find_g(const GroupTableC& W, uint64_t key) {
 // BALLOT: repeated keys' windows ranked by ballots instead of the cursor atomic's lane order.
 // Every key must hash to this bucket: a stream entry that does not (an unstable pass moving
 // another bucket's window in) is reported like an LDS overflow.
-#ifndef KMHG_NO_NT_TABLE
-constexpr bool NT_TABLE = true;                // (-DKMHG_NO_NT_TABLE: plain stores, A/B)
-#else
-constexpr bool NT_TABLE = false;
-#endif
 struct Words3 {                                // three consecutive code words, 4-B aligned
   uint32_t a, b, c;
 };
@@ -1147,60 +1142,92 @@ struct Words3 {                                // three consecutive code words, 
 // same bytes V_diag_prep would write), and for every window of a repeated key its bit in `rep`
 // (u32 word (pos - 1) / 32, zeroed before the launch), so the first query runs V_diag_valid
 // alone (uniq = indexed windows AND NOT rep).
-template <bool COUNT_ONLY, bool CK, bool BALLOT, bool AOS = false, bool TAGS = false>
-__global__ void __launch_bounds__(BLOCK, BALLOT ? 4 : KMHG_BUCKET_WGS)
-k_v2_bucket_wg(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ pos,
-               const uint32_t* __restrict__ start, Geom g, Slot* __restrict__ T,
-               int32_t* __restrict__ positions, BucketStats* __restrict__ bstats,
-               BuildMeta* __restrict__ meta, const uint32_t* __restrict__ code, int k,
-               const uint32_t* __restrict__ n_ptr, uint32_t nw, uint8_t* __restrict__ TG,
-               uint32_t* __restrict__ rep, uint32_t place, uint32_t* __restrict__ place_ctr) {
-  static_assert(!(CK && COUNT_ONLY), "code-word keys belong to position builds");
-  static_assert(!(TAGS && (CK || COUNT_ONLY)), "build-time tags: key-stream position builds");
-  static_assert(!(AOS && (CK || COUNT_ONLY)), "packed streams carry keys and positions");
-  static_assert(V2_CAPW % BLOCK == 0, "the side slot V2_CAPW is slot q = V2_CAPW / TB of thread 0");
-  constexpr int TB = BLOCK;
-  constexpr int NW = TB / 64;                         // waves of the workgroup
-  __shared__ GroupTableC W;
-  __shared__ uint64_t sh[2 * NW];
-  __shared__ uint32_t red[2][NW];
-  const uint32_t b = blockIdx.x;
+// "Report the bucket as overflowed and leave" (`return bucket_fail(meta);`): a bucket range
+// outside the stream, a full table, a key of another bucket or a stream out of position order
+// are all reported alike, and the index is rebuilt by the global-atomic build.
+__device__ __forceinline__ void bucket_fail(BuildMeta* __restrict__ meta) {
+  if (threadIdx.x == 0) atomicOr(&meta->overflow, 1u);
+}
+
+// The kernel's phases, in the order k_v2_bucket_wg (below) runs them.  Barriers that separate
+// two phases stand in the kernel body; a phase's inner barriers are named in Lds.  Pass A by
+// placement alone stays in the kernel body: as a function it spills two VGPRs in the headline
+// instance (profiles/bucket_phases_resources.txt).  The LDS objects are static members, used by
+// name: through a reference they stay generic pointers until late in the compile.
+template <bool COUNT_ONLY, bool CK, bool BALLOT, bool AOS, bool TAGS>
+struct BucketPhases {
+#define PHASE static __device__ __forceinline__
+  static constexpr int TB = BLOCK;
+  static constexpr int NW = TB / 64;                  // waves of the workgroup
   // elements per thread per batch: 2x the mean (code words: 1.5x, for the VGPR budget of
   // 8 waves / SIMD); a larger bucket takes more batches
-  constexpr int PER = (CK ? 3 : 4) * V2_BW_WG / 2 / TB;
-  constexpr int EW = (PER + 1) & ~1;                  // edge row: PER positions, written as pairs
-  __shared__ __attribute__((aligned(16))) uint32_t edge[EW * NW + 1];   // stream-order check
-  constexpr uint32_t BATCH = TB * PER;
-  const int wave = threadIdx.x >> 6, lane = lane_id();
-  const uint32_t s0 = start[b], s1 = start[b + 1];
-  // a bucket range outside the stream (a bounds error) is reported like an overflow, never
-  // dereferenced: the index is rebuilt by the global-atomic build
-  if (s0 > s1 || s1 > *n_ptr) {
-    if (threadIdx.x == 0) atomicOr(&meta->overflow, 1u);
-    return;
-  }
-  const bool one_batch = s1 - s0 <= BATCH;
-  uint64_t key[PER];
-  uint32_t ps[PER];
-  int slot[PER];
+  static constexpr int PER = (CK ? 3 : 4) * V2_BW_WG / 2 / TB;
+  static constexpr int EW = (PER + 1) & ~1;           // edge row: PER positions, written as pairs
+  static constexpr uint32_t BATCH = TB * PER;
+  static constexpr uint32_t SPT = (V2_CAPW + 1 + TB - 1) / TB;   // slots per owner thread
+
+  // The workgroup's LDS: who writes each field, who reads it, and the barrier in between.
+  struct Lds {
+    // W: table_clear | barrier | pass A (placement or CAS: keys, val = counts) | pass A's
+    // verdict barrier | counts pass (val -> owner registers) | its __syncthreads_or | list
+    // offsets (val = offset, VAL_MULTI if repeated) | barrier | pass B (val = inline position or
+    // cursor) | barrier | write-out.  A placed bucket skips the counts and the offsets; its val
+    // holds group starts where no key landed.
+    static inline __shared__ GroupTableC W;
+    // sh[0, NW): the placement scan's per-wave record, then the list offsets' block scan (which
+    // ends in a barrier of its own).  sh[NW, 2 NW): the counts pass's per-wave pair sums, read
+    // with the bucket statistics after the offsets -- the upper half, so the scan in between
+    // leaves them be.
+    static inline __shared__ uint64_t sh[2 * NW];
+    // red[0]: the counts pass's keys per wave; red[1]: its maximum count per wave, both read
+    // with the bucket statistics behind the counts pass's barriers.  red[1] first carries the
+    // placement's per-wave verdict bits, read behind its last barrier; the counts pass of a
+    // fallen-back bucket writes it only after the CAS pass's verdict barrier.
+    static inline __shared__ uint32_t red[2][NW];
+    // edge (stream-order check; none in a count-only build): row `wave` holds that wave's
+    // lane-63 positions, EW per row, written and read as pairs -- a handful of LDS instructions
+    // per wave: single-lane LDS instructions cost nearly a full one each in this LDS-bound
+    // kernel.  order_write fills the rows and zeroes the verdict word edge[EW * NW]; pass A's
+    // verdict barrier; order_read sets the verdict.  It is consumed once per bucket, behind the
+    // first barrier after order_read: the counts pass's (CAS buckets) or pass B's (placed ones).
+    static inline __shared__ __attribute__((aligned(16))) uint32_t edge[EW * NW + 1];
+  };
+  struct Bucket {                                     // block-uniform, but wave and lane
+    uint32_t b, s0, s1;
+    int wave, lane;
+    __device__ bool one_batch() const { return s1 - s0 <= BATCH; }
+    __device__ bool chk() const { return !COUNT_ONLY && one_batch(); }
+  };
+  // A thread's elements of the current batch, in registers: each phase takes the arrays it
+  // reads and writes by reference (every index is a constant once the loops are unrolled).
+  using Keys = uint64_t[PER];                         // key[c]
+  using Words = uint32_t[PER];                        // ps[c]: positions; wa/wb/wc: code words (CK)
+  using Slots = int[PER];                             // slot[c]: the key's LDS slot, -1 if none
   // element c of thread t in a batch: i0 + c * TB + t, so position order = (c, wave, lane)
-  auto elem = [&](uint32_t i0, int c) { return i0 + (uint32_t)c * TB + threadIdx.x; };
-  uint32_t wa[PER], wb[PER], wc[PER];                 // CK: each window's three code words
-  bool ovf = false;                                   // LDS table full
-  bool disorder = false;                              // the bucket's stream out of position order
+  PHASE uint32_t elem(uint32_t i0, int c) {
+    return i0 + (uint32_t)c * TB + threadIdx.x;
+  }
+
+  PHASE void range(const uint32_t* __restrict__ start, Bucket& x) {
+    x.b = blockIdx.x;
+    x.wave = threadIdx.x >> 6;
+    x.lane = lane_id();
+    x.s0 = start[x.b];
+    x.s1 = start[x.b + 1];
+  }
+
   // CK: load() issues the positions, then the code words, all in flight at once; cut() turns
-  // them into keys -- after the table clear for the first batch, so the clear hides the loads
-  auto load = [&](uint32_t i0) {
+  // them into keys -- after the table clear for the first batch, so the clear hides the loads.
+  // A multi-batch bucket checks its stream order here, with a neighbour load per element.
+  PHASE void load(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ pos,
+                  const uint32_t* __restrict__ code, uint32_t nw, const Bucket& x, uint32_t i0,
+                  Keys& key, Words& ps, Words& wa, Words& wb, Words& wc, bool& disorder) {
     if (CK) {
 #pragma unroll
       for (int c = 0; c < PER; ++c) {
         const uint32_t i = elem(i0, c);
-#ifdef KMHG_EXP_NTLOAD
-        ps[c] = i < s1 ? __builtin_nontemporal_load(pos + i) : 1u;
-#else
-        ps[c] = i < s1 ? pos[i] : 1u;               // 1-based window start
-#endif
-        if (!one_batch) disorder |= stream_out_of_order(pos, i, s0, s1, ps[c]);
+        ps[c] = i < x.s1 ? pos[i] : 1u;             // 1-based window start
+        if (!x.one_batch()) disorder |= stream_out_of_order(pos, i, x.s0, x.s1, ps[c]);
       }
 #pragma unroll
       for (int c = 0; c < PER; ++c) {       // one 12-B load per window (global_load_dwordx3)
@@ -1217,66 +1244,72 @@ k_v2_bucket_wg(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ p
     for (int c = 0; c < PER; ++c) {
       const uint32_t i = elem(i0, c);
       if (AOS) {
-        const uint3 v = i < s1 ? reinterpret_cast<const uint3*>(keys)[i] : make_uint3(0u, 0u, 0u);
+        const uint3 v = i < x.s1 ? reinterpret_cast<const uint3*>(keys)[i] : make_uint3(0u, 0u, 0u);
         key[c] = ((uint64_t)v.y << 32) | v.x;
         ps[c] = v.z;
       } else {
-        key[c] = i < s1 ? keys[i] : 0;
-        ps[c] = (!COUNT_ONLY && i < s1) ? pos[i] : 0;
+        key[c] = i < x.s1 ? keys[i] : 0;
+        ps[c] = (!COUNT_ONLY && i < x.s1) ? pos[i] : 0;
       }
-      if (!COUNT_ONLY && i < s1 && ps[c] - 1u >= nw) disorder = true;   // outside [1, nw]
-      if (!COUNT_ONLY && !one_batch)
+      if (!COUNT_ONLY && i < x.s1 && ps[c] - 1u >= nw) disorder = true;   // outside [1, nw]
+      if (!COUNT_ONLY && !x.one_batch())
         disorder |= AOS ? stream_out_of_order<3>(reinterpret_cast<const uint32_t*>(keys) + 2, i,
-                                                  s0, s1, ps[c])
-                        : stream_out_of_order(pos, i, s0, s1, ps[c]);
+                                                    x.s0, x.s1, ps[c])
+                          : stream_out_of_order(pos, i, x.s0, x.s1, ps[c]);
     }
-  };
-  auto cut = [&](uint32_t i0) {
+  }
+  PHASE void cut(const Bucket& x, uint32_t i0, int k, Keys& key, const Words& ps, const Words& wa,
+                 const Words& wb, const Words& wc) {
     if (CK) {
 #pragma unroll
       for (int c = 0; c < PER; ++c)
-        key[c] = elem(i0, c) < s1 ? code_key(wa[c], wb[c], wc[c], (int64_t)ps[c] - 1, k) : 0;
+        key[c] = elem(i0, c) < x.s1
+                       ? code_key(wa[c], wb[c], wc[c], (int64_t)ps[c] - 1, k) : 0;
     }
-  };
-  STAMP_WG(b, 0);
-  load(s0);                                           // in flight while the table is cleared
-  for (uint32_t j = threadIdx.x; j <= V2_CAPW; j += TB) {
-    W.key[j] = EMPTY_KEY;
-    W.val[j] = 0u;
   }
-  __syncthreads();
-  cut(s0);
-  STAMP_WG(b, 1);
-  STAMP_WG_DRAIN(b, 6);
-  // Stream order of a one-batch bucket (multi-batch buckets check it with a neighbour load per
-  // element in load()): element (c, wave, lane) follows (c, wave, lane - 1) -- a DPP shift --
-  // and lane 0 follows lane 63 of the wave before (of row c - 1 for wave 0), exchanged through
-  // `edge` (order_write) and read after a barrier (order_read).  Both run after pass A, when the
-  // positions have long arrived, so the check makes no load wait earlier than it did.
-  const bool chk = !COUNT_ONLY && one_batch;
-  // (edge: row `wave` holds that wave's lane-63 positions, EW per row, written and read as
-  // pairs -- a handful of LDS instructions per wave: single-lane LDS instructions cost nearly a
-  // full one each in this LDS-bound kernel)
-  auto order_write = [&]() {
-    if (!chk) return;
-    if (threadIdx.x == 0) edge[EW * NW] = 0u;
+  // CK: positions in [1, nw] (checked after the cut: fewer live VGPRs)
+  PHASE void check_positions(const Bucket& x, uint32_t i0, uint32_t nw, const Words& ps,
+                             bool& disorder) {
+    if (CK) {
+#pragma unroll
+      for (int c = 0; c < PER; ++c)
+        if (elem(i0, c) < x.s1 && ps[c] - 1u >= nw) disorder = true;
+    }
+  }
+
+  PHASE void table_clear() {
+    for (uint32_t j = threadIdx.x; j <= V2_CAPW; j += TB) {
+      Lds::W.key[j] = EMPTY_KEY;
+      Lds::W.val[j] = 0u;
+    }
+  }
+
+  // Stream order of a one-batch bucket: element (c, wave, lane) follows (c, wave, lane - 1) -- a
+  // DPP shift -- and lane 0 follows lane 63 of the wave before (of row c - 1 for wave 0),
+  // exchanged through `edge` (order_write) and read after a barrier (order_read).  Both run
+  // after pass A, when the positions have long arrived, so the check makes no load wait earlier
+  // than it did.
+  PHASE void order_write(const Bucket& x, const Words& ps, bool& disorder) {
+    if (!x.chk()) return;
+    if (threadIdx.x == 0) Lds::edge[EW * NW] = 0u;
 #pragma unroll
     for (int c = 0; c < PER; ++c) {
       // lane - 1's position by a DPP wave shift (a VALU move; __shfl_up is an LDS permute)
       const uint32_t up = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)ps[c], 0x138 /* wave_shr:1 */,
                                                                 0xF, 0xF, false);
-      if (lane > 0 && elem(s0, c) < s1 && up >= ps[c]) disorder = true;
+      if (x.lane > 0 && elem(x.s0, c) < x.s1 && up >= ps[c]) disorder = true;
     }
-    if (lane == 63) {
+    if (x.lane == 63) {
 #pragma unroll
       for (int q = 0; q < PER; q += 2)
-        *reinterpret_cast<uint2*>(&edge[EW * wave + q]) = make_uint2(ps[q], q + 1 < PER ? ps[q + 1] : 0u);
+        *reinterpret_cast<uint2*>(&Lds::edge[EW * x.wave + q]) =
+            make_uint2(ps[q], q + 1 < PER ? ps[q + 1] : 0u);
     }
-  };
-  auto order_read = [&]() {
-    if (!(chk && lane == 0)) return;
+  }
+  PHASE void order_read(const Bucket& x, const Words& ps) {
+    if (!(x.chk() && x.lane == 0)) return;
     // lane 0 of wave w follows lane 63 of wave w - 1 (same row); wave 0 follows wave NW - 1
-    const uint32_t* row = edge + EW * (wave ? wave - 1 : NW - 1);
+    const uint32_t* row = Lds::edge + EW * (x.wave ? x.wave - 1 : NW - 1);
     uint32_t pv[PER + 1];
 #pragma unroll
     for (int q = 0; q < PER; q += 2) {
@@ -1287,12 +1320,233 @@ k_v2_bucket_wg(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ p
     bool bad = false;
 #pragma unroll
     for (int c = 0; c < PER; ++c) {
-      const uint32_t e = elem(s0, c);
-      const uint32_t prev = wave ? pv[c] : (c ? pv[c - 1] : 0u);   // wave 0: row c - 1
-      bad |= e > s0 && e < s1 && prev >= ps[c];
+      const uint32_t e = elem(x.s0, c);
+      const uint32_t prev = x.wave ? pv[c] : (c ? pv[c - 1] : 0u);   // wave 0: row c - 1
+      bad |= e > x.s0 && e < x.s1 && prev >= ps[c];
     }
-    if (bad) edge[EW * NW] = 1u;             // read after the next barrier
-  };
+    if (bad) Lds::edge[EW * NW] = 1u;           // read after the next barrier
+  }
+  PHASE bool order_verdict(const Bucket& x) {
+    return x.chk() && Lds::edge[EW * NW];
+  }
+  // pass A by CAS, one batch: distinct keys + counts (CAS on a table shared by the four waves).
+  // (Measured round 3, A/B in one run: letting the claiming occurrence skip the count add --
+  // counts pass adds 1 per occupied slot -- made the kernel 100 -> 142 us, as in round 2; and
+  // issuing the first CAS of all 8 elements of a lane back to back before resolving any,
+  // 98 -> 112 us.)
+  PHASE void pass_a_cas(const Bucket& x, Geom g, uint32_t nw, uint32_t i0, const Keys& key,
+                        const Words& ps, Slots& slot, bool& ovf, bool& disorder) {
+#pragma unroll
+    for (int c = 0; c < PER; ++c) {
+      slot[c] = -1;
+      if (elem(i0, c) < x.s1) {
+        // bucket membership (one multiply-high: CK keys are cut from the code words at the
+        // stream's positions, so this checks the positions too)
+        const uint64_t h = mix64(key[c]);
+        if (bucket_local(h, g) != x.b) disorder = true;
+        slot[c] = lds_insert_g(Lds::W, key[c], h);
+        if (slot[c] < 0) ovf = true;
+        else atomicAdd(&Lds::W.val[slot[c]], 1u);
+      }
+    }
+    check_positions(x, i0, nw, ps, disorder);
+  }
+
+  // counts: thread t owns slots t, t + TB, ... (lane-contiguous: conflict-free LDS; thread-
+  // contiguous runs of 6 slots ran 0.104 ms against 0.096 for the kernel).  Returns whether some
+  // key is repeated (block-uniform).
+  // The bucket's distinct keys by ballots (no cross-lane shuffles: each __shfl_xor is an LDS
+  // permute, in a kernel bound by its LDS instructions); the count maximum and the pairs only
+  // when some key is repeated, which the i.i.d. buckets of a large build almost never have.
+  PHASE bool counts(const Bucket& x, uint32_t (&cnt)[SPT], uint32_t& cs) {
+    uint32_t occ_w = 0;                      // wave-uniform
+    bool multi = false;
+#pragma unroll
+    for (uint32_t q = 0; q < SPT; ++q) {
+      const uint32_t j = q * TB + threadIdx.x;
+      const uint32_t c = j <= V2_CAPW ? Lds::W.val[j] : 0u;
+      cnt[q] = c;
+      cs += c;
+      multi |= c > 1;
+      occ_w += (uint32_t)__popcll(__ballot(c != 0));
+    }
+    if (x.lane == 0) Lds::red[0][x.wave] = occ_w;
+    const bool has_multi = __syncthreads_or(multi);
+    if (has_multi) {                         // block-uniform
+      uint32_t mx = 0;
+      uint64_t pairs = 0;
+#pragma unroll
+      for (uint32_t q = 0; q < SPT; ++q) {
+        mx = max(mx, cnt[q]);
+        pairs += (uint64_t)cnt[q] * (cnt[q] - (cnt[q] ? 1u : 0u)) / 2;
+      }
+      for (int d = 32; d >= 1; d >>= 1) {
+        pairs += __shfl_xor(pairs, d);
+        mx = max(mx, (uint32_t)__shfl_xor(mx, d));
+      }
+      if (x.lane == 0) {
+        Lds::red[1][x.wave] = mx;
+        Lds::sh[NW + x.wave] = pairs;
+      }
+      __syncthreads();
+    }
+    return has_multi;
+  }
+  // list offsets (only repeated keys have lists): any slot order gives each key a contiguous
+  // range of [s0, s1), here slot q * TB + t in (t, q) order
+  PHASE void list_offsets(const Bucket& x, const uint32_t (&cnt)[SPT], uint32_t cs) {
+    uint64_t tot;
+    uint32_t off_run = x.s0 + (uint32_t)block_excl_scan_n<NW>(cs, Lds::sh, tot);
+#pragma unroll
+    for (uint32_t q = 0; q < SPT; ++q) {
+      const uint32_t j = q * TB + threadIdx.x;
+      if (j <= V2_CAPW) Lds::W.val[j] = cnt[q] > 1 ? (VAL_MULTI | off_run) : off_run;
+      off_run += cnt[q];
+    }
+  }
+  // the bucket's statistics, from the counts pass's per-wave partials
+  PHASE void write_stats(const Bucket& x, bool placed, bool has_multi,
+                         BucketStats* __restrict__ bstats) {
+    if (threadIdx.x != 0) return;
+    BucketStats st;
+    st.n_kmers = 0;
+    st.max_count = 0;
+    st.n_pairs = 0;
+    if (placed) {                            // no repeated key: every window is a key
+      st.n_kmers = x.s1 - x.s0;
+      st.max_count = x.s1 > x.s0 ? 1u : 0u;
+      bstats[x.b] = st;
+      return;
+    }
+#pragma unroll
+    for (int w = 0; w < NW; ++w) st.n_kmers += Lds::red[0][w];
+    if (!has_multi) {
+      st.max_count = st.n_kmers ? 1u : 0u;
+    } else {
+#pragma unroll
+      for (int w = 0; w < NW; ++w) {
+        st.max_count = max(st.max_count, Lds::red[1][w]);
+        st.n_pairs += Lds::sh[NW + w];
+      }
+    }
+    bstats[x.b] = st;
+  }
+
+  // pass B, one batch whose slots are known.  Keys seen once keep their position inline (val) ...
+  PHASE void pass_b_inline(const Bucket& x, uint32_t i0, const Slots& slot, const Words& ps) {
+#pragma unroll
+    for (int c = 0; c < PER; ++c)
+      if (elem(i0, c) < x.s1) Lds::W.val[slot[c]] = ps[c];
+  }
+  // ... repeated keys are ranked in position order, the waves taking turns so that wave w
+  // follows waves < w (a barrier per turn)
+  PHASE void pass_b_rank(const Bucket& x, uint32_t i0, const Slots& slot, const Words& ps,
+                         int32_t* __restrict__ positions, uint32_t* __restrict__ rep) {
+    for (int c = 0; c < PER; ++c) {
+      const bool act = elem(i0, c) < x.s1;
+      // waves take turns on this c: wave w ranks after waves < w have advanced the cursors
+      for (int turn = 0; turn < NW; ++turn) {
+        if (x.wave == turn) {
+          const uint32_t v = act ? Lds::W.val[slot[c]] : 0u;
+          const bool multi = act && (v & VAL_MULTI);
+          if (act && !multi) Lds::W.val[slot[c]] = ps[c];
+          if (!BALLOT) {
+            // the cursor atomic's lane-ordered returns rank the wave's windows of one key
+            if (multi) {
+              const uint32_t at = atomicAdd(&Lds::W.val[slot[c]], 1u) & ~VAL_MULTI;
+              positions[at] = (int32_t)ps[c];
+              if (TAGS) atomicOr(&rep[(ps[c] - 1u) >> 5], 1u << ((ps[c] - 1u) & 31u));
+            }
+          } else if (__ballot(multi)) {
+            const uint64_t m = match_bits((uint32_t)slot[c], V2_SLOT_BITS_WG, multi);
+            const int leader = multi ? __ffsll((unsigned long long)m) - 1 : x.lane;
+            if (multi && leader == x.lane) Lds::W.val[slot[c]] = v + (uint32_t)__popcll(m);
+            const uint32_t cur = (uint32_t)__shfl((int)v, leader) & ~VAL_MULTI;
+            if (multi) positions[cur + (uint32_t)__popcll(m & lanemask_lt())] = (int32_t)ps[c];
+            if (TAGS && multi) atomicOr(&rep[(ps[c] - 1u) >> 5], 1u << ((ps[c] - 1u) & 31u));
+          }
+        }
+        __syncthreads();
+      }
+    }
+  }
+
+  // the bucket's sub-table, coalesced 16-B slots, counts from the registers of the slot's owner
+  // (a placed bucket had no counts pass: every occupied slot counts 1, taken from the key)
+  PHASE void write_table(const Bucket& x, bool placed, const uint32_t (&cnt)[SPT],
+                         Slot* __restrict__ T, uint8_t* __restrict__ TG) {
+    Slot* Tb = T + (uint64_t)x.b * V2_CAPW;
+#pragma unroll
+    for (uint32_t q = 0; q < SPT; ++q) {
+      const uint32_t j = q * TB + threadIdx.x;
+      if (j < V2_CAPW) {
+        const uint64_t kk = Lds::W.key[j];
+        // placed: val holds the group starts where no key landed
+        const uint32_t cq = placed ? (kk != EMPTY_KEY ? 1u : 0u) : cnt[q];
+        const uint32_t aux = COUNT_ONLY ? 0u : (placed && kk == EMPTY_KEY) ? 0u : (Lds::W.val[j] & ~VAL_MULTI);
+        if (CK) {
+          // code-word keys: the table streams past the L2 (nontemporal), which keeps the code
+          // words every bucket gathers from resident there
+          typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+          const u32x4 sv = {(uint32_t)kk, (uint32_t)(kk >> 32), cq, aux};
+          __builtin_nontemporal_store(sv, reinterpret_cast<u32x4*>(&Tb[j]));
+        } else {
+          *reinterpret_cast<uint4*>(&Tb[j]) = make_uint4((uint32_t)kk, (uint32_t)(kk >> 32), cq, aux);
+        }
+        if (TAGS)      // one byte per slot: 64 consecutive bytes per wave and row q
+          TG[(uint64_t)x.b * V2_CAPW + j] = kk == EMPTY_KEY ? (uint8_t)0 : slot_tag(mix64(kk));
+      }
+    }
+  }
+  PHASE void write_side(const Bucket& x, Geom g, bool placed, uint32_t n_real,
+                        const uint32_t (&cnt)[SPT], Slot* __restrict__ T) {
+    if (threadIdx.x == 0 && side_bucket(x.b, g)) {
+      // (placed: the windows that are not among the table's keys hold the sentinel key)
+      const uint2 c = make_uint2(placed ? x.s1 - x.s0 - n_real : cnt[V2_CAPW / TB],
+                                 COUNT_ONLY ? 0u : (Lds::W.val[V2_CAPW] & ~VAL_MULTI));
+      *reinterpret_cast<uint4*>(&T[side_slot(g)]) = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, c.x, c.y);
+    }
+  }
+#undef PHASE
+};
+
+template <bool COUNT_ONLY, bool CK, bool BALLOT, bool AOS = false, bool TAGS = false>
+__global__ void __launch_bounds__(BLOCK, BALLOT ? 4 : KMHG_BUCKET_WGS)
+k_v2_bucket_wg(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ pos,
+               const uint32_t* __restrict__ start, Geom g, Slot* __restrict__ T,
+               int32_t* __restrict__ positions, BucketStats* __restrict__ bstats,
+               BuildMeta* __restrict__ meta, const uint32_t* __restrict__ code, int k,
+               const uint32_t* __restrict__ n_ptr, uint32_t nw, uint8_t* __restrict__ TG,
+               uint32_t* __restrict__ rep, uint32_t place, uint32_t* __restrict__ place_ctr) {
+  static_assert(!(CK && COUNT_ONLY), "code-word keys belong to position builds");
+  static_assert(!(TAGS && (CK || COUNT_ONLY)), "build-time tags: key-stream position builds");
+  static_assert(!(AOS && (CK || COUNT_ONLY)), "packed streams carry keys and positions");
+  static_assert(V2_CAPW % BLOCK == 0, "the side slot V2_CAPW is slot q = V2_CAPW / TB of thread 0");
+  using P = BucketPhases<COUNT_ONLY, CK, BALLOT, AOS, TAGS>;
+  constexpr int TB = P::TB, NW = P::NW, PER = P::PER;
+  constexpr uint32_t BATCH = P::BATCH;
+  using S = typename P::Lds;
+  typename P::Bucket x;
+  P::range(start, x);
+  const uint32_t b = x.b, s0 = x.s0, s1 = x.s1;
+  const int wave = x.wave, lane = x.lane;
+  // a bucket range outside the stream (a bounds error) is never dereferenced
+  if (s0 > s1 || s1 > *n_ptr) return bucket_fail(meta);
+  const bool one_batch = x.one_batch();
+  uint64_t key[PER];
+  uint32_t ps[PER];
+  int slot[PER];
+  uint32_t wa[PER], wb[PER], wc[PER];                 // CK: each window's three code words
+  bool ovf = false;                                   // LDS table full
+  bool disorder = false;                              // the bucket's stream out of position order
+  STAMP_WG(b, 0);
+  // the first batch: its loads are in flight while the table is cleared
+  P::load(keys, pos, code, nw, x, s0, key, ps, wa, wb, wc, disorder);
+  P::table_clear();
+  __syncthreads();
+  P::cut(x, s0, k, key, ps, wa, wb, wc);
+  STAMP_WG(b, 1);
+  STAMP_WG_DRAIN(b, 6);
   // pass A by placement (one-batch position buckets): a linear-probing layout is fixed by how
   // many keys have each home slot, so a bucket WITHOUT a repeated key -- every bucket of an
   // i.i.d. sequence -- needs no find-or-insert: one u32 LDS add per element counts the keys of
@@ -1315,7 +1569,7 @@ k_v2_bucket_wg(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ p
   if (CK && one_batch && place) {
     constexpr uint32_t HB = V2_SLOT_BITS_WG, HM = (1u << HB) - 1u;
     constexpr uint32_t HPT = V2_CAPW / TB;            // homes per thread
-    static_assert(HPT % 2 == 0 && (sizeof(W.key) % 8) == 0, "the scan reads counts as pairs");
+    static_assert(HPT % 2 == 0 && (sizeof(S::W.key) % 8) == 0, "the scan reads counts as pairs");
     static_assert(BATCH < (1u << (32 - HB - 1)), "(home, rank) packs into slot[c]");
     constexpr uint32_t CROWD = 8, OFF = 2048;         // OFF >= BATCH keeps j + OFF - S(j) >= 0
     static_assert(BATCH <= OFF && V2_CAPW + OFF < 0x10000u, "the scan's per-wave record: 16-bit fields");
@@ -1323,26 +1577,22 @@ k_v2_bucket_wg(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ p
 #pragma unroll
     for (int c = 0; c < PER; ++c) {
       slot[c] = -1;
-      if (elem(s0, c) < s1) {
+      if (P::elem(s0, c) < s1) {
         const uint64_t h = mix64(key[c]);
         if (bucket_local(h, g) != b) disorder = true;
         if (key[c] == EMPTY_KEY) {                    // the side slot holds one key
-          rpt |= atomicAdd(&W.val[V2_CAPW], 1u) != 0u;
+          rpt |= atomicAdd(&S::W.val[V2_CAPW], 1u) != 0u;
           slot[c] = (int)V2_CAPW;
         } else {
           const uint32_t home = local_home(h, V2_CAPW);
-          slot[c] = (int)(home | (atomicAdd(&W.val[home], 1u) << HB));
+          slot[c] = (int)(home | (atomicAdd(&S::W.val[home], 1u) << HB));
         }
       }
     }
-    if (CK) {
-#pragma unroll
-      for (int c = 0; c < PER; ++c)
-        if (elem(s0, c) < s1 && ps[c] - 1u >= nw) disorder = true;
-    }
+    P::check_positions(x, s0, nw, ps, disorder);
     __syncthreads();
     uint32_t cn[HPT];
-    uint2* vp = reinterpret_cast<uint2*>(&W.val[HPT * threadIdx.x]);
+    uint2* vp = reinterpret_cast<uint2*>(&S::W.val[HPT * threadIdx.x]);
 #pragma unroll
     for (uint32_t i = 0; i < HPT; i += 2) {
       const uint2 v = vp[i / 2];
@@ -1363,13 +1613,13 @@ k_v2_bucket_wg(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ p
     const uint32_t mex = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)minc, 0x138 /* wave_shr:1 */,
                                                                0xF, 0xF, false);
     const bool wcrowd = __ballot(crowded) != 0;
-    if (lane == 63) sh[wave] = (uint64_t)inc | ((uint64_t)minc << 16) | ((uint64_t)wcrowd << 32);
+    if (lane == 63) S::sh[wave] = (uint64_t)inc | ((uint64_t)minc << 16) | ((uint64_t)wcrowd << 32);
     __syncthreads();
     int wbase = 0, Mw = 0, Mall = 0, ntot = 0;
     bool crowd = false;
 #pragma unroll
     for (int w = 0; w < NW; ++w) {
-      const uint64_t x = sh[w];
+      const uint64_t x = S::sh[w];
       const int G = (int)((uint32_t)(x >> 16) & 0xFFFFu) - (int)OFF - ntot;
       if (w < wave) {
         Mw = max(Mw, G);
@@ -1398,23 +1648,23 @@ k_v2_bucket_wg(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ p
       __syncthreads();
 #pragma unroll
       for (int c = 0; c < PER; ++c) {
-        if (elem(s0, c) < s1 && slot[c] != (int)V2_CAPW) {
+        if (P::elem(s0, c) < s1 && slot[c] != (int)V2_CAPW) {
           const uint32_t r = (uint32_t)slot[c] >> HB;
-          uint32_t j = W.val[(uint32_t)slot[c] & HM] + r;
+          uint32_t j = S::W.val[(uint32_t)slot[c] & HM] + r;
           if (j >= V2_CAPW) j -= V2_CAPW;
-          W.key[j] = key[c];
+          S::W.key[j] = key[c];
           slot[c] = (int)(j | (r << HB));
         }
       }
-      order_write();
+      P::order_write(x, ps, disorder);
       __syncthreads();
 #pragma unroll
       for (int c = 0; c < PER; ++c) {
-        if (elem(s0, c) < s1) {
+        if (P::elem(s0, c) < s1) {
           const uint32_t r = (uint32_t)slot[c] >> HB, j = (uint32_t)slot[c] & HM;
           uint32_t q = j >= r ? j - r : j + V2_CAPW - r;   // the group's first slot
           for (uint32_t i = 0; i < r; ++i) {          // r < CROWD; addresses known up front
-            rpt |= W.key[q] == key[c];
+            rpt |= S::W.key[q] == key[c];
             if (++q == V2_CAPW) q = 0;
           }
           slot[c] = (int)j;
@@ -1422,267 +1672,71 @@ k_v2_bucket_wg(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ p
       }
       // one reduction for both verdicts: bit 0 a repeated key, bit 1 a stream error
       const uint32_t wf = (__ballot(rpt) ? 1u : 0u) | (__ballot(ovf || disorder) ? 2u : 0u);
-      if (lane == 0) red[1][wave] = wf;
+      if (lane == 0) S::red[1][wave] = wf;
       __syncthreads();
       uint32_t bf = 0;
 #pragma unroll
-      for (int w = 0; w < NW; ++w) bf |= red[1][w];
-      if (bf & 2u) {
-        if (threadIdx.x == 0) atomicOr(&meta->overflow, 1u);
-        return;
-      }
+      for (int w = 0; w < NW; ++w) bf |= S::red[1][w];
+      if (bf & 2u) return bucket_fail(meta);
       if (!(bf & 1u)) {
         placed = true;
         which = 0;
-        order_read();
+        P::order_read(x, ps);
       }
     }
     if (!placed) {                                    // nobody reads the table past the barriers above
-      for (uint32_t j = threadIdx.x; j <= V2_CAPW; j += TB) {
-        W.key[j] = EMPTY_KEY;
-        W.val[j] = 0u;
-      }
+      P::table_clear();
       __syncthreads();
     }
     // test build only: buckets placed / fallen back for a repeat / for a second wrap
     if (place_ctr && threadIdx.x == 0) atomicAdd(&place_ctr[which], 1u);
   }
-  // pass A: distinct keys + counts (CAS on a table shared by the four waves).  (Measured round
-  // 3, A/B in one run: letting the claiming occurrence skip the count add -- counts pass adds 1
-  // per occupied slot -- made the kernel 100 -> 142 us, as in round 2; and issuing the first
-  // CAS of all 8 elements of a lane back to back before resolving any, 98 -> 112 us.)
+  // pass A by CAS, batch by batch (none if the bucket was placed)
   for (uint32_t i0 = s0; i0 < (placed ? s0 : s1); i0 += BATCH) {
-    if (i0 != s0) { load(i0); cut(i0); }
-#pragma unroll
-    for (int c = 0; c < PER; ++c) {
-      slot[c] = -1;
-      if (elem(i0, c) < s1) {
-        // bucket membership (one multiply-high: CK keys are cut from the code words at the
-        // stream's positions, so this checks the positions too)
-        const uint64_t h = mix64(key[c]);
-        if (bucket_local(h, g) != b) disorder = true;
-        slot[c] = lds_insert_g(W, key[c], h);
-        if (slot[c] < 0) ovf = true;
-        else atomicAdd(&W.val[slot[c]], 1u);
-      }
+    if (i0 != s0) {
+      P::load(keys, pos, code, nw, x, i0, key, ps, wa, wb, wc, disorder);
+      P::cut(x, i0, k, key, ps, wa, wb, wc);
     }
-    if (CK) {                      // positions in [1, nw] (checked after the cut: fewer live VGPRs)
-#pragma unroll
-      for (int c = 0; c < PER; ++c)
-        if (elem(i0, c) < s1 && ps[c] - 1u >= nw) disorder = true;
-    }
+    P::pass_a_cas(x, g, nw, i0, key, ps, slot, ovf, disorder);
   }
   if (!placed) {
-    order_write();
-    if (__syncthreads_or(ovf || disorder)) {
-      if (threadIdx.x == 0) atomicOr(&meta->overflow, 1u);
-      return;
-    }
-    order_read();                            // its verdict: read after the counts pass's barrier
+    P::order_write(x, ps, disorder);
+    if (__syncthreads_or(ovf || disorder)) return bucket_fail(meta);
+    P::order_read(x, ps);              // its verdict: read after the counts pass's barrier
   }
   STAMP_WG(b, 2);
-  // counts: thread t owns slots t, t + TB, ... (lane-contiguous: conflict-free LDS; thread-
-  // contiguous runs of 6 slots ran 0.104 ms against 0.096 for the kernel)
-  constexpr uint32_t SPT = (V2_CAPW + 1 + TB - 1) / TB;
-  // (a placed bucket has no counts pass: every occupied slot counts 1, taken from the key at
-  // the write-out)
+  constexpr uint32_t SPT = P::SPT;
   uint32_t cnt[SPT];
   uint32_t cs = 0;
   bool has_multi = false;
   if (!placed) {
-#ifndef KMHG_NO_LEAN_COUNTS
-  // The bucket's distinct keys by ballots (no cross-lane shuffles: each __shfl_xor is an LDS
-  // permute, in a kernel bound by its LDS instructions); the count maximum and the pairs only
-  // when some key is repeated, which the i.i.d. buckets of a large build almost never have.
-  uint32_t occ_w = 0;                      // wave-uniform
-  bool multi = false;
-#pragma unroll
-  for (uint32_t q = 0; q < SPT; ++q) {
-    const uint32_t j = q * TB + threadIdx.x;
-    const uint32_t c = j <= V2_CAPW ? W.val[j] : 0u;
-    cnt[q] = c;
-    cs += c;
-    multi |= c > 1;
-    occ_w += (uint32_t)__popcll(__ballot(c != 0));
+    has_multi = P::counts(x, cnt, cs);
+    // stream out of order at a wave / row boundary
+    if (P::order_verdict(x)) return bucket_fail(meta);
   }
-  if (lane == 0) red[0][wave] = occ_w;
-  has_multi = __syncthreads_or(multi);
-  if (has_multi) {                         // block-uniform
-    uint32_t mx = 0;
-    uint64_t pairs = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < SPT; ++q) {
-      mx = max(mx, cnt[q]);
-      pairs += (uint64_t)cnt[q] * (cnt[q] - (cnt[q] ? 1u : 0u)) / 2;
-    }
-    for (int d = 32; d >= 1; d >>= 1) {
-      pairs += __shfl_xor(pairs, d);
-      mx = max(mx, (uint32_t)__shfl_xor(mx, d));
-    }
-    if (lane == 0) {
-      red[1][wave] = mx;
-      sh[NW + wave] = pairs;               // sh[NW..2NW): the block scan below uses sh[0..NW)
-    }
-    __syncthreads();
-  }
-#else
-  uint32_t occ = 0, mx = 0;
-  uint64_t pairs = 0;
-#pragma unroll
-  for (uint32_t q = 0; q < SPT; ++q) {
-    const uint32_t j = q * TB + threadIdx.x;
-    const uint32_t c = j <= V2_CAPW ? W.val[j] : 0u;
-    cnt[q] = c;
-    cs += c;
-    occ += c ? 1u : 0u;
-    mx = max(mx, c);
-    pairs += (uint64_t)c * (c - (c ? 1u : 0u)) / 2;
-  }
-  for (int d = 32; d >= 1; d >>= 1) {
-    pairs += __shfl_xor(pairs, d);
-    occ += __shfl_xor(occ, d);
-    mx = max(mx, (uint32_t)__shfl_xor(mx, d));
-  }
-  if (lane == 0) {
-    red[0][wave] = occ;
-    red[1][wave] = mx;
-    sh[NW + wave] = pairs;                 // sh[NW..2NW): the block scan below uses sh[0..NW)
-  }
-  has_multi = __syncthreads_or(mx > 1);
-#endif
-  if (chk && edge[EW * NW]) {                // stream out of order at a wave / row boundary
-    if (threadIdx.x == 0) atomicOr(&meta->overflow, 1u);
-    return;
-  }
-  }
-  // list offsets (only repeated keys have lists): any slot order gives each key a contiguous
-  // range of [s0, s1), here slot q * TB + t in (t, q) order
   if (!COUNT_ONLY && has_multi) {
-    uint64_t tot;
-    uint32_t off_run = s0 + (uint32_t)block_excl_scan_n<NW>(cs, sh, tot);
-#pragma unroll
-    for (uint32_t q = 0; q < SPT; ++q) {
-      const uint32_t j = q * TB + threadIdx.x;
-      if (j <= V2_CAPW) W.val[j] = cnt[q] > 1 ? (VAL_MULTI | off_run) : off_run;
-      off_run += cnt[q];
-    }
+    P::list_offsets(x, cnt, cs);
     __syncthreads();
   }
   STAMP_WG(b, 3);
-  if (threadIdx.x == 0) {
-    BucketStats st;
-    st.n_kmers = 0;
-    st.max_count = 0;
-    st.n_pairs = 0;
-    if (placed) {                          // no repeated key: every window is a key
-      st.n_kmers = s1 - s0;
-      st.max_count = s1 > s0 ? 1u : 0u;
-      bstats[b] = st;
-    } else {
-#pragma unroll
-    for (int w = 0; w < NW; ++w) st.n_kmers += red[0][w];
-#ifndef KMHG_NO_LEAN_COUNTS
-    if (!has_multi) {
-      st.max_count = st.n_kmers ? 1u : 0u;
-    } else
-#endif
-    {
-#pragma unroll
-      for (int w = 0; w < NW; ++w) {
-        st.max_count = max(st.max_count, red[1][w]);
-        st.n_pairs += sh[NW + w];
-      }
-    }
-    bstats[b] = st;
-    }
-  }
-  // pass B: keys seen once keep their position inline (val); repeated keys are ranked in
-  // position order, the waves taking turns so that wave w follows waves < w
+  P::write_stats(x, placed, has_multi, bstats);
+  // pass B, batch by batch
   for (uint32_t i0 = s0; i0 < (COUNT_ONLY ? s0 : s1); i0 += BATCH) {
     if (!one_batch) {
-      load(i0);
-      cut(i0);
+      P::load(keys, pos, code, nw, x, i0, key, ps, wa, wb, wc, disorder);
+      P::cut(x, i0, k, key, ps, wa, wb, wc);
 #pragma unroll
-      for (int c = 0; c < PER; ++c) slot[c] = elem(i0, c) < s1 ? lds_find_g(W, key[c]) : -1;
+      for (int c = 0; c < PER; ++c) slot[c] = P::elem(i0, c) < s1 ? lds_find_g(S::W, key[c]) : -1;
     }
-    if (!has_multi) {                    // every key seen once: positions go inline
-#pragma unroll
-      for (int c = 0; c < PER; ++c)
-        if (elem(i0, c) < s1) W.val[slot[c]] = ps[c];
-      continue;
-    }
-    for (int c = 0; c < PER; ++c) {
-      const bool act = elem(i0, c) < s1;
-      // waves take turns on this c: wave w ranks after waves < w have advanced the cursors
-      for (int turn = 0; turn < NW; ++turn) {
-        if (wave == turn) {
-          const uint32_t v = act ? W.val[slot[c]] : 0u;
-          const bool multi = act && (v & VAL_MULTI);
-          if (act && !multi) W.val[slot[c]] = ps[c];
-          if (!BALLOT) {
-            // the cursor atomic's lane-ordered returns rank the wave's windows of one key
-            if (multi) {
-              const uint32_t at = atomicAdd(&W.val[slot[c]], 1u) & ~VAL_MULTI;
-              positions[at] = (int32_t)ps[c];
-              if (TAGS) atomicOr(&rep[(ps[c] - 1u) >> 5], 1u << ((ps[c] - 1u) & 31u));
-            }
-          } else if (__ballot(multi)) {
-            const uint64_t m = match_bits((uint32_t)slot[c], V2_SLOT_BITS_WG, multi);
-            const int leader = multi ? __ffsll((unsigned long long)m) - 1 : lane;
-            if (multi && leader == lane) W.val[slot[c]] = v + (uint32_t)__popcll(m);
-            const uint32_t cur = (uint32_t)__shfl((int)v, leader) & ~VAL_MULTI;
-            if (multi) positions[cur + (uint32_t)__popcll(m & lanemask_lt())] = (int32_t)ps[c];
-            if (TAGS && multi) atomicOr(&rep[(ps[c] - 1u) >> 5], 1u << ((ps[c] - 1u) & 31u));
-          }
-        }
-        __syncthreads();
-      }
-    }
+    if (!has_multi) P::pass_b_inline(x, i0, slot, ps);   // every key seen once
+    else P::pass_b_rank(x, i0, slot, ps, positions, rep);
   }
   __syncthreads();
-  if (placed && chk && edge[EW * NW]) {      // (placed: order_read's verdict, behind pass B's barrier)
-    if (threadIdx.x == 0) atomicOr(&meta->overflow, 1u);
-    return;
-  }
+  // (placed: order_read's verdict, behind pass B's barrier)
+  if (placed && P::order_verdict(x)) return bucket_fail(meta);
   STAMP_WG(b, 4);
-  // the bucket's sub-table, coalesced 16-B slots, counts from the registers of the slot's owner
-  Slot* Tb = T + (uint64_t)b * V2_CAPW;
-#ifdef KMHG_EXP_SLOT8
-  // EXPERIMENT ONLY (timing variant, wrong tables): the write-out of 8-B {count, aux} slots
-  uint2* T8 = reinterpret_cast<uint2*>(T) + (uint64_t)b * V2_CAPW;
-#pragma unroll
-  for (uint32_t q = 0; q < SPT; ++q) {
-    const uint32_t j = q * TB + threadIdx.x;
-    if (j < V2_CAPW) T8[j] = make_uint2(cnt[q], COUNT_ONLY ? 0u : (W.val[j] & ~VAL_MULTI));
-  }
-#else
-#pragma unroll
-  for (uint32_t q = 0; q < SPT; ++q) {
-    const uint32_t j = q * TB + threadIdx.x;
-    if (j < V2_CAPW) {
-      const uint64_t kk = W.key[j];
-      // placed: val holds the group starts where no key landed
-      const uint32_t cq = placed ? (kk != EMPTY_KEY ? 1u : 0u) : cnt[q];
-      const uint32_t aux = COUNT_ONLY ? 0u : (placed && kk == EMPTY_KEY) ? 0u : (W.val[j] & ~VAL_MULTI);
-      if (CK && NT_TABLE) {
-        // code-word keys: the table streams past the L2 (nontemporal), which keeps the code
-        // words every bucket gathers from resident there
-        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-        const u32x4 sv = {(uint32_t)kk, (uint32_t)(kk >> 32), cq, aux};
-        __builtin_nontemporal_store(sv, reinterpret_cast<u32x4*>(&Tb[j]));
-      } else {
-        *reinterpret_cast<uint4*>(&Tb[j]) = make_uint4((uint32_t)kk, (uint32_t)(kk >> 32), cq, aux);
-      }
-      if (TAGS)      // one byte per slot: 64 consecutive bytes per wave and row q
-        TG[(uint64_t)b * V2_CAPW + j] = kk == EMPTY_KEY ? (uint8_t)0 : slot_tag(mix64(kk));
-    }
-  }
-#endif
-  if (threadIdx.x == 0 && side_bucket(b, g)) {
-    // (placed: the windows that are not among the table's keys hold the sentinel key)
-    const uint2 c = make_uint2(placed ? s1 - s0 - n_real : cnt[V2_CAPW / TB], COUNT_ONLY ? 0u : (W.val[V2_CAPW] & ~VAL_MULTI));
-    *reinterpret_cast<uint4*>(&T[side_slot(g)]) = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, c.x, c.y);
-  }
+  P::write_table(x, placed, cnt, T, TG);
+  P::write_side(x, g, placed, n_real, cnt, T);
   STAMP_WG(b, 5);
 }
 
@@ -1996,6 +2050,10 @@ void launch_v2_scatter(const ScatterIn& in, StreamFmt fin, StreamFmt fout, void*
   }
 #undef KMHG_PASS
 }
+// a bucket kernel instance's switches <COUNT_ONLY, CK, BALLOT, AOS, TAGS> as one number
+static constexpr int bucket_inst(bool co, bool ck, bool bal, bool aos, bool tags) {
+  return co * 16 + ck * 8 + bal * 4 + aos * 2 + tags;
+}
 void launch_v2_bucket_wg(StreamFmt fmt, const void* keys_, const uint32_t* pos,
                          const uint32_t* start, Geom g, Slot* T, int32_t* positions,
                          BucketStats* bstats, BuildMeta* meta, hipStream_t s,
@@ -2007,22 +2065,29 @@ void launch_v2_bucket_wg(StreamFmt fmt, const void* keys_, const uint32_t* pos,
   const bool ballot = ballot_ranks();
   const bool tags = TG != nullptr && !count_only && !code;
   const dim3 gr(g.nb), bl(BLOCK);
-#define KMHG_BUCKET(CO, CKK, BAL, AO, TG_)                                                     \
-  hipLaunchKernelGGL((k_v2_bucket_wg<CO, CKK, BAL, AO, TG_>), gr, bl, 0, s, keys, pos, start, g, \
-                     T, positions, bstats, meta, CKK ? code : nullptr, CKK ? k : 0, n_ptr, nw,   \
-                     TG, rep, place ? 1u : 0u, place_ctr)
-  if (aos && tags)
-    { if (ballot) KMHG_BUCKET(false, false, true, true, true); else KMHG_BUCKET(false, false, false, true, true); }
-  else if (aos)
-    { if (ballot) KMHG_BUCKET(false, false, true, true, false); else KMHG_BUCKET(false, false, false, true, false); }
-  else if (count_only)              // no positions: nothing is ranked
+  // (count-only: no positions, so nothing is ranked, packed or tagged)
+  const int inst = count_only ? bucket_inst(true, false, false, false, false)
+                              : bucket_inst(false, code != nullptr, ballot, aos, tags);
+#define KMHG_BUCKET(CO, CKK, BAL, AO, TG_)                                                       \
+  case bucket_inst(CO, CKK, BAL, AO, TG_):                                                       \
+    hipLaunchKernelGGL((k_v2_bucket_wg<CO, CKK, BAL, AO, TG_>), gr, bl, 0, s, keys, pos, start,  \
+                       g, T, positions, bstats, meta, CKK ? code : nullptr, CKK ? k : 0, n_ptr,  \
+                       nw, TG, rep, place ? 1u : 0u, place_ctr);                                 \
+    break
+  switch (inst) {
     KMHG_BUCKET(true, false, false, false, false);
-  else if (code)
-    { if (ballot) KMHG_BUCKET(false, true, true, false, false); else KMHG_BUCKET(false, true, false, false, false); }
-  else if (tags)
-    { if (ballot) KMHG_BUCKET(false, false, true, false, true); else KMHG_BUCKET(false, false, false, false, true); }
-  else
-    { if (ballot) KMHG_BUCKET(false, false, true, false, false); else KMHG_BUCKET(false, false, false, false, false); }
+    KMHG_BUCKET(false, true, false, false, false);
+    KMHG_BUCKET(false, true, true, false, false);
+    KMHG_BUCKET(false, false, false, false, false);
+    KMHG_BUCKET(false, false, true, false, false);
+    KMHG_BUCKET(false, false, false, false, true);
+    KMHG_BUCKET(false, false, true, false, true);
+    KMHG_BUCKET(false, false, false, true, false);
+    KMHG_BUCKET(false, false, true, true, false);
+    KMHG_BUCKET(false, false, false, true, true);
+    KMHG_BUCKET(false, false, true, true, true);
+    default: std::abort();     // code words with a packed stream or tags: no such build
+  }
 #undef KMHG_BUCKET
 }
 // The hardware property the radix passes' ranks rest on, checked on the device itself

@@ -130,6 +130,18 @@ def test_ballot_variant(gpu, test_lib, monkeypatch):
     _all_modes(monkeypatch, rr.tobytes().decode("latin-1"), 21, pairs=True, qks=[21])
 
 
+@pytest.mark.parametrize("ballot", ["0", "1"])
+@pytest.mark.parametrize("base,k,n", [("A", 31, n) for n in (1535, 1536, 1537, 3073, 2047, 2048, 2049)]
+                         + [("G", 32, 1537), ("G", 32, 2049)])
+def test_batch_boundary(gpu, test_lib, monkeypatch, base, k, n, ballot):
+    """One bucket of exactly n windows of one key, n on either side of a batch: 1536 windows per
+    batch of a bucket-id stream, 2048 of a key stream (one batch against two, two against three).
+    All-G at k = 32 is the sentinel key, so the many-batch count lands in the side slot."""
+    monkeypatch.setenv("KMHG_TEST_BALLOT", ballot)
+    seen = _all_modes(monkeypatch, base * (n + k - 1), k, pairs=False)
+    assert all(v[4] == 0 for v in seen.values()), seen
+
+
 @pytest.mark.parametrize("tags", ["0", "1"])
 def test_query_paths_over_placed_layout(gpu, test_lib, monkeypatch, tags):
     """The table probe and the tag probe (diagonal path off) find keys placed in home order,

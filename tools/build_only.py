@@ -5,7 +5,8 @@
 Builds a synthetic iid sequence (splitmix64 seed 2 for 100 Mbp, 1 otherwise) `steps` times like
 bench.py's headline (asynchronous builds, freed, bracketed by synchronize) and prints one JSON
 line: ms per build, Gbp/s, and the per-kernel HIP-event times of one build.  No query, readout or
-other use of the tables is made, so a timing-only variant (e.g. -DKMHG_EXP_SLOT8) is safe here.
+other use of the tables is made, so a timing-only variant (`make variant` with a switch whose
+tables are wrong on purpose) is safe here.
 """
 import json
 import os
