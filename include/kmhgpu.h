@@ -159,6 +159,38 @@ int kmhg_query_run_device_range_runs(kmhg_index *idx, const void *d_seq, size_t 
                                      int64_t w_begin, int64_t w_end, void *stream,
                                      kmhg_query **q, int64_t *n_rows, int64_t *n_runs);
 int kmhg_query_runs_device(kmhg_query *q, const int32_t **d_runs);   /* owned by q */
+/* seq.kmer.pos.rc: the query's REVERSE COMPLEMENT against the index, made on the device from the
+ * forward sequence (the dot plot's second strand: the reference's usage script calls
+ * seq.kmer.pos(hash, reverseComplement(x), k), test.R:42-43, 49-52, 72-73, with the 2-bit rule
+ * (v + 2) %% 4 of its rev.comp, test.R:31-36).  `seq` / `d_seq` is the sequence S as the forward
+ * entries read it, of length L (kmhg_query_run_rc ends S at its first NUL or at L; the device
+ * entries use L bytes); no reversed copy is made on the host or the device.  For p in [0, L)
+ *   rc(S)[p] = 'N'                                   if S[L-1-p] is 'N' or 'n',
+ *            = "ACTG"[((S[L-1-p] >> 1) & 3) ^ 2]     otherwise.
+ * One deviation from rev.comp: it would turn an N into a C (it complements N's 2-bit code);
+ * here an N stays an N and breaks windows on both strands.  Every other byte, ambiguity codes
+ * included, is complemented by its 2-bit code as the reference encodes it (no IUPAC rule).
+ * The result is exactly the reference's sequence_kmer_positions(index, rc(S), k)
+ * (src/kmer_hash.c:1151-1172, src/kmer_pos.c:110-136): rows (i, j) ordered by i then j, i the
+ * 1-based END of the window in rc(S) -- that window STARTS at forward position L - i + 1
+ * (1-based) of S and is read leftwards on the opposite strand -- and j the index positions,
+ * ascending.  Window validity is the reference's rule applied to rc(S), end-drop quirk included;
+ * the quirk is not mirror-symmetric: a final N-free segment of rc(S) of exactly k chars is
+ * dropped, which in S is an INITIAL segment of exactly k chars followed by N (or a whole
+ * sequence of k chars).  Errors and their words are the forward entries'; the query k is
+ * independent of the index k; a counts index is accepted and a part index refused as by the
+ * forward whole-index entries.  w_begin / w_end are window starts in rc(S), and consecutive
+ * ranges concatenate to the unsharded rc result row for row.  The kmhg_query is an ordinary
+ * query handle.  KMHG_DEVICES is not honoured by kmhg_query_run_rc: it runs on the index's
+ * device. */
+int kmhg_query_run_rc(kmhg_index *idx, const char *seq, size_t L, int k, kmhg_query **q,
+                      int64_t *n_rows);
+int kmhg_query_run_rc_device_range(kmhg_index *idx, const void *d_seq, size_t L, int k,
+                                   int64_t w_begin, int64_t w_end, void *stream, kmhg_query **q,
+                                   int64_t *n_rows);
+int kmhg_query_run_rc_device_range_runs(kmhg_index *idx, const void *d_seq, size_t L, int k,
+                                        int64_t w_begin, int64_t w_end, void *stream,
+                                        kmhg_query **q, int64_t *n_rows, int64_t *n_runs);
 /* seq.kmer.pos over a PART of an owner-computes build (kmhg_build_device_part), without
  * assembling the parts: every window of the query is hashed and only the windows whose k-mer
  * this part owns are probed, so the rows are those windows' rows, in window order.  With one

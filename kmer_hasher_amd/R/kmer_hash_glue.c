@@ -16,6 +16,7 @@
  *   kmer_spectrum_suffix_hash_n(ptr, ...)   src/kmer_hash.c:1010-1039 -> REALSXP
  *   count_kmers_fastq_sh(ptr, params, f)    src/kmer_hash.c:715-806   -> EXTPTRSXP (suffix_hash)
  *   kmer_spectrum_suffix_hash(ptr, max)     src/kmer_hash.c:993-1008  -> REALSXP
+ *   sequence_kmer_positions_rc(ptr, seq, k) (not in the reference)    -> INTSXP 2 x H
  *
  * Differences, all deliberate: the finaliser frees the whole payload (the reference leaks the
  * 32-B khash_ptr, src/kmer_hash.c:56-66); a freed pointer is detected instead of dereferenced;
@@ -123,10 +124,9 @@ SEXP kmer_positions(SEXP ptr_r, SEXP opt_flag_r) {
   return ret;
 }
 
-/* With KMHG_DEVICES=d0,d1,... in the environment, kmhg_query_run splits the query over those
- * GPUs (index replicas peer-copied once, rows filled straight into the R matrix by
- * kmhg_query_fill at each device's row offset): same signature, same result. */
-SEXP sequence_kmer_positions(SEXP ptr_r, SEXP seq_r, SEXP k_r) {
+/* sequence_kmer_positions and its reverse-strand twin: one body over the C-ABI entry. */
+typedef int (*seq_query_fn)(kmhg_index *, const char *, size_t, int, kmhg_query **, int64_t *);
+static SEXP seq_positions_by(seq_query_fn run, SEXP ptr_r, SEXP seq_r, SEXP k_r) {
   kmhg_index *idx = gpu_index_of(ptr_r);
   if (TYPEOF(seq_r) != STRSXP || length(seq_r) != 1) error("seq_r should be a single sequence");
   if (TYPEOF(k_r) != INTSXP || length(k_r) != 1) error("k should be an integer of length 1");
@@ -134,7 +134,7 @@ SEXP sequence_kmer_positions(SEXP ptr_r, SEXP seq_r, SEXP k_r) {
   SEXP s = STRING_ELT(seq_r, 0);
   kmhg_query *q = NULL;
   int64_t h = 0;
-  if (kmhg_query_run(idx, CHAR(s), (size_t)length(s), k, &q, &h) != KMHG_OK)
+  if (run(idx, CHAR(s), (size_t)length(s), k, &q, &h) != KMHG_OK)
     error("%s", kmhg_last_error());
   if (h > INT_MAX) {
     kmhg_query_free(q);
@@ -146,6 +146,25 @@ SEXP sequence_kmer_positions(SEXP ptr_r, SEXP seq_r, SEXP k_r) {
   if (rc != KMHG_OK) error("%s", kmhg_last_error());
   UNPROTECT(1);
   return ret;
+}
+
+/* With KMHG_DEVICES=d0,d1,... in the environment, kmhg_query_run splits the query over those
+ * GPUs (index replicas peer-copied once, rows filled straight into the R matrix by
+ * kmhg_query_fill at each device's row offset): same signature, same result. */
+SEXP sequence_kmer_positions(SEXP ptr_r, SEXP seq_r, SEXP k_r) {
+  return seq_positions_by(kmhg_query_run, ptr_r, seq_r, k_r);
+}
+
+/* Not in the reference: sequence_kmer_positions of the REVERSE COMPLEMENT of seq, made on the
+ * device from the forward string (kmhg_query_run_rc, include/kmhgpu.h) -- what the reference's
+ * usage script computes as seq.kmer.pos(hash, reverseComplement(x), k) (test.R:42-43) with
+ * rev.comp's 2-bit rule (test.R:31-36), except that N stays N (rev.comp turns it into C).  Same
+ * validation in the same order, same INTSXP 2 x H of (i, j) in the coordinates of rc(seq): a
+ * row's window starts at forward position nchar(seq) - i + 1.  Exported, but like
+ * count_kmers_fastq_sh not in the registration table (.Call by name finds it by its dynamic
+ * lookup).  KMHG_DEVICES is not honoured. */
+SEXP sequence_kmer_positions_rc(SEXP ptr_r, SEXP seq_r, SEXP k_r) {
+  return seq_positions_by(kmhg_query_run_rc, ptr_r, seq_r, k_r);
 }
 
 /* kmer_pair_pos, src/kmer_hash.c:1174-1203 (called by kmer.pairs, kmer_hash.R:30-34): rows

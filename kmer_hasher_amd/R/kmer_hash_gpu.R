@@ -33,6 +33,18 @@ seq.kmer.pos <- function(ex.ptr, seq, k){
     t(m)
 }
 
+## not in the reference: the dot plot's other strand, seq.kmer.pos(ex.ptr, rc(seq), k) without
+## building rc(seq) (the reference's usage script does that on the host with rev.comp /
+## reverseComplement).  rc reverses seq and complements each char by its 2-bit code
+## ("ACTG"[code ^ 2], rev.comp's rule); one deviation from rev.comp: N stays N (it would become C),
+## so N breaks windows on both strands.  Rows are in the coordinates of rc(seq): i = end of the
+## window in rc(seq); that window starts at forward position nchar(seq) - i + 1 of seq.
+seq.kmer.pos.rc <- function(ex.ptr, seq, k){
+    m <- .Call("sequence_kmer_positions_rc", ex.ptr, as.character(seq), as.integer(k))
+    rownames(m) <- c("i", "j")
+    t(m)
+}
+
 ## shared k-mers of two indices: rows (a, b) = a position in ptr.a with a position in ptr.b
 ## (the reference's version crashes, test.R:330; this one visits only live k-mers, same k)
 kmer.pairs <- function(ptr.a, ptr.b){

@@ -203,6 +203,23 @@ def seq_kmer_pos(ex_ptr, seq, k) -> np.ndarray:
 
     Returns an (H, 2) int32 matrix with columns (i, j): i = 1-based end of the query window,
     j = 1-based start of the indexed occurrence; rows ordered by i then j."""
+    return _seq_kmer_pos(ex_ptr, seq, k, "kmhg_query_run")
+
+
+def seq_kmer_pos_rc(ex_ptr, seq, k) -> np.ndarray:
+    """seq.kmer.pos.rc: seq.kmer.pos of the REVERSE COMPLEMENT of seq, made on the device from
+    the forward string -- what the reference's usage script writes as
+    seq.kmer.pos(hash, reverseComplement(x), k) (test.R:42-43), with rev.comp's 2-bit rule
+    (test.R:31-36) except that N stays N (rev.comp would turn it into C).
+
+    Returns the same (H, 2) int32 matrix as seq_kmer_pos would for rc(seq): i = 1-based end of
+    the window in rc(seq), j = 1-based start of the indexed occurrence, ordered by i then j.  A
+    row's window starts at forward position len(seq) - i + 1 (1-based) of seq.  Runs on the
+    index's device (KMHG_DEVICES is not honoured)."""
+    return _seq_kmer_pos(ex_ptr, seq, k, "kmhg_query_run_rc")
+
+
+def _seq_kmer_pos(ex_ptr, seq, k, entry) -> np.ndarray:
     p = _extract(ex_ptr)
     if isinstance(seq, (list, tuple)) and len(seq) != 1:
         raise KmerHashError("seq_r should be a single sequence")
@@ -213,7 +230,7 @@ def seq_kmer_pos(ex_ptr, seq, k) -> np.ndarray:
     L = _lib.lib()
     q = C.c_void_p()
     h = C.c_int64()
-    rc = L.kmhg_query_run(p.handle, b, len(b), kk, C.byref(q), C.byref(h))
+    rc = getattr(L, entry)(p.handle, b, len(b), kk, C.byref(q), C.byref(h))
     if rc == _lib.KMHG_EINVAL:
         raise KmerHashError(L.kmhg_last_error().decode())
     _lib.check(rc)

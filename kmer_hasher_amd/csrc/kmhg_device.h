@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kmhg_common.h"
+#include "kmhg_revcomp.h"
 
 namespace kmhg {
 
@@ -299,6 +300,33 @@ __device__ __forceinline__ void stage_tile(const uint8_t* __restrict__ seq, int6
   StageRegs<W16> r;
   stage_load<W16, ALWAYS_ALIGNED>(r, seq, L, base, aligned);
   stage_pack(r, st);
+}
+
+// The stage of the query's reverse complement, filled from the FORWARD sequence
+// (kmhg_revcomp.h): `base` is an rc char index with base == L (mod 16) (rc_stage_base), so word
+// w's forward chars start at a multiple of 16 and an aligned sequence is read by the same single
+// 16-B loads as the forward stage, under stage_word's rule (no byte outside the 16-B blocks of
+// valid bytes); an unaligned one takes its byte path.  Chars outside [0, L) read as 'N' on
+// either strand.  The word is packed forward, then mirrored and complemented in registers.
+template <int W16>
+__device__ __forceinline__ void stage_tile_rc(const uint8_t* __restrict__ seq, int64_t L,
+                                              int64_t base, StageN<W16>& st, bool aligned) {
+  StageRegs<W16> r;
+#pragma unroll
+  for (int j = 0; j < StageRegs<W16>::kPer; ++j) {   // clamped word: one load on every path
+    const int w = min((int)threadIdx.x + j * BLOCK, W16 - 1);
+    r.v[j] = stage_word(seq, L, rc_word_fwd0(L, base, w), 0, aligned);
+  }
+#pragma unroll
+  for (int j = 0; j < StageRegs<W16>::kPer; ++j) {
+    const int w = threadIdx.x + j * BLOCK;
+    if (w < W16) {
+      uint32_t cd, nb;
+      pack16v(r.v[j], cd, nb);
+      st.code[w] = rc_code16(cd);
+      st.nbit[w] = rc_nbit16(nb);
+    }
+  }
 }
 
 // Window whose first char is stage offset o (global start s).  Returns validity per the

@@ -1176,9 +1176,11 @@ void finish_build(kmhg_index* idx) {
 // ---------------------------------------------------------------------------- query
 // Windows [w0, w1) of the query (default: all L - kq + 1).  Rows come out ordered by window
 // end, so shards of consecutive window ranges concatenate to the unsharded result.
+// rc: the reverse strand (kmhg_query_run_rc*).  d_seq is still the FORWARD sequence; only the
+// probe's stage fill differs, and w0, w1 and the rows' i are in rc(seq)'s coordinates.
 kmhg_query* query_device(kmhg_index* idx, const uint8_t* d_seq, int64_t L, int kq, int64_t w0,
                          int64_t w1, hipStream_t s, bool part_query = false,
-                         bool runs_mode = false) {
+                         bool runs_mode = false, bool rc = false) {
   ReleaseGroup rg(s);
   if (idx->canonical) fail(KMHG_EINVAL, "External pointer has incorrect tag");
   if (idx->is_part != part_query)
@@ -1257,7 +1259,7 @@ kmhg_query* query_device(kmhg_index* idx, const uint8_t* d_seq, int64_t L, int k
   LAUNCH("k_query_probe", s,
          launch_query_probe(d_seq, L, kq, idx->table.p, idx->geom, qrec.p, qmulti.p, w0, w1, aligned,
                             tile_row0, s, diag ? idx->diag_view() : DiagIdx{nullptr, nullptr, 0},
-                            diag && tags_on() ? idx->ptag.p : nullptr, elist.p + nt));
+                            diag && tags_on() ? idx->ptag.p : nullptr, elist.p + nt, rc));
   LAUNCH("k_scan_tiles_u64", s, launch_scan_u64(tile_row0, nt, total, tiles.p + nt, s));
   if (runs_mode) {
     // the rows as diagonal runs, made from the window records (k_qruns_*); rows written only
@@ -3107,6 +3109,60 @@ int kmhg_query_run_device_range_runs(kmhg_index* idx, const void* d_seq, size_t 
     DeviceGuard g(idx->device);
     hipStream_t s = (hipStream_t)stream;
     *q = query_device(idx, (const uint8_t*)d_seq, (int64_t)L, k, w_begin, w_end, s, false, true);
+    if (n_rows) *n_rows = (*q)->H;
+    if (n_runs) *n_runs = (*q)->n_runs;
+  });
+}
+
+// The reverse strand (include/kmhgpu.h): the forward entries' checks and words, the forward
+// sequence on the device, rc = true down to the probe's stage fill.
+int kmhg_query_run_rc(kmhg_index* idx, const char* seq, size_t L, int k, kmhg_query** q,
+                      int64_t* n_rows) {
+  return guarded([&] {
+    if (!idx || !seq || !q) fail(KMHG_EINVAL, "null argument");
+    if (L < H2D_SCAN_MIN || k < 1 || k > 31 || L >= (size_t)INT32_MAX) {
+      L = effective_len(seq, L);             // (as kmhg_query_run)
+      check_query_args(L, k);
+    }
+    DeviceGuard g(idx->device);
+    hipStream_t s = lib_stream();
+    DBuf<uint8_t> d(L + 16, s);
+    L = h2d_cstring(d.p, seq, L, s);         // the forward string: no reversed copy anywhere
+    check_query_args(L, k);
+    *q = query_device(idx, d.p, (int64_t)L, k, 0, (int64_t)L - k + 1, s, false, false, true);
+    HIPC(hipStreamSynchronize(s));
+    if (n_rows) *n_rows = (*q)->H;
+  });
+}
+
+int kmhg_query_run_rc_device_range(kmhg_index* idx, const void* d_seq, size_t L, int k,
+                                   int64_t w_begin, int64_t w_end, void* stream, kmhg_query** q,
+                                   int64_t* n_rows) {
+  return guarded([&] {
+    if (!idx || !d_seq || !q) fail(KMHG_EINVAL, "null argument");
+    check_query_args(L, k);
+    const int64_t Nw = (int64_t)L - k + 1;
+    if (w_begin < 0 || w_end > Nw || w_begin > w_end) fail(KMHG_EINVAL, "window range out of bounds");
+    DeviceGuard g(idx->device);
+    hipStream_t s = (hipStream_t)stream;   // caller stream; NULL = HIP null stream
+    *q = query_device(idx, (const uint8_t*)d_seq, (int64_t)L, k, w_begin, w_end, s, false, false,
+                      true);
+    if (n_rows) *n_rows = (*q)->H;
+  });
+}
+
+int kmhg_query_run_rc_device_range_runs(kmhg_index* idx, const void* d_seq, size_t L, int k,
+                                        int64_t w_begin, int64_t w_end, void* stream,
+                                        kmhg_query** q, int64_t* n_rows, int64_t* n_runs) {
+  return guarded([&] {
+    if (!idx || !d_seq || !q) fail(KMHG_EINVAL, "null argument");
+    check_query_args(L, k);
+    const int64_t Nw = (int64_t)L - k + 1;
+    if (w_begin < 0 || w_end > Nw || w_begin > w_end) fail(KMHG_EINVAL, "window range out of bounds");
+    DeviceGuard g(idx->device);
+    hipStream_t s = (hipStream_t)stream;
+    *q = query_device(idx, (const uint8_t*)d_seq, (int64_t)L, k, w_begin, w_end, s, false, true,
+                      true);
     if (n_rows) *n_rows = (*q)->H;
     if (n_runs) *n_runs = (*q)->n_runs;
   });

@@ -77,12 +77,14 @@ inline DiagBlock diag_block(uint64_t* p, int64_t Nw) {
   return DiagBlock{c, reinterpret_cast<uint16_t*>(c + cw), c + cw + cw / 2};
 }
 // X.code == nullptr: table probes only.  TG (optional, with X, g.capb % 16 == 0): slot tags for
-// the windows the diagonal path does not resolve
+// the windows the diagonal path does not resolve.  rc: the query's reverse strand, staged from the
+// forward sequence (kmhg_revcomp.h); w0, w1 and the records are then in rc coordinates (whole
+// indices only: a part's table with rc is refused)
 void launch_query_probe(const uint8_t* seq, int64_t L, int kq, const Slot* T, Geom g,
                         uint32_t* qrec, uint2* qmulti, int64_t w0, int64_t w1, bool aligned,
                         uint64_t* tile_rows,
                         hipStream_t s, DiagIdx X = DiagIdx{nullptr, nullptr, 0},
-                        const uint8_t* TG = nullptr, uint32_t* ecount = nullptr);
+                        const uint8_t* TG = nullptr, uint32_t* ecount = nullptr, bool rc = false);
 // Once per index, before its first diagonal query: `uniq` = the indexed windows (from the N
 // flags: the reference's window rule), then TG[i] = slot_tag of slot i (0 empty), all nslots
 // slots, and the `uniq` bits of every position of a key seen more than once cleared

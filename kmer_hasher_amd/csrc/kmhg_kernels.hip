@@ -647,7 +647,10 @@ __device__ __forceinline__ uint64_t diag_resolve8(const ST& st, int o0, int64_t 
 // PART (owner-routed query over a part of an owner-computes build): table probes only, and only
 // for the windows whose key this part owns; every other window records no hit here (its owner's
 // rank emits its rows).
-template <bool DIAG, bool NT, bool PART = false>
+// RC (the reverse strand, kmhg_query_run_rc*): the stage is filled with the query's reverse
+// complement from the forward sequence (stage_tile_rc) and w0, w1, the records and the rows are
+// in rc coordinates; nothing behind the stage differs.
+template <bool DIAG, bool NT, bool PART = false, bool RC = false>
 __global__ void PROBE_BOUNDS
 k_query_probe(const uint8_t* __restrict__ seq, int64_t L, int kq, const Slot* __restrict__ T,
               Geom g, uint32_t* __restrict__ qrec, uint2* __restrict__ qmulti, int64_t w0,
@@ -665,9 +668,11 @@ k_query_probe(const uint8_t* __restrict__ seq, int64_t L, int kq, const Slot* __
   // windows [w0, w1) of the FULL sequence: halo chars come from the real neighbours, so the
   // N / end-of-sequence rules at a shard boundary are those of the unsharded walk
   const int64_t t_start = w0 + (int64_t)tile * TILE;
-  const int64_t base = (t_start & ~15ll) - HALO;
+  static_assert(!(PART && RC), "the reverse-strand probe has no part form");
+  const int64_t base = RC ? rc_stage_base(t_start, L) : (t_start & ~15ll) - HALO;
   const int o0 = (int)(t_start - base);
-  stage_tile(seq, L, base, st, aligned != 0);
+  if (RC) stage_tile_rc(seq, L, base, st, aligned != 0);
+  else stage_tile(seq, L, base, st, aligned != 0);
   __syncthreads();
   if (DIAG) diag_anchors<NT, PART>(st, o0, t_start, w1, L, kq, T, g, A);
   uint64_t rows = 0;
@@ -1321,7 +1326,7 @@ constexpr uint64_t NT_PROBE_BYTES = (uint64_t)KMHG_NT_PROBE_MB << 20;
 void launch_query_probe(const uint8_t* seq, int64_t L, int kq, const Slot* T, Geom g,
                         uint32_t* qrec, uint2* qmulti, int64_t w0, int64_t w1, bool aligned,
                         uint64_t* tile_rows,
-                        hipStream_t s, DiagIdx X, const uint8_t* TG, uint32_t* ecount) {
+                        hipStream_t s, DiagIdx X, const uint8_t* TG, uint32_t* ecount, bool rc) {
   uint32_t nt = grid_for(w1 - w0, TILE);
   if (g.capb % 16 != 0) TG = nullptr;           // the tag groups are aligned 16-slot spans
   // nontemporal slot reads for a table of more than NT_PROBE_BYTES.  A/B in one run
@@ -1341,18 +1346,34 @@ void launch_query_probe(const uint8_t* seq, int64_t L, int kq, const Slot* T, Ge
                          DiagIdx{nullptr, nullptr, 0}, nullptr, ecount);
     return;
   }
-  if (X.code) {
-    if (ntl)
-      hipLaunchKernelGGL((k_query_probe<true, true>), dim3(nt), dim3(BLOCK), 0, s, seq, L, kq, T, g,
-                         qrec, qmulti, w0, w1, aligned ? 1 : 0, tile_rows, X, TG, ecount);
-    else
-      hipLaunchKernelGGL((k_query_probe<true, false>), dim3(nt), dim3(BLOCK), 0, s, seq, L, kq, T, g,
-                         qrec, qmulti, w0, w1, aligned ? 1 : 0, tile_rows, X, TG, ecount);
-  } else {
-    hipLaunchKernelGGL((k_query_probe<false, false>), dim3(nt), dim3(BLOCK), 0, s, seq, L, kq, T, g,
-                       qrec, qmulti, w0, w1, aligned ? 1 : 0, tile_rows,
-                       DiagIdx{nullptr, nullptr, 0}, nullptr, ecount);
+  if (!rc) {
+    if (X.code) {
+      if (ntl)
+        hipLaunchKernelGGL((k_query_probe<true, true>), dim3(nt), dim3(BLOCK), 0, s, seq, L, kq, T, g,
+                           qrec, qmulti, w0, w1, aligned ? 1 : 0, tile_rows, X, TG, ecount);
+      else
+        hipLaunchKernelGGL((k_query_probe<true, false>), dim3(nt), dim3(BLOCK), 0, s, seq, L, kq, T, g,
+                           qrec, qmulti, w0, w1, aligned ? 1 : 0, tile_rows, X, TG, ecount);
+    } else {
+      hipLaunchKernelGGL((k_query_probe<false, false>), dim3(nt), dim3(BLOCK), 0, s, seq, L, kq, T, g,
+                         qrec, qmulti, w0, w1, aligned ? 1 : 0, tile_rows,
+                         DiagIdx{nullptr, nullptr, 0}, nullptr, ecount);
+    }
+    return;
   }
+  // the reverse strand of a whole index
+  if (X.code && ntl)
+    hipLaunchKernelGGL((k_query_probe<true, true, false, true>), dim3(nt), dim3(BLOCK), 0, s, seq,
+                       L, kq, T, g, qrec, qmulti, w0, w1, aligned ? 1 : 0, tile_rows, X, TG,
+                       ecount);
+  else if (X.code)
+    hipLaunchKernelGGL((k_query_probe<true, false, false, true>), dim3(nt), dim3(BLOCK), 0, s,
+                       seq, L, kq, T, g, qrec, qmulti, w0, w1, aligned ? 1 : 0, tile_rows, X, TG,
+                       ecount);
+  else
+    hipLaunchKernelGGL((k_query_probe<false, false, false, true>), dim3(nt), dim3(BLOCK), 0, s,
+                       seq, L, kq, T, g, qrec, qmulti, w0, w1, aligned ? 1 : 0, tile_rows,
+                       DiagIdx{nullptr, nullptr, 0}, nullptr, ecount);
 }
 // ---------------------------------------------------------------- owner-routed query merge
 // dist.owner_query: rank r queried every window against its part of an owner-computes build and

@@ -149,6 +149,38 @@ class DeviceIndex:
             return "rows", dq.rows_view(), h.value
         return "runs", dq.runs_view(nr.value), h.value
 
+    # The reverse strand: `seq` is the FORWARD sequence; the rows are those of query(rc(seq))
+    # -- i the 1-based window end in rc(seq), whose window starts at forward position
+    # seq.numel() - i + 1 -- and w0, w1 are window starts in rc(seq).  N stays N
+    # (include/kmhgpu.h, kmhg_query_run_rc).  No reversed copy of the sequence is made.
+    def query_rc(self, seq: torch.Tensor, k: int, stream=None) -> "DeviceQuery":
+        return self.query_range_rc(seq, k, 0, max(seq.numel() - k + 1, 0), stream)
+
+    def query_range_rc(self, seq: torch.Tensor, k: int, w0: int, w1: int,
+                       stream=None) -> "DeviceQuery":
+        _check_seq(seq)
+        q = C.c_void_p()
+        h = C.c_int64()
+        with torch.cuda.device(seq.device):
+            _lib.check(_lib.lib().kmhg_query_run_rc_device_range(
+                self._h, C.c_void_p(seq.data_ptr()), seq.numel(), k, w0, w1, _stream_ptr(stream),
+                C.byref(q), C.byref(h)))
+        return DeviceQuery(q.value, h.value, seq.device)
+
+    def query_range_runs_rc(self, seq: torch.Tensor, k: int, w0: int, w1: int, stream=None):
+        """query_range_runs on the reverse strand: ('runs', ...) or ('rows', ...)."""
+        _check_seq(seq)
+        q = C.c_void_p()
+        h, nr = C.c_int64(), C.c_int64()
+        with torch.cuda.device(seq.device):
+            _lib.check(_lib.lib().kmhg_query_run_rc_device_range_runs(
+                self._h, C.c_void_p(seq.data_ptr()), seq.numel(), k, w0, w1, _stream_ptr(stream),
+                C.byref(q), C.byref(h), C.byref(nr)))
+        dq = DeviceQuery(q.value, h.value, seq.device)
+        if nr.value < 0:
+            return "rows", dq.rows_view(), h.value
+        return "runs", dq.runs_view(nr.value), h.value
+
     def positions(self, opt: int, stream=None) -> dict:
         """kmer.pos into device tensors: {'kmer': uint8 (U, k+1), 'pos': int32 (N, 2),
         'pair.pos': int32 (P, 3), 'count': int32 (U,)} for the requested bits."""
