@@ -283,6 +283,41 @@ int kmhg_query_rows_device(kmhg_query *q, const int32_t **d_rows); /* owned by q
 int kmhg_query_copy_device(kmhg_query *q, void *d_dst, void *stream);
 int kmhg_query_free(kmhg_query *q);
 
+/* seq.kmer.segs (not in the reference): a seq.kmer.pos result as maximal diagonal segments.
+ * The rows R are the (i, j) int32 rows of sequence_kmer_positions (src/kmer_pos.c:110-136), with
+ * i, j >= 1 and strictly ascending by (i, j), as every route of this library delivers them.  A
+ * segment (i, j, len) is a maximal diagonal stretch of R:
+ *   (i + t, j + t) is in R for 0 <= t < len;  (i - 1, j - 1) is not;  (i + len, j + len) is not.
+ * len counts rows (windows): the exact match covers len + k - 1 bases.  The result is 3 x S int32
+ * in R's column-major order, {i, j, len} per segment, ordered by (i, j) of the first row -- the
+ * order of the start rows among R.  min_len >= 1 keeps the segments with len >= min_len, in the
+ * same order.  The segments partition R: the min_len = 1 result, expanded and sorted by (i, j),
+ * is R.  Membership is decided from the ROWS alone, never from sequence characters, so the
+ * result is right for a query k that differs from the index k, for reverse-strand rows
+ * (kmhg_query_run_rc), for merged multi-GPU rows and for kmer.pairs rows, with no window rule
+ * restated.  The reference's author started on this and commented it out (offset_diagonals,
+ * src/kmer_hash.c:414-486: "there is something to be said for a non-heuristic function for
+ * identifying the structure of the underlying sequences"); the run format above (kmhg_rows_runs)
+ * joins only rows adjacent in row order and so breaks at every window with several hits.
+ *
+ * kmhg_rows_segments: any such rows in device memory, n_rows < 2^31, on `stream`, which it
+ * waits for; n_rows = 0 gives 0 segments and d_rows is not read.  kmhg_query_segments: the rows
+ * of a query handle, on its device (a KMHG_DEVICES query is gathered there first, as by
+ * kmhg_query_rows_device; a handle that holds runs is refused in that entry's words).  Errors,
+ * KMHG_EINVAL: "min_len must be a positive integer"; "rows are not in ascending (i, j) order"
+ * (also for a repeated row); "rows must have i, j >= 1".  The kmhg_segs handle owns the result:
+ * kmhg_segs_device gives its device pointer (valid until kmhg_segs_free), kmhg_segs_copy_device
+ * copies it into caller device memory on `stream`, kmhg_segs_fill into host memory (3 * n_segs
+ * int32).  kmhg_segs_free(NULL) is a no-op. */
+typedef struct kmhg_segs kmhg_segs;
+int kmhg_rows_segments(const void *d_rows, int64_t n_rows, int64_t min_len, void *stream,
+                       kmhg_segs **out, int64_t *n_segs);
+int kmhg_query_segments(kmhg_query *q, int64_t min_len, kmhg_segs **out, int64_t *n_segs);
+int kmhg_segs_device(kmhg_segs *g, const int32_t **d_segs, int64_t *n_segs);
+int kmhg_segs_copy_device(kmhg_segs *g, void *d_dst, void *stream);
+int kmhg_segs_fill(kmhg_segs *g, int32_t *segs);                 /* host, 3 * n_segs int32 */
+int kmhg_segs_free(kmhg_segs *g);
+
 /* kmer.pairs <- .Call("kmer_pair_pos", ptr_a, ptr_b)           src/kmer_hash.c:1174-1203
  * Rows (a, b) = (position in index a, position in index b) for every k-mer both indices hold:
  * a's k-mers in a's kmer.pos row order (kmhg_set_row_order), a's positions outer, b's inner;

@@ -17,6 +17,7 @@
  *   count_kmers_fastq_sh(ptr, params, f)    src/kmer_hash.c:715-806   -> EXTPTRSXP (suffix_hash)
  *   kmer_spectrum_suffix_hash(ptr, max)     src/kmer_hash.c:993-1008  -> REALSXP
  *   sequence_kmer_positions_rc(ptr, seq, k) (not in the reference)    -> INTSXP 2 x H
+ *   sequence_kmer_segments(ptr, seq, k, min_len, rc) (not in the reference) -> INTSXP 3 x S
  *
  * Differences, all deliberate: the finaliser frees the whole payload (the reference leaks the
  * 32-B khash_ptr, src/kmer_hash.c:56-66); a freed pointer is detected instead of dereferenced;
@@ -165,6 +166,48 @@ SEXP sequence_kmer_positions(SEXP ptr_r, SEXP seq_r, SEXP k_r) {
  * lookup).  KMHG_DEVICES is not honoured. */
 SEXP sequence_kmer_positions_rc(SEXP ptr_r, SEXP seq_r, SEXP k_r) {
   return seq_positions_by(kmhg_query_run_rc, ptr_r, seq_r, k_r);
+}
+
+/* Not in the reference: the dot plot of seq against the index as maximal diagonal segments
+ * (kmhg_query_segments, include/kmhgpu.h, which cites the reference author's abandoned
+ * offset_diagonals, src/kmer_hash.c:414-486).  Runs sequence_kmer_positions (rc = 0) or
+ * sequence_kmer_positions_rc (rc != 0) and returns INTSXP 3 x S of (i, j, len), ordered by (i, j):
+ * rows (i + t, j + t), t < len, are all among the positions and neither (i - 1, j - 1) nor
+ * (i + len, j + len) is; only segments of at least min_len rows are kept.  The argument checks
+ * come first, in argument order after the sequence's and k's own words; the pointer must be a
+ * position index (a count.kmers pointer's "positions" are count vectors).  Exported, not
+ * registered, like sequence_kmer_positions_rc. */
+SEXP sequence_kmer_segments(SEXP ptr_r, SEXP seq_r, SEXP k_r, SEXP min_len_r, SEXP rc_r) {
+  if (TYPEOF(seq_r) != STRSXP || length(seq_r) != 1) error("seq_r should be a single sequence");
+  if (TYPEOF(k_r) != INTSXP || length(k_r) != 1) error("k should be an integer of length 1");
+  if (TYPEOF(min_len_r) != INTSXP || length(min_len_r) != 1 || INTEGER(min_len_r)[0] < 1)
+    error("min_len must be a positive integer");
+  if (TYPEOF(rc_r) != INTSXP || length(rc_r) != 1) error("rc should be an integer of length 1");
+  kmhg_index *idx = gpu_index_of(ptr_r);
+  kmhg_info inf;
+  if (kmhg_index_info(idx, &inf) != KMHG_OK) error("%s", kmhg_last_error());
+  if (inf.kind != 0) error("segments need a position index");
+  int k = asInteger(k_r);
+  SEXP s = STRING_ELT(seq_r, 0);
+  kmhg_query *q = NULL;
+  kmhg_segs *g = NULL;
+  int64_t h = 0, n = 0;
+  if ((INTEGER(rc_r)[0] ? kmhg_query_run_rc : kmhg_query_run)(idx, CHAR(s), (size_t)length(s), k,
+                                                              &q, &h) != KMHG_OK)
+    error("%s", kmhg_last_error());
+  int rc = kmhg_query_segments(q, INTEGER(min_len_r)[0], &g, &n);
+  kmhg_query_free(q);
+  if (rc != KMHG_OK) error("%s", kmhg_last_error());
+  if (n > INT_MAX) {
+    kmhg_segs_free(g);
+    error("result has more than 2^31-1 columns (R matrix limit)");
+  }
+  SEXP ret = PROTECT(allocMatrix(INTSXP, 3, (int)n));
+  rc = kmhg_segs_fill(g, INTEGER(ret));
+  kmhg_segs_free(g);
+  if (rc != KMHG_OK) error("%s", kmhg_last_error());
+  UNPROTECT(1);
+  return ret;
 }
 
 /* kmer_pair_pos, src/kmer_hash.c:1174-1203 (called by kmer.pairs, kmer_hash.R:30-34): rows

@@ -45,6 +45,20 @@ seq.kmer.pos.rc <- function(ex.ptr, seq, k){
     t(m)
 }
 
+## not in the reference: the dot plot as maximal diagonal segments instead of points.  Runs
+## seq.kmer.pos (rc=FALSE) or seq.kmer.pos.rc (rc=TRUE) and returns a matrix with columns
+## i, j, len, ordered by (i, j): rows (i + t, j + t), t < len, are all in that result and neither
+## (i - 1, j - 1) nor (i + len, j + len) is.  len counts windows: the exact match covers
+## len + k - 1 bases, drawn with segments(m[,"j"], m[,"i"], m[,"j"] + m[,"len"] - 1,
+## m[,"i"] + m[,"len"] - 1).  min.len keeps the segments of at least that many rows; with
+## min.len=1 they expand back to exactly seq.kmer.pos's rows.  Position indices only.
+seq.kmer.segs <- function(ex.ptr, seq, k, min.len=1, rc=FALSE){
+    m <- .Call("sequence_kmer_segments", ex.ptr, as.character(seq), as.integer(k),
+               as.integer(min.len), as.integer(rc))
+    rownames(m) <- c("i", "j", "len")
+    t(m)
+}
+
 ## shared k-mers of two indices: rows (a, b) = a position in ptr.a with a position in ptr.b
 ## (the reference's version crashes, test.R:330; this one visits only live k-mers, same k)
 kmer.pairs <- function(ptr.a, ptr.b){

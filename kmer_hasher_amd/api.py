@@ -219,6 +219,51 @@ def seq_kmer_pos_rc(ex_ptr, seq, k) -> np.ndarray:
     return _seq_kmer_pos(ex_ptr, seq, k, "kmhg_query_run_rc")
 
 
+def seq_kmer_segs(ex_ptr, seq, k, min_len=1, rc=False) -> np.ndarray:
+    """seq.kmer.segs (not in the reference): the dot plot of seq against the index as maximal
+    diagonal segments instead of points.
+
+    Runs seq.kmer.pos (rc=False) or seq.kmer.pos.rc (rc=True) on the device and returns an (S, 3)
+    int32 matrix with columns (i, j, len), ordered by (i, j): rows (i + t, j + t), 0 <= t < len,
+    are all in the seq.kmer.pos result and neither (i - 1, j - 1) nor (i + len, j + len) is.  len
+    counts windows; the exact match covers len + k - 1 bases.  min_len keeps the segments of at
+    least that many rows; with min_len = 1 the segments expand back to exactly the rows.  Only a
+    position index (make_kmer_hash) is accepted: a counts index's "positions" are count vectors,
+    not ascending."""
+    p = _extract(ex_ptr)
+    L = _lib.lib()
+    if p.info().kind != 0:
+        raise KmerHashError("segments need a position index")
+    if isinstance(seq, (list, tuple)) and len(seq) != 1:
+        raise KmerHashError("seq_r should be a single sequence")
+    b = _as_seq_bytes(seq, "seq_r should be a single sequence")
+    if isinstance(k, (list, tuple, np.ndarray)) and len(k) != 1:
+        raise KmerHashError("k should be an integer of length 1")
+    kk = _as_int(k, "k should be an integer of length 1")
+    ml = _as_int(min_len, "min_len must be a positive integer")
+    q = C.c_void_p()
+    h = C.c_int64()
+    rcode = (L.kmhg_query_run_rc if rc else L.kmhg_query_run)(p.handle, b, len(b), kk,
+                                                              C.byref(q), C.byref(h))
+    if rcode == _lib.KMHG_EINVAL:
+        raise KmerHashError(L.kmhg_last_error().decode())
+    _lib.check(rcode)
+    g = C.c_void_p()
+    n = C.c_int64()
+    try:
+        rcode = L.kmhg_query_segments(q, ml, C.byref(g), C.byref(n))
+        if rcode == _lib.KMHG_EINVAL:
+            raise KmerHashError(L.kmhg_last_error().decode())
+        _lib.check(rcode)
+        segs = np.empty(3 * n.value, np.int32)
+        if n.value:
+            _lib.check(L.kmhg_segs_fill(g, segs.ctypes.data))
+    finally:
+        L.kmhg_segs_free(g)
+        L.kmhg_query_free(q)
+    return segs.reshape(-1, 3)
+
+
 def _seq_kmer_pos(ex_ptr, seq, k, entry) -> np.ndarray:
     p = _extract(ex_ptr)
     if isinstance(seq, (list, tuple)) and len(seq) != 1:

@@ -614,6 +614,15 @@ struct kmhg_query {
   int64_t n_runs = -1;
 };
 
+// seq.kmer.segs: the {i, j, len} segments of some rows (kmhg_rows_segments), complete when the
+// handle is returned; `stream` is the stream they were made on.
+struct kmhg_segs {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  int64_t S = 0;
+  DBuf<int32_t> segs;
+};
+
 namespace {
 
 struct DeviceGuard {
@@ -3416,6 +3425,147 @@ int kmhg_query_copy_device(kmhg_query* q, void* d_dst, void* stream) {
 
 int kmhg_query_free(kmhg_query* q) {
   return guarded([&] { free_query(q); });
+}
+
+// ---------------------------------------------------------------------------- seq.kmer.segs
+namespace {
+
+// The maximal diagonal segments of n_rows ascending rows on the current device (kmhg_segs.hip;
+// include/kmhgpu.h has the definition).  Waits for `s` twice (the number of segments sizes the
+// sort; min_len > 1: the number kept sizes the result) and once more at the end.
+kmhg_segs* rows_segments(const int2* rows, int64_t n_rows, int64_t min_len, hipStream_t s) {
+  auto g = std::make_unique<kmhg_segs>();
+  if (!n_rows) return g.release();      // (no device call: an empty result is host-only)
+  HIPC(hipGetDevice(&g->device));
+  g->stream = s;
+  ReleaseGroup rg(s);
+  const uint64_t n = (uint64_t)n_rows, nt = (n + TILE - 1) / TILE;
+  DBuf<uint64_t> tiles(nt + scan_u64_scratch(nt), s);
+  DBuf<uint64_t> masks(2 * nt * (TILE / 64), s);
+  uint64_t* smask = masks.p;
+  uint64_t* emask = masks.p + nt * (TILE / 64);
+  PinnedRec hrec = PinnedPool::get().take();
+  GiveBack give_back{hrec, s};
+  BuildMeta* hm = hrec.meta;            // n_kmers: scan totals; n_small / n_large: input faults
+  __atomic_store_n(&hm->n_small, 0u, __ATOMIC_RELEASE);
+  __atomic_store_n(&hm->n_large, 0u, __ATOMIC_RELEASE);
+  LAUNCH("k_segs_classify", s, launch_segs_classify(rows, n, smask, emask, tiles.p, &hm->n_small,
+                                                    &hm->n_large, s));
+  LAUNCH("k_scan_tiles_u64", s, launch_scan_u64(tiles.p, nt, &hm->n_kmers, tiles.p + nt, s));
+  HIPC(hipStreamSynchronize(s));
+  if (__atomic_load_n(&hm->n_large, __ATOMIC_ACQUIRE)) fail(KMHG_EINVAL, "rows must have i, j >= 1");
+  if (__atomic_load_n(&hm->n_small, __ATOMIC_ACQUIRE))
+    fail(KMHG_EINVAL, "rows are not in ascending (i, j) order");
+  const uint64_t both = __atomic_load_n(&hm->n_kmers, __ATOMIC_ACQUIRE);
+  const uint64_t S = both & 0xFFFFFFFFull;
+  // on every diagonal starts and ends alternate, so there are as many of each
+  if (!S || (both >> 32) != S) fail(KMHG_EDEVICE, "segment starts and ends do not pair");
+  if (min_len > INT32_MAX) return g.release();            // no segment has that many rows
+  DBuf<uint64_t> keys(4 * S, s);                          // start, end keys; both sorted
+  DBuf<uint32_t> ranks(2 * S, s);
+  uint64_t *skey = keys.p, *ekey = keys.p + S, *skey_o = keys.p + 2 * S, *ekey_o = keys.p + 3 * S;
+  LAUNCH("k_segs_emit", s, launch_segs_emit(rows, n, smask, emask, tiles.p, skey, ranks.p, ekey, s));
+  size_t tb = 0;
+  HIPC(segs_sort_temp_bytes(S, &tb));
+  DBuf<uint8_t> temp(std::max<size_t>(tb, 16), s);
+  hipError_t sort_err = hipSuccess;
+  LAUNCH("k_segs_sort", s, sort_err = launch_segs_sort(skey, ranks.p, ekey, S, skey_o, ranks.p + S,
+                                                       ekey_o, temp.p, tb, s));
+  HIPC(sort_err);
+  if (min_len == 1) {
+    g->segs.reset(3 * S);
+    LAUNCH("k_segs_pair", s, launch_segs_pair(skey_o, ranks.p + S, ekey_o, S, g->segs.p, s));
+    g->S = (int64_t)S;
+  } else {
+    DBuf<int32_t> all(3 * S, s);
+    LAUNCH("k_segs_pair", s, launch_segs_pair(skey_o, ranks.p + S, ekey_o, S, all.p, s));
+    const uint64_t nts = (S + TILE - 1) / TILE;
+    DBuf<uint64_t> ftiles(nts + scan_u64_scratch(nts), s);
+    LAUNCH("k_segs_filter", s, launch_segs_filter_count(all.p, S, (int32_t)min_len, ftiles.p, s));
+    LAUNCH("k_scan_tiles_u64", s,
+           launch_scan_u64(ftiles.p, nts, &hm->n_positions, ftiles.p + nts, s));
+    HIPC(hipStreamSynchronize(s));
+    const uint64_t K = __atomic_load_n(&hm->n_positions, __ATOMIC_ACQUIRE);
+    g->segs.reset(3 * K);
+    if (K)
+      LAUNCH("k_segs_filter", s, launch_segs_filter_emit(all.p, S, (int32_t)min_len, ftiles.p,
+                                                         g->segs.p, s));
+    g->S = (int64_t)K;
+  }
+  HIPC(hipStreamSynchronize(s));
+  rg.synced = true;
+  return g.release();
+}
+
+void check_segs_args(int64_t min_len, kmhg_segs** out) {
+  if (!out) fail(KMHG_EINVAL, "null argument");
+  if (min_len < 1) fail(KMHG_EINVAL, "min_len must be a positive integer");
+}
+
+}  // namespace
+
+int kmhg_rows_segments(const void* d_rows, int64_t n_rows, int64_t min_len, void* stream,
+                       kmhg_segs** out, int64_t* n_segs) {
+  return guarded([&] {
+    check_segs_args(min_len, out);
+    if (n_rows < 0 || n_rows > INT32_MAX) fail(KMHG_EINVAL, "bad row count");
+    if (n_rows && !d_rows) fail(KMHG_EINVAL, "null argument");
+    *out = rows_segments(static_cast<const int2*>(d_rows), n_rows, min_len, (hipStream_t)stream);
+    if (n_segs) *n_segs = (*out)->S;
+  });
+}
+
+int kmhg_query_segments(kmhg_query* q, int64_t min_len, kmhg_segs** out, int64_t* n_segs) {
+  return guarded([&] {
+    if (!q) fail(KMHG_EINVAL, "null argument");
+    check_segs_args(min_len, out);
+    if (q->n_runs >= 0) fail(KMHG_EINVAL, "the query holds runs (kmhg_query_runs_device)");
+    if (q->H > INT32_MAX) fail(KMHG_EINVAL, "bad row count");
+    gather_parts(q);                    // a multi-device query's rows, on its home device
+    DeviceGuard g(q->device);
+    *out = rows_segments(q->rows.p, q->H, min_len, q->stream);
+    if (n_segs) *n_segs = (*out)->S;
+  });
+}
+
+int kmhg_segs_device(kmhg_segs* g, const int32_t** d_segs, int64_t* n_segs) {
+  return guarded([&] {
+    if (!g || !d_segs) fail(KMHG_EINVAL, "null argument");
+    *d_segs = g->S ? g->segs.p : nullptr;
+    if (n_segs) *n_segs = g->S;
+  });
+}
+
+int kmhg_segs_copy_device(kmhg_segs* g, void* d_dst, void* stream) {
+  return guarded([&] {
+    if (!g) fail(KMHG_EINVAL, "null argument");
+    if (!g->S) return;
+    if (!d_dst) fail(KMHG_EINVAL, "null output");
+    DeviceGuard dg(g->device);
+    HIPC(hipMemcpyAsync(d_dst, g->segs.p, (size_t)g->S * 12, hipMemcpyDeviceToDevice,
+                        (hipStream_t)stream));
+  });
+}
+
+int kmhg_segs_fill(kmhg_segs* g, int32_t* segs) {
+  return guarded([&] {
+    if (!g) fail(KMHG_EINVAL, "null argument");
+    if (!g->S) return;
+    if (!segs) fail(KMHG_EINVAL, "null output");
+    DeviceGuard dg(g->device);
+    d2h_host(segs, g->segs.p, (size_t)g->S * 12, lib_stream());
+  });
+}
+
+int kmhg_segs_free(kmhg_segs* g) {
+  return guarded([&] {
+    if (!g) return;
+    std::unique_ptr<kmhg_segs> own(g);
+    if (!g->S) return;
+    DeviceGuard dg(g->device);
+    // the caller keeps the stream it made the segments on alive until here (as for a query)
+    HIPC(hipStreamSynchronize(g->stream));
+  });
 }
 
 int kmhg_image_sizes_get(const kmhg_index* cidx, kmhg_image_sizes* sz, int64_t header[8]) {

@@ -123,6 +123,30 @@ void launch_runs_emit(const int2* rows, uint64_t n, const uint64_t* tile_off, in
                       hipStream_t s);
 void launch_runs_expand(const int32_t* runs, uint64_t n_runs, uint64_t n, uint32_t* cover,
                         int2* out, hipStream_t s);
+// maximal diagonal segments of ascending query rows (kmhg_rows_segments; kmhg_segs.hip, the
+// arithmetic in kmhg_segs.h).  classify: row r's start / end bits as ballot words, smask / emask
+// (32 u64 per TILE rows each), tile_cnt = {ends << 32 | starts} per tile, *unsorted / *nonpos <- 1
+// (host-visible words, zeroed by the caller) on rows that are not ascending / below 1.  emit
+// (tile_off = the scanned tile_cnt): the starts' pairing keys with their ranks, and the ends'
+// keys, in row order.  sort: both key arrays ascending, ranks carried (temp: segs_sort_temp_bytes).
+// pair: {i, j, len} of sorted pair m at out + 3 * its start's rank.  filter: the segments with
+// len >= min_len, in order (count per TILE segments, scan, emit).
+void launch_segs_classify(const int2* rows, uint64_t n, uint64_t* smask, uint64_t* emask,
+                          uint64_t* tile_cnt, uint32_t* unsorted, uint32_t* nonpos,
+                          hipStream_t s);
+void launch_segs_emit(const int2* rows, uint64_t n, const uint64_t* smask, const uint64_t* emask,
+                      const uint64_t* tile_off, uint64_t* skey, uint32_t* srank, uint64_t* ekey,
+                      hipStream_t s);
+hipError_t segs_sort_temp_bytes(uint64_t S, size_t* bytes);
+hipError_t launch_segs_sort(const uint64_t* skey, const uint32_t* srank, const uint64_t* ekey,
+                            uint64_t S, uint64_t* skey_out, uint32_t* srank_out,
+                            uint64_t* ekey_out, void* temp, size_t temp_bytes, hipStream_t s);
+void launch_segs_pair(const uint64_t* skey, const uint32_t* srank, const uint64_t* ekey,
+                      uint64_t S, int32_t* out, hipStream_t s);
+void launch_segs_filter_count(const int32_t* segs, uint64_t S, int32_t min_len,
+                              uint64_t* tile_cnt, hipStream_t s);
+void launch_segs_filter_emit(const int32_t* segs, uint64_t S, int32_t min_len,
+                             const uint64_t* tile_off, int32_t* out, hipStream_t s);
 // exclusive u64 scan in place, *total <- sum: one workgroup up to SCAN1_MAX entries, else
 // reduce-then-scan with `scratch` = scan_u64_scratch(n) u64
 // (round 4: one workgroup up to 64 K / 256 K totals instead -- config 3 query 185 -> 162 Gbp/s,

@@ -475,6 +475,53 @@ def runs_expand(runs: torch.Tensor, n_rows: int, out: torch.Tensor, stream=None)
     return out
 
 
+def _segs_tensor(h: C.c_void_p, n: int, device) -> torch.Tensor:
+    """The (S, 3) int32 tensor of a kmhg_segs handle, which it owns (rows_view's contract)."""
+    g = _DeviceSegs(h)
+    if not n:
+        g.free()
+        return torch.empty((0, 3), dtype=torch.int32, device=device)
+    d = C.c_void_p()
+    _lib.check(_lib.lib().kmhg_segs_device(h, C.byref(d), None))
+    return torch.as_tensor(_RowsBuffer(g, d.value, (n, 3)), device=device)
+
+
+def rows_segments(rows: torch.Tensor, min_len: int = 1, stream=None) -> torch.Tensor:
+    """kmhg_rows_segments (seq.kmer.segs): the (H, 2) int32 device rows of a seq.kmer.pos result
+    -- i, j >= 1, strictly ascending by (i, j) -- as their maximal diagonal segments, an (S, 3)
+    int32 tensor of {i, j, len} ordered by (i, j): (i + t, j + t) is a row for 0 <= t < len and
+    neither (i - 1, j - 1) nor (i + len, j + len) is.  min_len keeps the segments of at least
+    that many rows.  Decided from the rows alone (include/kmhgpu.h).  Synchronous."""
+    if not (rows.is_cuda and rows.dtype == torch.int32 and rows.dim() == 2 and rows.shape[1] == 2):
+        raise TypeError("rows must be an (H, 2) torch.int32 CUDA tensor")
+    rows = rows.contiguous()
+    g = C.c_void_p()
+    n = C.c_int64()
+    with torch.cuda.device(rows.device):
+        _lib.check(_lib.lib().kmhg_rows_segments(
+            C.c_void_p(rows.data_ptr() if rows.shape[0] else None), rows.shape[0], int(min_len),
+            _stream_ptr(stream), C.byref(g), C.byref(n)))
+    return _segs_tensor(g, n.value, rows.device)
+
+
+class _DeviceSegs:
+    """Owner of a kmhg_segs handle (freed with the last tensor made from it)."""
+
+    def __init__(self, h: C.c_void_p):
+        self._h = h
+
+    def free(self):
+        if self._h:
+            _lib.lib().kmhg_segs_free(self._h)
+            self._h = C.c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class DeviceQuery:
     def __init__(self, handle: int, n_rows: int, device: torch.device | None = None):
         self._h = C.c_void_p(handle)
@@ -521,6 +568,15 @@ class DeviceQuery:
         _lib.check(_lib.lib().kmhg_query_rows_device(self._h, C.byref(d)))
         return torch.as_tensor(_RowsBuffer(self, d.value))   # on the rows' own device
 
+    def segments(self, min_len: int = 1) -> torch.Tensor:
+        """kmhg_query_segments: this query's rows as maximal diagonal segments, (S, 3) int32
+        {i, j, len} on the query's device (rows_segments of its rows; a KMHG_DEVICES query is
+        gathered there first)."""
+        g = C.c_void_p()
+        n = C.c_int64()
+        _lib.check(_lib.lib().kmhg_query_segments(self._h, int(min_len), C.byref(g), C.byref(n)))
+        return _segs_tensor(g, n.value, self.device)
+
     def runs_view(self, n_runs: int) -> torch.Tensor:
         """The (n_runs, 3) int32 runs of a runs query (kmhg_query_runs_device), as a tensor that
         owns this query (rows_view's contract)."""
@@ -546,7 +602,7 @@ class _RowsBuffer:
     """__cuda_array_interface__ of a query's device rows; torch keeps this object (and so the
     query) alive for as long as the tensor made from it."""
 
-    def __init__(self, q: DeviceQuery, ptr: int, shape: tuple | None = None):
+    def __init__(self, q, ptr: int, shape: tuple | None = None):
         self.q = q
         self.__cuda_array_interface__ = {"shape": shape or (q.n_rows, 2), "typestr": "<i4",
                                          "data": (ptr, False), "version": 3, "strides": None,
