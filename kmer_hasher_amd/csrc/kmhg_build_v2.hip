@@ -80,14 +80,23 @@ __device__ __forceinline__ bool in_part(uint64_t h, const Geom& g) {
 __device__ __forceinline__ bool side_bucket(uint32_t b, const Geom& g) {
   return b + g.b0 == bucket_of(mix64(EMPTY_KEY), g.nbh ? g.nbh : g.nb);
 }
-// radix digit of a bucket id (bucket-id streams carry it instead of the key)
+// A build of fewer than 2^16 buckets (Digit::small; digit32_ok, digit32 in kmhg_plan.h) takes
+// the 32-bit form instead: one v_mul_hi_u32 per division where the 64-bit form is four multiplies.
+// radix digit of a bucket id (bucket-id streams carry it instead of the key).  SMALL: the caller
+// has tested D.small once (V_hist0's window loop), 1 = set, 0 = not set; -1: tested here.
+template <int SMALL = -1>
 __device__ __forceinline__ uint32_t digit_of_b(uint32_t b, const Digit& D) {
+  if (SMALL < 0 ? D.small != 0 : SMALL != 0) {
+    uint32_t hi;
+    return digit32(b, D.m32div, D.m32R, D.R, hi);
+  }
   const uint32_t q = div_magic(b, D.mdiv);
   return q - div_magic(q, D.mR) * D.R;
 }
 // ... and the quotient above it, floor(b / (div R)): in a two-pass plan (b < R^2) the next pass's
 // digit, for free (the digit-pos word of the packed bucket-id stream)
 __device__ __forceinline__ uint32_t digit_of_b_hi(uint32_t b, const Digit& D, uint32_t& hi) {
+  if (D.small) return digit32(b, D.m32div, D.m32R, D.R, hi);
   const uint32_t q = div_magic(b, D.mdiv);
   hi = div_magic(q, D.mR);
   return q - hi * D.R;
@@ -178,7 +187,7 @@ __device__ __forceinline__ void diag_words_out(const PStage& st, uint32_t tile, 
 // outside this part) is stored in window order, one coalesced 4-B store per window, so the first
 // scatter pass reads the ids instead of encoding and hashing every window a second time.
 #ifndef KMHG_HIST0_WAVES
-#define KMHG_HIST0_WAVES 6   // Win8: 80 VGPRs without spills (7 spills 44 B / lane)
+#define KMHG_HIST0_WAVES 6   // the bound; the kernels need 42-47 VGPRs (hist0_valu_resources.txt)
 #endif
 // PARTC (a part build of an owner-computes build, key streams): the windows this part owns are
 // written compacted per tile instead of counted -- (key, position) of tile t's owned windows in
@@ -225,17 +234,29 @@ k_v2_hist0p(const uint8_t* __restrict__ seq, int64_t L, int k, int64_t Nw, Geom 
       const int64_t s0 = tile0 + w0;
       const Win8 win(st, HALO + w0, s0, L, k);
       uint32_t bl[8];
+      // `all`: the windows are known to be valid (vm unused), else vm says which are; `small`:
+      // D.small, tested once per tile instead of once per window
+      auto windows = [&](auto all, auto small, uint32_t vm) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        bl[j] = ~0u;
-        if (s0 + j < Nw && win.valid(j)) {
-          const uint32_t b = bucket_local(mix64(win.key(j)), g);
-          if (b < g.nb) {
-            if (!PARTC) atomicAdd(&lh[digit_of_b(b, D)], 1u);
-            bl[j] = b;
+        for (int j = 0; j < 8; ++j) {
+          bl[j] = ~0u;
+          if (decltype(all)::value || (vm >> j & 1u)) {
+            const uint32_t b = bucket_local(mix64(win.key(j)), g);
+            if (b < g.nb) {
+              if (!PARTC) atomicAdd(&lh[digit_of_b<decltype(small)::value ? 1 : 0>(b, D)], 1u);
+              bl[j] = b;
+            }
           }
         }
-      }
+      };
+      auto windows_of = [&](auto all, uint32_t vm) {
+        if (!PARTC && D.small) windows(all, std::true_type{}, vm);
+        else windows(all, std::false_type{}, vm);
+      };
+      // Validity once per thread, and not at all in a wave that sees no N and is nowhere near
+      // the sequence's end -- almost every wave of real input
+      if (__ballot(!win.all_valid(Nw)) == 0) windows_of(std::true_type{}, 0xFFu);
+      else windows_of(std::false_type{}, win.valid_mask(Nw));
       if (PARTC) {                 // this part's windows, compacted in window order
         uint32_t own = 0;
 #pragma unroll

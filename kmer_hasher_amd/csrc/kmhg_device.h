@@ -357,11 +357,14 @@ __device__ __forceinline__ bool window_key(const ST& st, int o, int64_t s, int64
 // Eight consecutive windows at stage offsets o0 .. o0 + 7 (global starts s0 .. s0 + 7), the same
 // rule as window_key, from 4 code words and 4 N-flag words read once: 8 LDS reads for 8 windows
 // instead of 48.  o0 >= 1 (the stage has HALO chars in front); chars [o0 - 1, o0 + 7 + k) lie
-// in the 64 chars from 16 * ((o0 - 1) / 16) for any o0 % 16 and k <= 32.  key(j) and
-// valid(j) take static j; only the six words stay live across the windows.
+// in the 64 chars from 16 * ((o0 - 1) / 16) for any o0 % 16 and k <= 32.
+// The words are aligned to window 0 ONCE (the only shifts by a per-thread amount): window j's
+// bits then sit a constant 2 j (code) or j (flags) further down, so key(j) and valid(j), with j
+// static, shift by constants and by the wave-uniform k alone.
 struct Win8 {
-  uint64_t hi, lo, nx;                       // code bits of chars 16 q .., N flags of 16 qn ..
-  int b, c0, k;
+  uint64_t top0, next;                       // code bits: window 0's first char at bit 63 of top0
+  uint64_t nal;                              // N flags: bit 63 = the char before window 0
+  int k;
   int64_t s0, L;
   template <class ST>
   __device__ __forceinline__ Win8(const ST& st, int o0, int64_t s0_, int64_t L_, int k_)
@@ -369,22 +372,45 @@ struct Win8 {
     // (words past the stage's end are clamped: the windows of the stage never reach them)
     constexpr int W = ST::kWords - 1;
     const int q = o0 >> 4, qn = (o0 - 1) >> 4;
-    b = o0 & 15;
-    c0 = (o0 - 1) & 15;
-    hi = ((uint64_t)st.code[q] << 32) | st.code[q + 1];
-    lo = ((uint64_t)st.code[min(q + 2, W)] << 32) | st.code[min(q + 3, W)];
-    nx = ((uint64_t)st.nbit[qn] << 48) | ((uint64_t)st.nbit[qn + 1] << 32) |
-         ((uint64_t)st.nbit[min(qn + 2, W)] << 16) | (uint64_t)st.nbit[min(qn + 3, W)];
+    const int sh = 2 * (o0 & 15);            // <= 30
+    const uint64_t hi = ((uint64_t)st.code[q] << 32) | st.code[q + 1];
+    const uint64_t lo = ((uint64_t)st.code[min(q + 2, W)] << 32) | st.code[min(q + 3, W)];
+    const uint64_t nx = ((uint64_t)st.nbit[qn] << 48) | ((uint64_t)st.nbit[qn + 1] << 32) |
+                        ((uint64_t)st.nbit[min(qn + 2, W)] << 16) | (uint64_t)st.nbit[min(qn + 3, W)];
+    top0 = sh ? (hi << sh) | (lo >> (64 - sh)) : hi;
+    next = lo << sh;
+    nal = nx << ((o0 - 1) & 15);
   }
   __device__ __forceinline__ uint64_t key(int j) const {
-    const int sh = 2 * (b + j);              // <= 44: the window's chars start here
-    const uint64_t top = sh ? (hi << sh) | (lo >> (64 - sh)) : hi;
+    const uint64_t top = j ? (top0 << (2 * j)) | (next >> (64 - 2 * j)) : top0;
     return top >> (64 - 2 * k);
   }
   __device__ __forceinline__ bool valid(int j) const {
     const int64_t s = s0 + j;
-    const uint64_t m = (nx << (c0 + j)) >> (63 - k);   // N flags of chars [o - 1, o + k)
+    const uint64_t m = (nal << j) >> (63 - k);         // N flags of chars [o - 1, o + k)
     return s + k <= L && !(m & ((2ull << (k - 1)) - 1ull)) && !(s + k == L && ((m >> k) & 1ull));
+  }
+  // Whether all eight windows are valid for sure: no N among their chars [o0, o0 + 7 + k), and
+  // even the last one ends before the sequence does, so the end rules (s + k <= L, the dropped
+  // window at s + k == L) and the window count Nw cannot bite.  A wave whose lanes all say so
+  // skips valid_mask.
+  __device__ __forceinline__ bool all_valid(int64_t Nw) const {
+    return ((nal << 1) >> (57 - k)) == 0 && s0 + 7 + k < L && s0 + 7 < Nw;
+  }
+  // valid(j) && s0 + j < Nw for the eight windows, bit j: the N test per window, the sequence-end
+  // rules once per thread (windows up to jl = min(L - k, Nw - 1) - s0 exist; the one at je =
+  // L - k - s0 is dropped if the char before it is N)
+  __device__ __forceinline__ uint32_t valid_mask(int64_t Nw) const {
+    const int64_t je = L - k - s0;
+    const int64_t jl = min(je, Nw - 1 - s0);
+    if (jl < 0) return 0u;
+    uint32_t vm = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      vm |= (((nal << (j + 1)) >> (64 - k)) == 0 ? 1u : 0u) << j;
+    if (jl < 7) vm &= (2u << jl) - 1u;
+    if (je <= 7 && ((nal >> (63 - je)) & 1ull)) vm &= ~(1u << je);
+    return vm;
   }
 };
 

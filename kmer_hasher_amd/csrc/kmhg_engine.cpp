@@ -827,6 +827,8 @@ kmhg_index* build_device_v2(const BuildRequest& rq, const StreamPtrs& in, hipStr
   const uint32_t passes = P.passes, R = P.R, ntiles = P.ntiles, nb = P.geom.nb;
   const uint64_t nhist = P.nhist;
   const Geom g = P.geom;
+  // every digit of this build: the 32-bit form where the plan allows it
+  auto mk_digit = [&](uint32_t dv, uint32_t r) { return make_digit(dv, r, P.digit32 ? g.nb : 0u); };
   const uint64_t* d_keys = in.d_keys;
   // the partition kernels read the sequence as aligned 16-B words: copy an unaligned input
   const uint8_t* d_seq = in.d_seq;
@@ -855,7 +857,7 @@ kmhg_index* build_device_v2(const BuildRequest& rq, const StreamPtrs& in, hipStr
   DBuf<uint16_t> dsb(P.ds_on ? ((uint64_t)Nw + PTILE + 8) / (P.ds8 ? 2 : 1) + 8 : 1, s);
   uint8_t* ds8p = P.ds8 ? reinterpret_cast<uint8_t*>(dsb.p) : nullptr;
   uint16_t* ds16p = P.ds8 ? nullptr : dsb.p;
-  const Pack8 pk8{P.pack8 ? P.sh8 : 0, segb.p, P.nseg8, make_digit(1, R)};
+  const Pack8 pk8{P.pack8 ? P.sh8 : 0, segb.p, P.nseg8, mk_digit(1, R)};
   // scratch (zeroed in-kernel by V_hist0 / V_hist, no memset): [n_valid][meta][scan status]
   const size_t off_meta = 64, off_status = 128;
   const uint32_t n_status = P.scan_tiles + 1;               // look-back words + ticket
@@ -896,7 +898,7 @@ kmhg_index* build_device_v2(const BuildRequest& rq, const StreamPtrs& in, hipStr
       db = idx->diag_block_of();
     }
     LAUNCH("k_v2_hist0", s,
-           launch_v2_hist0(d_seq, L, k, Nw, g, make_digit(1, R), hist.p, ntiles, status,
+           launch_v2_hist0(d_seq, L, k, Nw, g, mk_digit(1, R), hist.p, ntiles, status,
                            n_status, meta, s, db.code, db.nbit,
                            bid ? static_cast<uint32_t*>(kptr(-1)) : nullptr,
                            partc ? kB.p : nullptr, partc ? pB.p : nullptr,
@@ -905,11 +907,11 @@ kmhg_index* build_device_v2(const BuildRequest& rq, const StreamPtrs& in, hipStr
       LAUNCH("k_scan_u32", s, launch_scan_u32(tcnt.p, ntiles, status, n_valid, s));
     } else {       // pass 0: over the sequence, or over V_hist0's ids
       LAUNCH("k_scan_u32", s, launch_scan_u32(hist.p, nhist, status, n_valid, s));
-      const DigitOut ds0{ds16p, make_digit(R, R), ds8p};
+      const DigitOut ds0{ds16p, mk_digit(R, R), ds8p};
       LAUNCH("k_v2_scatter_seq", s,
              launch_v2_scatter(bid ? ScatterIn::first_pass(kptr(-1), Nw)
                                    : ScatterIn::sequence(d_seq, L, k, Nw),
-                               P.F(-1), P.F(0), kptr(0), pptr(0), pad, n_valid, g, make_digit(1, R),
+                               P.F(-1), P.F(0), kptr(0), pptr(0), pad, n_valid, g, mk_digit(1, R),
                                hist.p, ntiles, s, nullptr, P.pack8 ? &pk8 : nullptr,
                                P.ds_out(0) ? &ds0 : nullptr));
       // the segment table, before pass 1's histogram overwrites pass 0's
@@ -956,7 +958,7 @@ kmhg_index* build_device_v2(const BuildRequest& rq, const StreamPtrs& in, hipStr
     const bool last = p + 1 == passes;
     const uint32_t* lin = p == 1 ? lo_save.p : ((p - 1) % 2 ? lvA.p : lvB.p);
     uint32_t* lout = last ? start.p : (p % 2 ? lvA.p : lvB.p);
-    return BoundsFuse{lin, lout, make_digit((uint32_t)dv, R), (uint32_t)dv, spread,
+    return BoundsFuse{lin, lout, mk_digit((uint32_t)dv, R), (uint32_t)dv, spread,
                       last ? g.nb : (uint32_t)(dv * R)};
   };
   auto launch_level = [&](uint32_t p, const BoundsFuse& f) {   // over pass p's input
@@ -967,7 +969,7 @@ kmhg_index* build_device_v2(const BuildRequest& rq, const StreamPtrs& in, hipStr
   // the radix passes left: histogram (of the digits the pass before left, else of its input),
   // scan, scatter with the fused level, the level on its own where it is not fused
   for (uint32_t p = P.first_pass; p < passes; ++p) {
-    const Digit Dp = make_digit(div, R);
+    const Digit Dp = mk_digit(div, R);
     const bool keys0 = from_keys && p == 0;
     const bool last = p + 1 == passes;
     const bool hll = co_auto && p == 0;
@@ -992,7 +994,7 @@ kmhg_index* build_device_v2(const BuildRequest& rq, const StreamPtrs& in, hipStr
       HIPC(hipEventRecord(hrec.ev, s));
     }
     const BoundsFuse lv = level_of(p, 1u);              // (pass 0 has none: never fused)
-    const DigitOut dsn{ds16p, make_digit(div * R, R), ds8p};
+    const DigitOut dsn{ds16p, mk_digit(div * R, R), ds8p};
     LAUNCH("k_v2_scatter", s,
            launch_v2_scatter(keys0 ? ScatterIn::first_pass(d_keys, Nw, rq.skip_empty)
                                    : ScatterIn::stream(kptr(pi), pptr(pi)),
@@ -1018,7 +1020,7 @@ kmhg_index* build_device_v2(const BuildRequest& rq, const StreamPtrs& in, hipStr
   if (passes == 1) {
     // one pass (pass 0 reads chars or the caller's keys): the starts are the scanned column 0
     LAUNCH("k_v2_bounds", s,
-           launch_v2_bounds_lo(StreamFmt::Keys, nullptr, n_valid, g, make_digit(1, R), 1u,
+           launch_v2_bounds_lo(StreamFmt::Keys, nullptr, n_valid, g, mk_digit(1, R), 1u,
                                partc ? hp : hist.p, partc ? C : ntiles, nullptr, g.nb / gb.nb,
                                start.p, g.nb, s));
   } else if (!P.fused(passes - 1)) {

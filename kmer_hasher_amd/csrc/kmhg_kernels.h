@@ -188,17 +188,27 @@ struct Digit {
   uint64_t mR;     // ceil(2^64 / R), 0 for R = 1
   uint32_t R;
   int nbits;       // bits to name a digit 0..R-1
+  // the 32-bit form (magic32, kmhg_plan.h), used instead where `small` is set: a build of fewer
+  // than 2^16 buckets, whose every dividend (a bucket id, or its quotient by div) is below 2^16
+  uint32_t m32div; // ceil(2^32 / div), 0 for div = 1
+  uint32_t m32R;   // ceil(2^32 / R), 0 for R = 1
+  uint32_t small;
 };
 inline uint64_t magic64(uint32_t d) {   // ceil(2^64 / d) for d >= 2
   return d <= 1 ? 0 : (uint64_t)(~0ull / d) + 1;
 }
-inline Digit make_digit(uint32_t div, uint32_t R) {
+// nb: the build's bucket count where the plan found it small enough for the 32-bit form
+// (BuildPlan::digit32), else 0
+inline Digit make_digit(uint32_t div, uint32_t R, uint32_t nb = 0) {
   Digit d;
   d.mdiv = magic64(div);
   d.mR = magic64(R);
   d.R = R;
   d.nbits = 0;
   while ((1u << d.nbits) < R) ++d.nbits;
+  d.small = nb != 0 && digit32_ok(nb, div, R) ? 1u : 0u;
+  d.m32div = d.small ? magic32(div) : 0u;
+  d.m32R = d.small ? magic32(R) : 0u;
   return d;
 }
 // StreamFmt, what one element of a radix stream looks like, and its predicates: kmhg_plan.h.

@@ -217,6 +217,39 @@ inline int co_spread_for(double distinct, uint64_t total, int forced) {
   return std::max(1, std::min(4, f));
 }
 
+// Radix digits of small builds by 32-bit multiplies.  A digit is floor(b / div) mod R of a bucket
+// id b < nb, taken with magic multipliers (Digit, kmhg_kernels.h).  With m = ceil(2^32 / d),
+// d m - 2^32 < d, so for x < 2^16 and d <= 2^16 the error term x (d m - 2^32) stays below 2^32 and
+// (x m) >> 32 = floor(x / d) exactly: one 32-bit high multiply where the general 64-bit form takes
+// four multiplies.  magic32(1) = 0 stands for d = 1 (2^32 does not fit).
+constexpr uint32_t DIGIT32_LIMIT = 1u << 16;
+inline uint32_t magic32(uint32_t d) {   // ceil(2^32 / d) for d >= 2
+  return d <= 1 ? 0u : (uint32_t)(0xFFFFFFFFull / d) + 1u;
+}
+// every dividend of a build of nb buckets is below nb (and so is its quotient by div)
+inline bool digit32_ok(uint32_t nb, uint32_t div, uint32_t R) {
+  return nb >= 1 && nb < DIGIT32_LIMIT && div >= 1 && div <= DIGIT32_LIMIT && R >= 1 &&
+         R <= DIGIT32_LIMIT;
+}
+// floor(x / d) by m = magic32(d), x < 2^16.  (m = 0, d = 1: the high product is 0 and the mask
+// keeps x -- no branch.)  The kernels' own code (kmhg_build_v2.hip digit_of_b), here so that the
+// host can check it (tools/asan/digit_check.cpp).
+__host__ __device__ inline uint32_t div_magic32(uint32_t x, uint32_t m) {
+  return (uint32_t)(((uint64_t)x * m) >> 32) | (x & (m ? 0u : ~0u));
+}
+// the digit floor(b / div) mod R and the quotient above it, hi = floor(b / (div R)); hi and R are
+// below 2^16, so their product is a 24-bit multiply on the device
+__host__ __device__ inline uint32_t digit32(uint32_t b, uint32_t m32div, uint32_t m32R, uint32_t R,
+                                            uint32_t& hi) {
+  const uint32_t q = div_magic32(b, m32div);
+  hi = div_magic32(q, m32R);
+#ifdef __HIP_DEVICE_COMPILE__
+  return q - __umul24(hi, R);
+#else
+  return q - hi * R;
+#endif
+}
+
 // ---------------------------------------------------------------------------- the plan
 struct BuildPlan {
   int err = KMHG_OK;           // a refusal: the engine's fail(err, msg)
@@ -227,6 +260,7 @@ struct BuildPlan {
   bool is_part = false;
   bool empty_part = false;     // more parts than buckets: nothing to build (only geom is set)
   uint32_t R = 0, passes = 0;  // radix and radix passes: R^passes >= nb
+  bool digit32 = false;        // fewer than 2^16 buckets: digits by 32-bit multiplies (digit32_ok)
   bool from_keys = false;
   bool no_pos = false;         // count-only: keys only through the passes
   bool co_auto = false;        // count-only, the spread chosen after the passes
@@ -340,6 +374,7 @@ inline bool plan_geometry(BuildPlan& P, const BuildRequest& rq, const BuildKnobs
     return false;
   }
   P.geom = Geom{nb, V2_CAPW, b0, nbh};
+  P.digit32 = digit32_ok(nb, 1u, P.R);
   P.nhist = (uint64_t)P.R * P.ntiles;
   P.scan_tiles = (uint32_t)((P.nhist + TILE - 1) / TILE);
   return true;
