@@ -21,6 +21,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <numeric>
 #include <string>
 #include <thread>
 #include <vector>
@@ -31,6 +32,7 @@
 #include "kmhg_hostwork.h"
 #include "kmhg_pool.h"
 #include "kmhg_reads.h"
+#include "kmhg_querycall.h"
 #include "kmhg_parts_read.h"
 #include "kmhg_fastx.h"
 #include "kmhg_khash.h"
@@ -671,12 +673,43 @@ void check_build_args(size_t L, int k) {
   if (L >= (size_t)INT32_MAX) fail(KMHG_EOVERFLOW, "sequence longer than 2^31-1 (int positions)");
 }
 
-void check_query_args(size_t L, int k) {
-  // sequence_kmer_positions, src/kmer_hash.c:1163-1164
-  if ((int64_t)L <= k || k > 31 || k < 1)
-    fail(KMHG_EINVAL,
-         "the sequence should be longer than k and k should not be longer than 31");
-  if (L >= (size_t)INT32_MAX) fail(KMHG_EOVERFLOW, "sequence longer than 2^31-1 (int positions)");
+// A query call (kmhg_querycall.h) that was not refused.
+QueryCall checked(const QueryCall& c) {
+  if (c.code != KMHG_OK) fail(c.code, c.text);
+  return c;
+}
+
+void check_query_args(size_t L, int k) { checked(query_call(L, k)); }
+
+// fn(i) for every part i, one host thread per distinct key[i] (the first key's on the caller's);
+// the parts of one key run in order on its thread.  Every part's failure is kept and the first
+// one by part is returned (code KMHG_OK: none), so a caller can release what the others made.
+template <class F>
+Error for_parts(const std::vector<int>& key, F&& fn) {
+  const int n = (int)key.size();
+  std::vector<Error> errs(n, Error{KMHG_OK, ""});
+  std::vector<int> uniq;
+  for (int d : key)
+    if (std::find(uniq.begin(), uniq.end(), d) == uniq.end()) uniq.push_back(d);
+  auto run_key = [&](int d) {
+    for (int i = 0; i < n; ++i) {
+      if (key[i] != d) continue;
+      try {
+        fn(i);
+      } catch (const Error& e) {
+        errs[i] = e;
+      } catch (const std::bad_alloc&) {
+        errs[i] = Error{KMHG_ENOMEM, "host allocation failed"};
+      }
+    }
+  };
+  std::vector<std::thread> th;
+  for (size_t u = 1; u < uniq.size(); ++u) th.emplace_back(run_key, uniq[u]);
+  if (!uniq.empty()) run_key(uniq[0]);
+  for (auto& t : th) t.join();
+  for (const Error& e : errs)
+    if (e.code != KMHG_OK) return e;
+  return Error{KMHG_OK, ""};
 }
 
 // ---------------------------------------------------------------------------- build
@@ -1185,16 +1218,48 @@ void finish_build(kmhg_index* idx) {
 }
 
 // ---------------------------------------------------------------------------- query
-// Windows [w0, w1) of the query (default: all L - kq + 1).  Rows come out ordered by window
-// end, so shards of consecutive window ranges concatenate to the unsharded result.
-// rc: the reverse strand (kmhg_query_run_rc*).  d_seq is still the FORWARD sequence; only the
+// The diagonal path's once-per-index preparation (DiagIdx, kmhg_kernels.h): the uniq bits of
+// the windows of repeated keys, and the slot tags where the build did not write them.  True when
+// the path may be used: prepared now, or by an earlier query, possibly on another thread.  One
+// synchronize, once per index: later queries may run on other streams.  Without room for the
+// tags the index stays on table probes for good (ps_failed).
+bool ensure_diag(kmhg_index* idx, hipStream_t s) {
+  if (idx->ps_ready.load(std::memory_order_acquire)) return true;
+  std::lock_guard<std::mutex> lk(idx->ps_mu);
+  if (idx->ps_ready.load(std::memory_order_relaxed) || idx->ps_failed) return !idx->ps_failed;
+  if (!idx->tags_built) {
+    try {
+      idx->ptag.reset(idx->slots() + 32);  // + the 32-B span the last probe group reads
+    } catch (const Error& e) {             // no room for the tags: table probes only
+      if (e.code != KMHG_ENOMEM) throw;
+      idx->ps_failed = true;
+      (void)hipGetLastError();
+      return false;
+    }
+    idx->ptag.bind(s);
+  }
+  idx->dcodes.bind(s);
+  const DiagBlock db = idx->diag_block_of();
+  if (idx->tags_built)                     // the build wrote the tags and repeat bits
+    LAUNCH("k_diag_valid", s, launch_diag_valid(db.nbit, idx->L, idx->k, db.uniq, true, s));
+  else
+    LAUNCH("k_diag_prep", s,
+           launch_diag_prep(db.nbit, idx->L, idx->k, db.uniq, idx->table.p, idx->slots(),
+                            idx->positions.p, idx->ptag.p, s));
+  HIPC(hipStreamSynchronize(s));
+  idx->ps_ready.store(true, std::memory_order_release);
+  return true;
+}
+
+// Windows [c.w0, c.w1) of the query.  Rows come out ordered by window end, so shards of
+// consecutive window ranges concatenate to the unsharded result.
+// c.rc: the reverse strand (kmhg_query_run_rc*).  d_seq is still the FORWARD sequence; only the
 // probe's stage fill differs, and w0, w1 and the rows' i are in rc(seq)'s coordinates.
-kmhg_query* query_device(kmhg_index* idx, const uint8_t* d_seq, int64_t L, int kq, int64_t w0,
-                         int64_t w1, hipStream_t s, bool part_query = false,
-                         bool runs_mode = false, bool rc = false) {
+kmhg_query* query_device(kmhg_index* idx, const uint8_t* d_seq, const QueryCall& c,
+                         hipStream_t s) {
   ReleaseGroup rg(s);
   if (idx->canonical) fail(KMHG_EINVAL, "External pointer has incorrect tag");
-  if (idx->is_part != part_query)
+  if (idx->is_part != c.part)
     fail(KMHG_EINVAL, idx->is_part ? "a part index must be assembled before it is queried"
                                    : "not a part of an owner-computes build");
   finish_build(idx);
@@ -1202,60 +1267,24 @@ kmhg_query* query_device(kmhg_index* idx, const uint8_t* d_seq, int64_t L, int k
   q->device = idx->device;
   q->stream = s;
   idx->stream = s;
-  const int64_t Nw = w1 - w0;
+  const int64_t L = c.L, w0 = c.w0, w1 = c.w1, Nw = w1 - w0;
+  const int kq = c.k;
   if (Nw <= 0) return q.release();
   const bool aligned = (reinterpret_cast<uintptr_t>(d_seq) & 15) == 0;
   const uint32_t nt = tiles_for(Nw);
-  // rows are written into a guessed capacity before the total is known (no host round trip
-  // inside the query); a query with more rows than the guess -- heavy repeats -- is redone
-  // by the two-pass path into an exact buffer
-  uint64_t cap = (uint64_t)Nw + ((uint64_t)Nw >> 3) + 64;
-  if (!runs_mode) q->rows.reset(cap);
+  uint64_t cap = query_rows_guess(Nw);
+  if (!c.runs) q->rows.reset(cap);
   // probe / scan / emit.  (A one-pass probe + look-back + emit was measured slower and removed
   // in round 4: config 2 0.403 against 0.365 ms; re-measured round 3 with the diagonal path,
   // self query 94 -> 53 Gbp/s -- a tile that has probed waits for its predecessors' totals
   // while holding its CU slot, and the probe is occupancy / latency bound.)
   uint64_t H = 0;
-  // diagonal path (k_query_probe): a position index queried at its own k
-  const int64_t nA = idx->L - idx->k + 1;
-  const char* de = test_build_knob("KMHG_QUERY_DIAG");
   // (a part query too: its anchors and verified windows count only where the part owns the key,
   // and its tags and repeated-key bits come from its own table, k_query_probe<..., PART>)
-  const bool diag_ok = !(de && de[0] == '0') && kq == idx->k && idx->sources == 0 && nA > 0 &&
-                       idx->U > 0 && idx->dcodes.p;
-  bool diag = diag_ok;
-  if (diag && !idx->ps_ready.load(std::memory_order_acquire)) {
-    std::lock_guard<std::mutex> lk(idx->ps_mu);
-    if (!idx->ps_ready.load(std::memory_order_relaxed) && !idx->ps_failed) {
-      if (!idx->tags_built) {
-        try {
-          idx->ptag.reset(idx->slots() + 32);  // + the 32-B span the last probe group reads
-        } catch (const Error& e) {             // no room for the tags: table probes only
-          if (e.code != KMHG_ENOMEM) throw;
-          idx->ps_failed = true;
-          (void)hipGetLastError();
-        }
-      }
-      if (idx->tags_built) {                   // the build wrote the tags and repeat bits
-        idx->dcodes.bind(s);
-        const DiagBlock db = idx->diag_block_of();
-        LAUNCH("k_diag_valid", s, launch_diag_valid(db.nbit, idx->L, idx->k, db.uniq, true, s));
-        HIPC(hipStreamSynchronize(s));
-        idx->ps_ready.store(true, std::memory_order_release);
-      } else if (!idx->ps_failed) {
-        idx->ptag.bind(s);
-        idx->dcodes.bind(s);
-        const DiagBlock db = idx->diag_block_of();
-        LAUNCH("k_diag_prep", s,
-               launch_diag_prep(db.nbit, idx->L, idx->k, db.uniq, idx->table.p, idx->slots(),
-                                idx->positions.p, idx->ptag.p, s));
-        // once per index: later queries may run on other streams
-        HIPC(hipStreamSynchronize(s));
-        idx->ps_ready.store(true, std::memory_order_release);
-      }
-    }
-  }
-  diag = diag && idx->ps_ready.load(std::memory_order_acquire);
+  const char* de = test_build_knob("KMHG_QUERY_DIAG");
+  const bool diag = diag_eligible(kq, idx->k, idx->sources, idx->L - idx->k + 1, idx->U,
+                                  idx->dcodes.p != nullptr, !(de && de[0] == '0')) &&
+                    ensure_diag(idx, s);
 
   DBuf<uint32_t> qrec(Nw, s);         // per window: 0, the one hit's position, or multi
   DBuf<uint2> qmulti(Nw, s);          // {count, first index}: written for multi-hit windows only
@@ -1270,11 +1299,11 @@ kmhg_query* query_device(kmhg_index* idx, const uint8_t* d_seq, int64_t L, int k
   LAUNCH("k_query_probe", s,
          launch_query_probe(d_seq, L, kq, idx->table.p, idx->geom, qrec.p, qmulti.p, w0, w1, aligned,
                             tile_row0, s, diag ? idx->diag_view() : DiagIdx{nullptr, nullptr, 0},
-                            diag && tags_on() ? idx->ptag.p : nullptr, elist.p + nt, rc));
+                            diag && tags_on() ? idx->ptag.p : nullptr, elist.p + nt, c.rc));
   LAUNCH("k_scan_tiles_u64", s, launch_scan_u64(tile_row0, nt, total, tiles.p + nt, s));
-  if (runs_mode) {
+  if (c.runs) {
     // the rows as diagonal runs, made from the window records (k_qruns_*); rows written only
-    // when runs would not be smaller (12 B per run against 8 B per row)
+    // when runs would not be smaller (runs_pay)
     DBuf<uint64_t> rtiles((size_t)nt + scan_u64_scratch(nt), s);
     PinnedRec hrec2 = PinnedPool::get().take();
     GiveBack give_back2{hrec2, s};
@@ -1286,7 +1315,7 @@ kmhg_query* query_device(kmhg_index* idx, const uint8_t* d_seq, int64_t L, int k
     const uint64_t NR = __atomic_load_n(n_runs, __ATOMIC_ACQUIRE);
     q->H = (int64_t)H;
     if (H > (uint64_t)INT32_MAX) fail(KMHG_EOVERFLOW, "result has more than 2^31-1 rows");
-    if (H && 3 * NR < 2 * H) {
+    if (runs_pay(H, NR)) {
       q->runs.reset(3 * NR);
       q->n_runs = (int64_t)NR;
       LAUNCH("k_qruns_emit", s,
@@ -1303,12 +1332,12 @@ kmhg_query* query_device(kmhg_index* idx, const uint8_t* d_seq, int64_t L, int k
   HIPC(hipStreamSynchronize(s));
   H = __atomic_load_n(total, __ATOMIC_ACQUIRE);
   q->H = (int64_t)H;
-  if (part_query) {              // the tile offsets stay with the query (the root's merge)
+  if (c.part) {                  // the tile offsets stay with the query (the root's merge)
     tiles.bind(s);
     q->tile_off.swap_with(tiles);
     q->n_tiles = nt;
   }
-  if (H <= cap) {
+  if (!needs_exact_redo(H, cap)) {
     rg.synced = true;                            // nothing queued behind the synchronize
     return q.release();
   }
@@ -2196,20 +2225,8 @@ std::vector<int> query_devices() {
   if (!e || !*e) return out;
   int n = 0;
   HIPC(hipGetDeviceCount(&n));
-  const std::string str(e);
-  size_t a = 0;
-  while (a <= str.size()) {
-    size_t b = str.find(',', a);
-    if (b == std::string::npos) b = str.size();
-    const std::string tok = str.substr(a, b - a);
-    char* end = nullptr;
-    const long d = std::strtol(tok.c_str(), &end, 10);
-    if (tok.empty() || *end || d < 0 || d >= n)
-      fail(KMHG_EINVAL, "KMHG_DEVICES must list device ordinals (0.." + std::to_string(n - 1) +
-                            "), got \"" + str + "\"");
-    out.push_back((int)d);
-    a = b + 1;
-  }
+  const DeviceList bad = parse_device_list(e, n, out);
+  if (bad.code != KMHG_OK) fail(bad.code, bad.text);
   return out;
 }
 
@@ -2262,7 +2279,7 @@ kmhg_index* replica_on(kmhg_index* home, int dev) {
   return r;
 }
 
-kmhg_query* query_multi_device(kmhg_index* idx, const char* seq, int64_t L, int k,
+kmhg_query* query_multi_device(kmhg_index* idx, const char* seq, const QueryCall& whole,
                                const std::vector<int>& devs) {
   {
     DeviceGuard g(idx->device);
@@ -2270,63 +2287,39 @@ kmhg_query* query_multi_device(kmhg_index* idx, const char* seq, int64_t L, int 
     if (idx->canonical) fail(KMHG_EINVAL, "External pointer has incorrect tag");
   }
   const int G = (int)devs.size();
-  const int64_t Nw = L - k + 1;
+  const int64_t L = whole.L;
   auto q = std::make_unique<kmhg_query>();
   q->device = idx->device;
-  std::vector<kmhg_query*> parts(G, nullptr);
-  std::vector<Error> errs(G, Error{KMHG_OK, ""});
+  q->parts.assign(G, nullptr);                       // freed with q, also on the error path
   const bool poison = test_build_knob("KMHG_SLICE_POISON") != nullptr;   // tests: garbage outside
   // tests: parts after the first on the index's own device use a same-device replica, so the
   // copy path runs on a one-GPU box too
   const bool test_replica = test_build_knob("KMHG_TEST_REPLICA") != nullptr;
-  auto run = [&](int i) {
-    try {
-      const int64_t w0 = Nw * i / G, w1 = Nw * (i + 1) / G;
-      const bool home = devs[i] == idx->device && !(test_replica && i > 0);
-      kmhg_index* use = home ? idx : replica_on(idx, devs[i]);
-      DeviceGuard g(devs[i]);
-      hipStream_t s = lib_stream();
-      // a full-length buffer holding only chars [a, b): the window rule of windows [w0, w1)
-      // reads chars [w0 - 1, w1 + k - 1); the tile stage's aligned loads and halo read a few
-      // more around them, which feed only windows outside the range
-      const int64_t a = std::max<int64_t>(0, (w0 & ~15ll) - 64);
-      const int64_t b = std::min<int64_t>(L, w1 + k + 64);
-      DBuf<uint8_t> d((size_t)L + 16, s);
-      if (poison) HIPC(hipMemsetAsync(d.p, 'A', (size_t)L + 16, s));
-      if (b > a) h2d_host(d.p + a, seq + a, (size_t)(b - a), s);
-      parts[i] = query_device(use, d.p, L, k, w0, w1, s);
-      HIPC(hipStreamSynchronize(s));
-    } catch (const Error& e) {
-      errs[i] = e;
-    } catch (const std::bad_alloc&) {
-      errs[i] = Error{KMHG_ENOMEM, "host allocation failed"};
-    }
-  };
   // one host thread per distinct device; the parts of one device run in order on its thread
   // (they share that device's stream and index copy)
-  std::vector<int> uniq;
-  for (int d : devs)
-    if (std::find(uniq.begin(), uniq.end(), d) == uniq.end()) uniq.push_back(d);
-  auto run_device = [&](int d) {
-    for (int i = 0; i < G; ++i)
-      if (devs[i] == d) run(i);
-  };
-  std::vector<std::thread> th;
-  for (size_t u = 1; u < uniq.size(); ++u) th.emplace_back(run_device, uniq[u]);
-  run_device(uniq[0]);
-  for (auto& t : th) t.join();
-  q->parts = parts;                                  // freed with q, also on the error path
-  for (int i = 0; i < G; ++i)
-    if (errs[i].code != KMHG_OK) {
-      free_query(q.release());
-      fail(errs[i].code, errs[i].msg);
-    }
-  int64_t off = 0;
-  for (auto* p : parts) {
-    q->part_off.push_back(off);
-    off += p->H;
+  const Error bad = for_parts(devs, [&](int i) {
+    const Span64 w = shard_windows(whole.w1, i, G);
+    const bool home = devs[i] == idx->device && !(test_replica && i > 0);
+    kmhg_index* use = home ? idx : replica_on(idx, devs[i]);
+    DeviceGuard g(devs[i]);
+    hipStream_t s = lib_stream();
+    // a full-length buffer holding only the chars the part's windows may read (shard_chars)
+    const Span64 ch = shard_chars(L, whole.k, w.begin, w.end);
+    DBuf<uint8_t> d((size_t)L + 16, s);
+    if (poison) HIPC(hipMemsetAsync(d.p, 'A', (size_t)L + 16, s));
+    if (ch.end > ch.begin)
+      h2d_host(d.p + ch.begin, seq + ch.begin, (size_t)(ch.end - ch.begin), s);
+    q->parts[i] = query_device(
+        use, d.p, checked(query_call_range((size_t)L, whole.k, w.begin, w.end)), s);
+    HIPC(hipStreamSynchronize(s));
+  });
+  if (bad.code != KMHG_OK) {
+    free_query(q.release());
+    fail(bad.code, bad.msg);
   }
-  q->H = off;
+  std::vector<int64_t> rows;
+  for (auto* p : q->parts) rows.push_back(p->H);
+  q->H = part_offsets(rows, q->part_off);
   return q.release();
 }
 
@@ -3055,57 +3048,60 @@ int kmhg_pairs_run_device(kmhg_index* a, kmhg_index* b, void* stream, kmhg_query
   });
 }
 
+// The host-pointer entries (kmhg_query_run, kmhg_query_run_rc) on the index's device: the
+// string goes up as it is -- the forward one for rc too, no reversed copy anywhere -- and the
+// call is checked again at its C length.
+static void query_host(kmhg_index* idx, const char* seq, size_t L, int k, bool rc, kmhg_query** q,
+                       int64_t* n_rows) {
+  if (L < H2D_SCAN_MIN || k < 1 || k > 31 || L >= (size_t)INT32_MAX) {
+    L = effective_len(seq, L);             // (as kmhg_build)
+    check_query_args(L, k);
+  }
+  DeviceGuard g(idx->device);
+  hipStream_t s = lib_stream();
+  DBuf<uint8_t> d(L + 16, s);
+  L = h2d_cstring(d.p, seq, L, s);
+  *q = query_device(idx, d.p, checked(query_call(L, k)).on_rc(rc), s);
+  HIPC(hipStreamSynchronize(s));
+  if (n_rows) *n_rows = (*q)->H;
+}
+
+// The device-pointer entries: `c` names the query, `stream` is the caller's (NULL = HIP null
+// stream).
+static void query_entry(kmhg_index* idx, const void* d_seq, const QueryCall& c, void* stream,
+                        kmhg_query** q, int64_t* n_rows, int64_t* n_runs = nullptr) {
+  if (!idx || !d_seq || !q) fail(KMHG_EINVAL, "null argument");
+  checked(c);
+  DeviceGuard g(idx->device);
+  *q = query_device(idx, static_cast<const uint8_t*>(d_seq), c, (hipStream_t)stream);
+  if (n_rows) *n_rows = (*q)->H;
+  if (n_runs) *n_runs = (*q)->n_runs;
+}
+
 int kmhg_query_run(kmhg_index* idx, const char* seq, size_t L, int k, kmhg_query** q,
                    int64_t* n_rows) {
   return guarded([&] {
     if (!idx || !seq || !q) fail(KMHG_EINVAL, "null argument");
     const std::vector<int> devs = query_devices();
     if (devs.size() > 1 && idx->sources == 0) {   // position index over several devices
-      L = effective_len(seq, L);
-      check_query_args(L, k);
-      *q = query_multi_device(idx, seq, (int64_t)L, k, devs);
+      *q = query_multi_device(idx, seq, checked(query_call(effective_len(seq, L), k)), devs);
       if (n_rows) *n_rows = (*q)->H;
       return;
     }
-    if (L < H2D_SCAN_MIN || k < 1 || k > 31 || L >= (size_t)INT32_MAX) {
-      L = effective_len(seq, L);             // (as kmhg_build)
-      check_query_args(L, k);
-    }
-    DeviceGuard g(idx->device);
-    hipStream_t s = lib_stream();
-    DBuf<uint8_t> d(L + 16, s);
-    L = h2d_cstring(d.p, seq, L, s);
-    check_query_args(L, k);
-    *q = query_device(idx, d.p, (int64_t)L, k, 0, (int64_t)L - k + 1, s);
-    HIPC(hipStreamSynchronize(s));
-    if (n_rows) *n_rows = (*q)->H;
+    query_host(idx, seq, L, k, false, q, n_rows);
   });
 }
 
 int kmhg_query_run_device(kmhg_index* idx, const void* d_seq, size_t L, int k, void* stream,
                           kmhg_query** q, int64_t* n_rows) {
-  return guarded([&] {
-    if (!idx || !d_seq || !q) fail(KMHG_EINVAL, "null argument");
-    check_query_args(L, k);
-    DeviceGuard g(idx->device);
-    hipStream_t s = (hipStream_t)stream;   // caller stream; NULL = HIP null stream
-    *q = query_device(idx, (const uint8_t*)d_seq, (int64_t)L, k, 0, (int64_t)L - k + 1, s);
-    if (n_rows) *n_rows = (*q)->H;
-  });
+  return guarded([&] { query_entry(idx, d_seq, query_call(L, k), stream, q, n_rows); });
 }
 
 int kmhg_query_run_device_range(kmhg_index* idx, const void* d_seq, size_t L, int k,
                                 int64_t w_begin, int64_t w_end, void* stream, kmhg_query** q,
                                 int64_t* n_rows) {
   return guarded([&] {
-    if (!idx || !d_seq || !q) fail(KMHG_EINVAL, "null argument");
-    check_query_args(L, k);
-    const int64_t Nw = (int64_t)L - k + 1;
-    if (w_begin < 0 || w_end > Nw || w_begin > w_end) fail(KMHG_EINVAL, "window range out of bounds");
-    DeviceGuard g(idx->device);
-    hipStream_t s = (hipStream_t)stream;   // caller stream; NULL = HIP null stream
-    *q = query_device(idx, (const uint8_t*)d_seq, (int64_t)L, k, w_begin, w_end, s);
-    if (n_rows) *n_rows = (*q)->H;
+    query_entry(idx, d_seq, query_call_range(L, k, w_begin, w_end), stream, q, n_rows);
   });
 }
 
@@ -3113,36 +3109,18 @@ int kmhg_query_run_device_range_runs(kmhg_index* idx, const void* d_seq, size_t 
                                      int64_t w_begin, int64_t w_end, void* stream,
                                      kmhg_query** q, int64_t* n_rows, int64_t* n_runs) {
   return guarded([&] {
-    if (!idx || !d_seq || !q) fail(KMHG_EINVAL, "null argument");
-    check_query_args(L, k);
-    const int64_t Nw = (int64_t)L - k + 1;
-    if (w_begin < 0 || w_end > Nw || w_begin > w_end) fail(KMHG_EINVAL, "window range out of bounds");
-    DeviceGuard g(idx->device);
-    hipStream_t s = (hipStream_t)stream;
-    *q = query_device(idx, (const uint8_t*)d_seq, (int64_t)L, k, w_begin, w_end, s, false, true);
-    if (n_rows) *n_rows = (*q)->H;
-    if (n_runs) *n_runs = (*q)->n_runs;
+    query_entry(idx, d_seq, query_call_range(L, k, w_begin, w_end).as_runs(), stream, q, n_rows,
+                n_runs);
   });
 }
 
 // The reverse strand (include/kmhgpu.h): the forward entries' checks and words, the forward
-// sequence on the device, rc = true down to the probe's stage fill.
+// sequence on the device, rc down to the probe's stage fill.
 int kmhg_query_run_rc(kmhg_index* idx, const char* seq, size_t L, int k, kmhg_query** q,
                       int64_t* n_rows) {
   return guarded([&] {
     if (!idx || !seq || !q) fail(KMHG_EINVAL, "null argument");
-    if (L < H2D_SCAN_MIN || k < 1 || k > 31 || L >= (size_t)INT32_MAX) {
-      L = effective_len(seq, L);             // (as kmhg_query_run)
-      check_query_args(L, k);
-    }
-    DeviceGuard g(idx->device);
-    hipStream_t s = lib_stream();
-    DBuf<uint8_t> d(L + 16, s);
-    L = h2d_cstring(d.p, seq, L, s);         // the forward string: no reversed copy anywhere
-    check_query_args(L, k);
-    *q = query_device(idx, d.p, (int64_t)L, k, 0, (int64_t)L - k + 1, s, false, false, true);
-    HIPC(hipStreamSynchronize(s));
-    if (n_rows) *n_rows = (*q)->H;
+    query_host(idx, seq, L, k, true, q, n_rows);
   });
 }
 
@@ -3150,15 +3128,7 @@ int kmhg_query_run_rc_device_range(kmhg_index* idx, const void* d_seq, size_t L,
                                    int64_t w_begin, int64_t w_end, void* stream, kmhg_query** q,
                                    int64_t* n_rows) {
   return guarded([&] {
-    if (!idx || !d_seq || !q) fail(KMHG_EINVAL, "null argument");
-    check_query_args(L, k);
-    const int64_t Nw = (int64_t)L - k + 1;
-    if (w_begin < 0 || w_end > Nw || w_begin > w_end) fail(KMHG_EINVAL, "window range out of bounds");
-    DeviceGuard g(idx->device);
-    hipStream_t s = (hipStream_t)stream;   // caller stream; NULL = HIP null stream
-    *q = query_device(idx, (const uint8_t*)d_seq, (int64_t)L, k, w_begin, w_end, s, false, false,
-                      true);
-    if (n_rows) *n_rows = (*q)->H;
+    query_entry(idx, d_seq, query_call_range(L, k, w_begin, w_end).on_rc(), stream, q, n_rows);
   });
 }
 
@@ -3166,17 +3136,14 @@ int kmhg_query_run_rc_device_range_runs(kmhg_index* idx, const void* d_seq, size
                                         int64_t w_begin, int64_t w_end, void* stream,
                                         kmhg_query** q, int64_t* n_rows, int64_t* n_runs) {
   return guarded([&] {
-    if (!idx || !d_seq || !q) fail(KMHG_EINVAL, "null argument");
-    check_query_args(L, k);
-    const int64_t Nw = (int64_t)L - k + 1;
-    if (w_begin < 0 || w_end > Nw || w_begin > w_end) fail(KMHG_EINVAL, "window range out of bounds");
-    DeviceGuard g(idx->device);
-    hipStream_t s = (hipStream_t)stream;
-    *q = query_device(idx, (const uint8_t*)d_seq, (int64_t)L, k, w_begin, w_end, s, false, true,
-                      true);
-    if (n_rows) *n_rows = (*q)->H;
-    if (n_runs) *n_runs = (*q)->n_runs;
+    query_entry(idx, d_seq, query_call_range(L, k, w_begin, w_end).as_runs().on_rc(), stream, q,
+                n_rows, n_runs);
   });
+}
+
+int kmhg_query_run_device_part(kmhg_index* part, const void* d_seq, size_t L, int k,
+                               void* stream, kmhg_query** q, int64_t* n_rows) {
+  return guarded([&] { query_entry(part, d_seq, query_call(L, k).of_part(), stream, q, n_rows); });
 }
 
 int kmhg_query_runs_device(kmhg_query* q, const int32_t** d_runs) {
@@ -3184,18 +3151,6 @@ int kmhg_query_runs_device(kmhg_query* q, const int32_t** d_runs) {
     if (!q || !d_runs) fail(KMHG_EINVAL, "null argument");
     if (q->n_runs < 0) fail(KMHG_EINVAL, "the query holds rows, not runs");
     *d_runs = q->runs.p;
-  });
-}
-
-int kmhg_query_run_device_part(kmhg_index* part, const void* d_seq, size_t L, int k,
-                               void* stream, kmhg_query** q, int64_t* n_rows) {
-  return guarded([&] {
-    if (!part || !d_seq || !q) fail(KMHG_EINVAL, "null argument");
-    check_query_args(L, k);
-    DeviceGuard g(part->device);
-    *q = query_device(part, (const uint8_t*)d_seq, (int64_t)L, k, 0, (int64_t)L - k + 1,
-                      (hipStream_t)stream, true);
-    if (n_rows) *n_rows = (*q)->H;
   });
 }
 
@@ -3364,23 +3319,15 @@ int kmhg_query_fill(kmhg_query* q, int32_t* rows) {
     if (!q->H) return;
     if (!rows) fail(KMHG_EINVAL, "null output");
     if (!q->parts.empty() && !q->gathered) {   // every part straight into its rows, in parallel
-      std::vector<Error> errs(q->parts.size(), Error{KMHG_OK, ""});
-      auto copy = [&](size_t i) {
-        try {
-          kmhg_query* p = q->parts[i];
-          if (!p->H) return;
-          DeviceGuard g(p->device);
-          rows_to_host(p->rows.p, (uint64_t)p->H, rows + 2 * q->part_off[i], lib_stream());
-        } catch (const Error& e) {
-          errs[i] = e;
-        }
-      };
-      std::vector<std::thread> th;
-      for (size_t i = 1; i < q->parts.size(); ++i) th.emplace_back(copy, i);
-      copy(0);
-      for (auto& t : th) t.join();
-      for (auto& e : errs)
-        if (e.code != KMHG_OK) fail(e.code, e.msg);
+      std::vector<int> each(q->parts.size());
+      std::iota(each.begin(), each.end(), 0);
+      const Error bad = for_parts(each, [&](int i) {
+        kmhg_query* p = q->parts[i];
+        if (!p->H) return;
+        DeviceGuard g(p->device);
+        rows_to_host(p->rows.p, (uint64_t)p->H, rows + 2 * q->part_off[i], lib_stream());
+      });
+      if (bad.code != KMHG_OK) fail(bad.code, bad.msg);
       return;
     }
     DeviceGuard g(q->device);

@@ -6,6 +6,7 @@
 // kmhg_khash.h (the khash row-order replay), kmhg_plan.h (the partitioned build's plan),
 // kmhg_hostwork.h (the readout's worker pool, stripes and row expansions), kmhg_reads.h (the host
 // side of read counting), kmhg_pool.h (the device block pool, over a fake device),
+// kmhg_querycall.h (the query entries' calls, rules and multi-device split),
 // oracle/kmer_oracle.c and oracle/sh_oracle.c.  host_check_tsan is this file under
 // ThreadSanitizer (tests/test_host_work.py, tests/test_pool_host.py).
 //
@@ -49,6 +50,16 @@
 //                                           the return value, the records, and every kept read's
 //                                           length and has_qual with FNV sums over all batches
 //   host_check spectrum-status <S> <comb,...> <comb_inner,...>   spectrum_status
+// kmhg_querycall.h (tests/test_query_host.py), one field=value line per call:
+//   host_check query call <L> <k> [<w_begin> <w_end>]   query_call / query_call_range: "err=<code>
+//                                           msg=<text>" or the call's fields
+//   host_check query rules guess=<Nw> | runs_pay=<H>,<NR> | redo=<H>,<cap> |
+//                          diag=<kq>,<index k>,<sources>,<index windows>,<U>,<codes 0|1>,<knob 0|1> ...
+//                                           query_rows_guess, runs_pay, needs_exact_redo,
+//                                           diag_eligible: one line per argument
+//   host_check query devices <text> <n>     parse_device_list: "err=.. msg=.." or devices=<d,...>
+//   host_check query shards <L> <k> <G>     shard_windows and shard_chars of every part: w0 w1 c0 c1
+//   host_check query offsets <H,...>        part_offsets: total and off
 // kmhg_pool.h (tests/test_pool_host.py): BlockPool over FakeDev, whose blocks are malloc'ed bytes
 // and whose events are the integers 1, 2, ... in the order they were made
 //   host_check pool <script>                one operation per line of the file, one line of state
@@ -87,6 +98,7 @@
 #include "../../kmer_hasher_amd/csrc/kmhg_hostwork.h"
 #include "../../kmer_hasher_amd/csrc/kmhg_pool.h"
 #include "../../kmer_hasher_amd/csrc/kmhg_reads.h"
+#include "../../kmer_hasher_amd/csrc/kmhg_querycall.h"
 
 extern "C" {
 long orc_windows(const char* seq, long L, int k, uint64_t* keys, int32_t* s, int32_t* e);
@@ -743,11 +755,87 @@ static int cmd_spectrum_status(uint32_t S, const char* comb_csv, const char* inn
   return 0;
 }
 
+// ---------------------------------------------------------------------------- kmhg_querycall.h
+static long long ll(const char* s) { return strtoll(s, nullptr, 10); }
+
+static int cmd_query(int argc, char** argv) {
+  using namespace kmhg;
+  const std::string m = argv[2];
+  if (m == "call" && (argc == 5 || argc == 7)) {
+    const size_t L = (size_t)strtoull(argv[3], nullptr, 10);
+    const QueryCall c = argc == 5 ? query_call(L, atoi(argv[4]))
+                                  : query_call_range(L, atoi(argv[4]), ll(argv[5]), ll(argv[6]));
+    const QueryCall f = c.of_part().as_runs().on_rc();       // the modes keep call and refusal
+    if (f.code != c.code || f.text != c.text || f.w0 != c.w0 || f.w1 != c.w1 || !f.part ||
+        !f.runs || !f.rc)
+      return 1;
+    if (c.code) printf("err=%d msg=%s\n", c.code, c.text);
+    else
+      printf("err=0 L=%" PRId64 " k=%d w0=%" PRId64 " w1=%" PRId64 " part=%d runs=%d rc=%d\n", c.L,
+             c.k, c.w0, c.w1, c.part ? 1 : 0, c.runs ? 1 : 0, c.rc ? 1 : 0);
+    return 0;
+  }
+  if (m == "rules") {
+    for (int i = 3; i < argc; ++i) {
+      std::vector<long long> v;
+      const char* eq = strchr(argv[i], '=');
+      if (!eq) return 2;
+      std::istringstream is(eq + 1);
+      for (std::string w; std::getline(is, w, ',');) v.push_back(ll(w.c_str()));
+      const std::string name(argv[i], (size_t)(eq - argv[i]));
+      if (name == "guess" && v.size() == 1)
+        printf("guess=%" PRIu64 "\n", query_rows_guess(v[0]));
+      else if (name == "runs_pay" && v.size() == 2)
+        printf("runs_pay=%d\n", runs_pay((uint64_t)v[0], (uint64_t)v[1]) ? 1 : 0);
+      else if (name == "redo" && v.size() == 2)
+        printf("redo=%d\n", needs_exact_redo((uint64_t)v[0], (uint64_t)v[1]) ? 1 : 0);
+      else if (name == "diag" && v.size() == 7)
+        printf("diag=%d\n", diag_eligible((int)v[0], (int)v[1], (uint32_t)v[2], v[3], (uint64_t)v[4],
+                                          v[5] != 0, v[6] != 0) ? 1 : 0);
+      else
+        return 2;
+    }
+    return 0;
+  }
+  if (m == "devices" && argc == 5) {
+    std::vector<int> out;
+    const DeviceList bad = parse_device_list(argv[3], atoi(argv[4]), out);
+    if (bad.code) { printf("err=%d msg=%s\n", bad.code, bad.text.c_str()); return 0; }
+    printf("err=0 devices=");
+    for (size_t i = 0; i < out.size(); ++i) printf("%s%d", i ? "," : "", out[i]);
+    printf("\n");
+    return 0;
+  }
+  if (m == "shards" && argc == 6) {
+    const int64_t L = ll(argv[3]);
+    const int k = atoi(argv[4]), G = atoi(argv[5]);
+    for (int i = 0; i < G; ++i) {
+      const Span64 w = shard_windows(L - k + 1, i, G);
+      const Span64 c = shard_chars(L, k, w.begin, w.end);
+      printf("w0=%" PRId64 " w1=%" PRId64 " c0=%" PRId64 " c1=%" PRId64 "\n", w.begin, w.end,
+             c.begin, c.end);
+    }
+    return 0;
+  }
+  if (m == "offsets" && argc == 4) {
+    std::vector<int64_t> H, off;
+    std::istringstream is(argv[3]);
+    for (std::string w; std::getline(is, w, ',');) H.push_back(ll(w.c_str()));
+    const int64_t total = part_offsets(H, off);
+    printf("total=%" PRId64 " off=", total);
+    for (size_t i = 0; i < off.size(); ++i) printf("%s%" PRId64, i ? "," : "", off[i]);
+    printf("\n");
+    return 0;
+  }
+  return 2;
+}
+
 int main(int argc, char** argv) {
   if (argc < 3) { fprintf(stderr, "usage: see the file header\n"); return 2; }
   const std::string c = argv[1];
   if (c == "plan") return cmd_plan(argc, argv);
   if (c == "misc") return cmd_misc(argc, argv);
+  if (c == "query") return cmd_query(argc, argv);
   if (c == "stripes" && argc == 5)
     return cmd_stripes(strtoull(argv[2], nullptr, 10), atoi(argv[3]), strtoull(argv[4], nullptr, 10));
   if (c == "runs" && argc == 6 && atoi(argv[4]) > 0)
