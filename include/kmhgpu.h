@@ -318,6 +318,47 @@ int kmhg_segs_copy_device(kmhg_segs *g, void *d_dst, void *stream);
 int kmhg_segs_fill(kmhg_segs *g, int32_t *segs);                 /* host, 3 * n_segs int32 */
 int kmhg_segs_free(kmhg_segs *g);
 
+/* seq.kmer.blocks (not in the reference): the diagonal segments merged across small gaps.
+ * Input: rows R as for seq.kmer.segs -- i, j >= 1, strictly ascending by (i, j), n_rows < 2^31 --
+ * and three parameters, min_len >= 1, max_gap >= 0, min_hits >= 1.
+ *  1. G = the maximal diagonal segments of R with len >= min_len: exactly the result of
+ *     kmhg_rows_segments(..., min_len).
+ *  2. On each diagonal d = j - i, G's segments are ordered by i.  For consecutive segments a, b
+ *     of one diagonal, gap(a, b) = b.i - (a.i + a.len); segments are maximal, so it is >= 1.  A
+ *     segment dropped by min_len does not take part: the gap between its kept neighbours spans it.
+ *  3. A block is a maximal chain of consecutive kept segments of one diagonal in which every gap
+ *     is <= max_gap.
+ *  4. A block's record is four int32 {i, j, span, hits}: i, j are those of its first segment;
+ *     span = last.i + last.len - i, the windows from its first row to its last inclusive (at most
+ *     2^31 - 1); hits = the sum of len, the rows of R in the block.  span - hits is the sum of its
+ *     gaps.
+ *  5. Only blocks with hits >= min_hits are kept.
+ *  6. Blocks are ordered by the (i, j) of their first row (first rows are distinct rows of R).
+ * So max_gap = 0 gives the segments as (i, j, len, len); any max_gap >= 2^31 - 2 gives one block
+ * per diagonal that has a kept segment; the hits of all blocks at min_hits = 1 sum to the len of
+ * all kept segments; and raising max_gap only ever unions blocks.  With max_gap = k one isolated
+ * substitution between two sequences, which removes k consecutive windows from a diagonal, is
+ * bridged.  The result is 4 x B int32 in R's column-major order and the same bytes on every run.
+ *
+ * kmhg_rows_blocks / kmhg_query_blocks take their rows as kmhg_rows_segments /
+ * kmhg_query_segments do (n_rows = 0 gives an empty handle and d_rows is not read; a KMHG_DEVICES
+ * query is gathered first; a handle that holds runs is refused in kmhg_query_segments' words).
+ * Refusals, KMHG_EINVAL, before any device work and in this order: "null argument"; "min_len must
+ * be a positive integer"; "max_gap must not be negative"; "min_hits must be a positive integer";
+ * "bad row count".  The row faults keep seq.kmer.segs' words.  min_len, max_gap or min_hits beyond
+ * int32 are legal: they give an empty result, or "any gap".  The kmhg_blocks handle owns the
+ * result as a kmhg_segs handle does (kmhg_blocks_fill: 4 * n_blocks int32);
+ * kmhg_blocks_free(NULL) is a no-op. */
+typedef struct kmhg_blocks kmhg_blocks;
+int kmhg_rows_blocks(const void *d_rows, int64_t n_rows, int64_t min_len, int64_t max_gap,
+                     int64_t min_hits, void *stream, kmhg_blocks **out, int64_t *n_blocks);
+int kmhg_query_blocks(kmhg_query *q, int64_t min_len, int64_t max_gap, int64_t min_hits,
+                      kmhg_blocks **out, int64_t *n_blocks);
+int kmhg_blocks_device(kmhg_blocks *b, const int32_t **d_blocks, int64_t *n_blocks);
+int kmhg_blocks_copy_device(kmhg_blocks *b, void *d_dst, void *stream);
+int kmhg_blocks_fill(kmhg_blocks *b, int32_t *blocks);           /* host, 4 * n_blocks int32 */
+int kmhg_blocks_free(kmhg_blocks *b);
+
 /* kmer.pairs <- .Call("kmer_pair_pos", ptr_a, ptr_b)           src/kmer_hash.c:1174-1203
  * Rows (a, b) = (position in index a, position in index b) for every k-mer both indices hold:
  * a's k-mers in a's kmer.pos row order (kmhg_set_row_order), a's positions outer, b's inner;

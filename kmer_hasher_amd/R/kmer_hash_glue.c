@@ -18,6 +18,8 @@
  *   kmer_spectrum_suffix_hash(ptr, max)     src/kmer_hash.c:993-1008  -> REALSXP
  *   sequence_kmer_positions_rc(ptr, seq, k) (not in the reference)    -> INTSXP 2 x H
  *   sequence_kmer_segments(ptr, seq, k, min_len, rc) (not in the reference) -> INTSXP 3 x S
+ *   sequence_kmer_blocks(ptr, seq, k, max_gap, min_len, min_hits, rc) (not in the reference)
+ *                                                                     -> INTSXP 4 x B
  *
  * Differences, all deliberate: the finaliser frees the whole payload (the reference leaks the
  * 32-B khash_ptr, src/kmer_hash.c:56-66); a freed pointer is detected instead of dereferenced;
@@ -205,6 +207,52 @@ SEXP sequence_kmer_segments(SEXP ptr_r, SEXP seq_r, SEXP k_r, SEXP min_len_r, SE
   SEXP ret = PROTECT(allocMatrix(INTSXP, 3, (int)n));
   rc = kmhg_segs_fill(g, INTEGER(ret));
   kmhg_segs_free(g);
+  if (rc != KMHG_OK) error("%s", kmhg_last_error());
+  UNPROTECT(1);
+  return ret;
+}
+
+/* Not in the reference: the segments of sequence_kmer_segments merged, on every diagonal, across
+ * gaps of at most max_gap windows (kmhg_query_blocks, include/kmhgpu.h).  Returns INTSXP 4 x B of
+ * (i, j, span, hits), ordered by (i, j): span = the windows from the block's first row to its
+ * last, hits = its rows; only segments of at least min_len rows take part and only blocks of at
+ * least min_hits rows are kept.  The argument checks come first, in the C-ABI's words and order
+ * after the sequence's and k's own; the pointer must be a position index.  Exported, not
+ * registered, like sequence_kmer_segments. */
+SEXP sequence_kmer_blocks(SEXP ptr_r, SEXP seq_r, SEXP k_r, SEXP max_gap_r, SEXP min_len_r,
+                          SEXP min_hits_r, SEXP rc_r) {
+  if (TYPEOF(seq_r) != STRSXP || length(seq_r) != 1) error("seq_r should be a single sequence");
+  if (TYPEOF(k_r) != INTSXP || length(k_r) != 1) error("k should be an integer of length 1");
+  if (TYPEOF(min_len_r) != INTSXP || length(min_len_r) != 1 || INTEGER(min_len_r)[0] < 1)
+    error("min_len must be a positive integer");
+  if (TYPEOF(max_gap_r) != INTSXP || length(max_gap_r) != 1 || INTEGER(max_gap_r)[0] < 0)
+    error("max_gap must not be negative");
+  if (TYPEOF(min_hits_r) != INTSXP || length(min_hits_r) != 1 || INTEGER(min_hits_r)[0] < 1)
+    error("min_hits must be a positive integer");
+  if (TYPEOF(rc_r) != INTSXP || length(rc_r) != 1) error("rc should be an integer of length 1");
+  kmhg_index *idx = gpu_index_of(ptr_r);
+  kmhg_info inf;
+  if (kmhg_index_info(idx, &inf) != KMHG_OK) error("%s", kmhg_last_error());
+  if (inf.kind != 0) error("blocks need a position index");
+  int k = asInteger(k_r);
+  SEXP s = STRING_ELT(seq_r, 0);
+  kmhg_query *q = NULL;
+  kmhg_blocks *b = NULL;
+  int64_t h = 0, n = 0;
+  if ((INTEGER(rc_r)[0] ? kmhg_query_run_rc : kmhg_query_run)(idx, CHAR(s), (size_t)length(s), k,
+                                                              &q, &h) != KMHG_OK)
+    error("%s", kmhg_last_error());
+  int rc = kmhg_query_blocks(q, INTEGER(min_len_r)[0], INTEGER(max_gap_r)[0],
+                             INTEGER(min_hits_r)[0], &b, &n);
+  kmhg_query_free(q);
+  if (rc != KMHG_OK) error("%s", kmhg_last_error());
+  if (n > INT_MAX) {
+    kmhg_blocks_free(b);
+    error("result has more than 2^31-1 columns (R matrix limit)");
+  }
+  SEXP ret = PROTECT(allocMatrix(INTSXP, 4, (int)n));
+  rc = kmhg_blocks_fill(b, INTEGER(ret));
+  kmhg_blocks_free(b);
   if (rc != KMHG_OK) error("%s", kmhg_last_error());
   UNPROTECT(1);
   return ret;

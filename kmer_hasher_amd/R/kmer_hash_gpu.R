@@ -59,6 +59,23 @@ seq.kmer.segs <- function(ex.ptr, seq, k, min.len=1, rc=FALSE){
     t(m)
 }
 
+## not in the reference: seq.kmer.segs' segments merged across small gaps.  On every diagonal,
+## neighbouring segments whose gap -- the windows between the end of one and the start of the
+## next -- is at most max.gap form one block.  Returns a matrix with columns i, j, span, hits,
+## ordered by (i, j): the block starts at row (i, j), spans span windows of its diagonal from its
+## first row to its last and holds hits rows of seq.kmer.pos's result (span - hits = the sum of
+## its gaps); it covers span + k - 1 bases, drawn with segments(m[,"j"], m[,"i"],
+## m[,"j"] + m[,"span"] - 1, m[,"i"] + m[,"span"] - 1).  max.gap=k bridges an isolated
+## substitution, which removes k consecutive windows; max.gap=0 gives the segments as
+## (i, j, len, len).  min.len drops shorter segments before merging (the gap then spans them),
+## min.hits keeps the blocks of at least that many rows.  Position indices only.
+seq.kmer.blocks <- function(ex.ptr, seq, k, max.gap=k, min.len=1, min.hits=1, rc=FALSE){
+    m <- .Call("sequence_kmer_blocks", ex.ptr, as.character(seq), as.integer(k),
+               as.integer(max.gap), as.integer(min.len), as.integer(min.hits), as.integer(rc))
+    rownames(m) <- c("i", "j", "span", "hits")
+    t(m)
+}
+
 ## shared k-mers of two indices: rows (a, b) = a position in ptr.a with a position in ptr.b
 ## (the reference's version crashes, test.R:330; this one visits only live k-mers, same k)
 kmer.pairs <- function(ptr.a, ptr.b){

@@ -97,6 +97,13 @@ _PROTOS = {
     "kmhg_segs_copy_device": (C.c_int, [vp, vp, vp]),
     "kmhg_segs_fill": (C.c_int, [vp, vp]),
     "kmhg_segs_free": (C.c_int, [vp]),
+    "kmhg_rows_blocks": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp,
+                                   C.POINTER(vp), i64p]),
+    "kmhg_query_blocks": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, C.POINTER(vp), i64p]),
+    "kmhg_blocks_device": (C.c_int, [vp, C.POINTER(vp), i64p]),
+    "kmhg_blocks_copy_device": (C.c_int, [vp, vp, vp]),
+    "kmhg_blocks_fill": (C.c_int, [vp, vp]),
+    "kmhg_blocks_free": (C.c_int, [vp]),
     "kmhg_count": (C.c_int, [C.POINTER(vp), C.POINTER(C.c_char_p), C.POINTER(C.c_size_t),
                              C.c_int64, C.c_int, C.c_int, C.c_int]),
     "kmhg_count_device": (C.c_int, [C.POINTER(vp), vp, C.c_size_t, C.c_int, C.c_int, C.c_int,

@@ -230,24 +230,9 @@ def seq_kmer_segs(ex_ptr, seq, k, min_len=1, rc=False) -> np.ndarray:
     least that many rows; with min_len = 1 the segments expand back to exactly the rows.  Only a
     position index (make_kmer_hash) is accepted: a counts index's "positions" are count vectors,
     not ascending."""
-    p = _extract(ex_ptr)
     L = _lib.lib()
-    if p.info().kind != 0:
-        raise KmerHashError("segments need a position index")
-    if isinstance(seq, (list, tuple)) and len(seq) != 1:
-        raise KmerHashError("seq_r should be a single sequence")
-    b = _as_seq_bytes(seq, "seq_r should be a single sequence")
-    if isinstance(k, (list, tuple, np.ndarray)) and len(k) != 1:
-        raise KmerHashError("k should be an integer of length 1")
-    kk = _as_int(k, "k should be an integer of length 1")
-    ml = _as_int(min_len, "min_len must be a positive integer")
-    q = C.c_void_p()
-    h = C.c_int64()
-    rcode = (L.kmhg_query_run_rc if rc else L.kmhg_query_run)(p.handle, b, len(b), kk,
-                                                              C.byref(q), C.byref(h))
-    if rcode == _lib.KMHG_EINVAL:
-        raise KmerHashError(L.kmhg_last_error().decode())
-    _lib.check(rcode)
+    q, _, (ml,) = _dot_plot_query(ex_ptr, seq, k, rc, "segments need a position index",
+                                  [(min_len, "min_len must be a positive integer")])
     g = C.c_void_p()
     n = C.c_int64()
     try:
@@ -262,6 +247,66 @@ def seq_kmer_segs(ex_ptr, seq, k, min_len=1, rc=False) -> np.ndarray:
         L.kmhg_segs_free(g)
         L.kmhg_query_free(q)
     return segs.reshape(-1, 3)
+
+
+def _dot_plot_query(ex_ptr, seq, k, rc, need, ints):
+    """The query handle of seq.kmer.pos (rc=False) or seq.kmer.pos.rc (rc=True) of one sequence
+    against a position index (`need`: the message for any other index), which the caller frees;
+    with it k and the integers of `ints`, (value, message) pairs converted after k and before the
+    query runs (a value of None stands for k)."""
+    p = _extract(ex_ptr)
+    L = _lib.lib()
+    if p.info().kind != 0:
+        raise KmerHashError(need)
+    if isinstance(seq, (list, tuple)) and len(seq) != 1:
+        raise KmerHashError("seq_r should be a single sequence")
+    b = _as_seq_bytes(seq, "seq_r should be a single sequence")
+    if isinstance(k, (list, tuple, np.ndarray)) and len(k) != 1:
+        raise KmerHashError("k should be an integer of length 1")
+    kk = _as_int(k, "k should be an integer of length 1")
+    vals = [kk if v is None else _as_int(v, msg) for v, msg in ints]
+    q = C.c_void_p()
+    h = C.c_int64()
+    rcode = (L.kmhg_query_run_rc if rc else L.kmhg_query_run)(p.handle, b, len(b), kk,
+                                                              C.byref(q), C.byref(h))
+    if rcode == _lib.KMHG_EINVAL:
+        raise KmerHashError(L.kmhg_last_error().decode())
+    _lib.check(rcode)
+    return q, kk, vals
+
+
+def seq_kmer_blocks(ex_ptr, seq, k, max_gap=None, min_len=1, min_hits=1, rc=False) -> np.ndarray:
+    """seq.kmer.blocks (not in the reference): the dot plot of seq against the index as diagonal
+    segments merged across small gaps.
+
+    Takes the segments seq_kmer_segs(ex_ptr, seq, k, min_len, rc) gives and, on every diagonal,
+    joins neighbours whose gap -- the windows between the end of one and the start of the next --
+    is at most max_gap.  Returns a (B, 4) int32 matrix with columns (i, j, span, hits), ordered
+    by (i, j): the block starts at row (i, j), covers span windows of its diagonal from its first
+    row to its last, and holds hits rows of the seq.kmer.pos result (span - hits is the sum of
+    its gaps).  min_hits keeps the blocks with at least that many rows.  max_gap=None means k: one
+    isolated substitution removes k consecutive windows from a diagonal, and a gap of k bridges
+    it.  max_gap = 0 gives the segments themselves as (i, j, len, len).  Only a position index
+    (make_kmer_hash) is accepted."""
+    L = _lib.lib()
+    q, _, (ml, mg, mh) = _dot_plot_query(
+        ex_ptr, seq, k, rc, "blocks need a position index",
+        [(min_len, "min_len must be a positive integer"), (max_gap, "max_gap must not be negative"),
+         (min_hits, "min_hits must be a positive integer")])
+    g = C.c_void_p()
+    n = C.c_int64()
+    try:
+        rcode = L.kmhg_query_blocks(q, ml, mg, mh, C.byref(g), C.byref(n))
+        if rcode == _lib.KMHG_EINVAL:
+            raise KmerHashError(L.kmhg_last_error().decode())
+        _lib.check(rcode)
+        blocks = np.empty(4 * n.value, np.int32)
+        if n.value:
+            _lib.check(L.kmhg_blocks_fill(g, blocks.ctypes.data))
+    finally:
+        L.kmhg_blocks_free(g)
+        L.kmhg_query_free(q)
+    return blocks.reshape(-1, 4)
 
 
 def _seq_kmer_pos(ex_ptr, seq, k, entry) -> np.ndarray:

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "kmhg_common.h"
+#include "kmhg_blocks.h"
 #include "kmhg_kernels.h"
 #include "kmhg_plan.h"
 #include "kmhg_hostwork.h"
@@ -623,6 +624,15 @@ struct kmhg_segs {
   hipStream_t stream = nullptr;
   int64_t S = 0;
   DBuf<int32_t> segs;
+};
+
+// seq.kmer.blocks: the {i, j, span, hits} blocks of some rows (kmhg_rows_blocks), complete when
+// the handle is returned; `stream` is the stream they were made on.
+struct kmhg_blocks {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  int64_t B = 0;
+  DBuf<int32_t> blocks;
 };
 
 namespace {
@@ -3379,23 +3389,29 @@ int kmhg_query_free(kmhg_query* q) {
 // ---------------------------------------------------------------------------- seq.kmer.segs
 namespace {
 
-// The maximal diagonal segments of n_rows ascending rows on the current device (kmhg_segs.hip;
-// include/kmhgpu.h has the definition).  Waits for `s` twice (the number of segments sizes the
-// sort; min_len > 1: the number kept sizes the result) and once more at the end.
-kmhg_segs* rows_segments(const int2* rows, int64_t n_rows, int64_t min_len, hipStream_t s) {
-  auto g = std::make_unique<kmhg_segs>();
-  if (!n_rows) return g.release();      // (no device call: an empty result is host-only)
-  HIPC(hipGetDevice(&g->device));
-  g->stream = s;
-  ReleaseGroup rg(s);
-  const uint64_t n = (uint64_t)n_rows, nt = (n + TILE - 1) / TILE;
+// The front half of the segment pass, which seq.kmer.segs and seq.kmer.blocks share: segment m of
+// the (diagonal, i) order has the pairing keys skey()[m] (its first row) and ekey()[m] (its last)
+// and rank()[m], its first row's rank among all starts in row order.
+struct SegPairs {
+  uint64_t S = 0;
+  DBuf<uint64_t> keys;                  // start, end keys; both sorted
+  DBuf<uint32_t> ranks;
+  const uint64_t* skey() const { return keys.p + 2 * S; }
+  const uint64_t* ekey() const { return keys.p + 3 * S; }
+  const uint32_t* rank() const { return ranks.p + S; }
+};
+
+// Classifies and counts the starts and ends of n ascending rows, waits for `s` once (the number
+// of segments sizes the sort) and answers the two row faults; then, with `pair`, emits the
+// pairing keys and sorts them (kmhg_segs.hip).  hm: the caller's pinned record (n_kmers: the scan
+// totals; n_small / n_large: the faults).
+void segs_sorted_pairs(const int2* rows, uint64_t n, bool pair, BuildMeta* hm, hipStream_t s,
+                       SegPairs& sp) {
+  const uint64_t nt = (n + TILE - 1) / TILE;
   DBuf<uint64_t> tiles(nt + scan_u64_scratch(nt), s);
   DBuf<uint64_t> masks(2 * nt * (TILE / 64), s);
   uint64_t* smask = masks.p;
   uint64_t* emask = masks.p + nt * (TILE / 64);
-  PinnedRec hrec = PinnedPool::get().take();
-  GiveBack give_back{hrec, s};
-  BuildMeta* hm = hrec.meta;            // n_kmers: scan totals; n_small / n_large: input faults
   __atomic_store_n(&hm->n_small, 0u, __ATOMIC_RELEASE);
   __atomic_store_n(&hm->n_large, 0u, __ATOMIC_RELEASE);
   LAUNCH("k_segs_classify", s, launch_segs_classify(rows, n, smask, emask, tiles.p, &hm->n_small,
@@ -3409,25 +3425,48 @@ kmhg_segs* rows_segments(const int2* rows, int64_t n_rows, int64_t min_len, hipS
   const uint64_t S = both & 0xFFFFFFFFull;
   // on every diagonal starts and ends alternate, so there are as many of each
   if (!S || (both >> 32) != S) fail(KMHG_EDEVICE, "segment starts and ends do not pair");
-  if (min_len > INT32_MAX) return g.release();            // no segment has that many rows
-  DBuf<uint64_t> keys(4 * S, s);                          // start, end keys; both sorted
-  DBuf<uint32_t> ranks(2 * S, s);
-  uint64_t *skey = keys.p, *ekey = keys.p + S, *skey_o = keys.p + 2 * S, *ekey_o = keys.p + 3 * S;
-  LAUNCH("k_segs_emit", s, launch_segs_emit(rows, n, smask, emask, tiles.p, skey, ranks.p, ekey, s));
+  if (!pair) return;
+  sp.S = S;
+  sp.keys.reset(4 * S);
+  sp.keys.bind(s);
+  sp.ranks.reset(2 * S);
+  sp.ranks.bind(s);
+  uint64_t *skey = sp.keys.p, *ekey = sp.keys.p + S, *skey_o = sp.keys.p + 2 * S,
+           *ekey_o = sp.keys.p + 3 * S;
+  LAUNCH("k_segs_emit", s,
+         launch_segs_emit(rows, n, smask, emask, tiles.p, skey, sp.ranks.p, ekey, s));
   size_t tb = 0;
   HIPC(segs_sort_temp_bytes(S, &tb));
   DBuf<uint8_t> temp(std::max<size_t>(tb, 16), s);
   hipError_t sort_err = hipSuccess;
-  LAUNCH("k_segs_sort", s, sort_err = launch_segs_sort(skey, ranks.p, ekey, S, skey_o, ranks.p + S,
-                                                       ekey_o, temp.p, tb, s));
+  LAUNCH("k_segs_sort", s, sort_err = launch_segs_sort(skey, sp.ranks.p, ekey, S, skey_o,
+                                                       sp.ranks.p + S, ekey_o, temp.p, tb, s));
   HIPC(sort_err);
+}
+
+// The maximal diagonal segments of n_rows ascending rows on the current device (kmhg_segs.hip;
+// include/kmhgpu.h has the definition).  Waits for `s` twice (the number of segments sizes the
+// sort; min_len > 1: the number kept sizes the result) and once more at the end.
+kmhg_segs* rows_segments(const int2* rows, int64_t n_rows, int64_t min_len, hipStream_t s) {
+  auto g = std::make_unique<kmhg_segs>();
+  if (!n_rows) return g.release();      // (no device call: an empty result is host-only)
+  HIPC(hipGetDevice(&g->device));
+  g->stream = s;
+  ReleaseGroup rg(s);
+  PinnedRec hrec = PinnedPool::get().take();
+  GiveBack give_back{hrec, s};
+  BuildMeta* hm = hrec.meta;
+  SegPairs sp;
+  segs_sorted_pairs(rows, (uint64_t)n_rows, min_len <= INT32_MAX, hm, s, sp);
+  if (min_len > INT32_MAX) return g.release();            // no segment has that many rows
+  const uint64_t S = sp.S;
   if (min_len == 1) {
     g->segs.reset(3 * S);
-    LAUNCH("k_segs_pair", s, launch_segs_pair(skey_o, ranks.p + S, ekey_o, S, g->segs.p, s));
+    LAUNCH("k_segs_pair", s, launch_segs_pair(sp.skey(), sp.rank(), sp.ekey(), S, g->segs.p, s));
     g->S = (int64_t)S;
   } else {
     DBuf<int32_t> all(3 * S, s);
-    LAUNCH("k_segs_pair", s, launch_segs_pair(skey_o, ranks.p + S, ekey_o, S, all.p, s));
+    LAUNCH("k_segs_pair", s, launch_segs_pair(sp.skey(), sp.rank(), sp.ekey(), S, all.p, s));
     const uint64_t nts = (S + TILE - 1) / TILE;
     DBuf<uint64_t> ftiles(nts + scan_u64_scratch(nts), s);
     LAUNCH("k_segs_filter", s, launch_segs_filter_count(all.p, S, (int32_t)min_len, ftiles.p, s));
@@ -3442,6 +3481,86 @@ kmhg_segs* rows_segments(const int2* rows, int64_t n_rows, int64_t min_len, hipS
     g->S = (int64_t)K;
   }
   HIPC(hipStreamSynchronize(s));
+  rg.synced = true;
+  return g.release();
+}
+
+// The blocks of n_rows ascending rows on the current device (kmhg_blocks.hip; include/kmhgpu.h
+// has the definition): the segment pass's sorted keys, filtered by min_len, then heads / mark /
+// place / order.  Waits for `s` where a count sizes an allocation -- the number of segments (the
+// sort), min_len > 1: the number kept, and the number of blocks (the result) -- and once more at
+// the end.  The number of blocks before min_hits stays on the device.
+kmhg_blocks* rows_blocks(const int2* rows, int64_t n_rows, int64_t min_len, int64_t max_gap,
+                         int64_t min_hits, hipStream_t s) {
+  auto g = std::make_unique<kmhg_blocks>();
+  if (!n_rows) return g.release();      // (no device call: an empty result is host-only)
+  HIPC(hipGetDevice(&g->device));
+  g->stream = s;
+  ReleaseGroup rg(s);
+  PinnedRec hrec = PinnedPool::get().take();
+  GiveBack give_back{hrec, s};
+  BuildMeta* hm = hrec.meta;            // n_positions: segments kept; n_pairs: blocks
+  // no segment has 2^31 rows and no block 2^31 hits
+  const bool any = min_len <= INT32_MAX && min_hits <= INT32_MAX;
+  SegPairs sp;
+  segs_sorted_pairs(rows, (uint64_t)n_rows, any, hm, s, sp);
+  if (!any) return g.release();
+  const uint64_t S = sp.S;
+  const uint32_t gap_limit = blk_gap_limit(max_gap);
+  const uint64_t *skey = sp.skey(), *ekey = sp.ekey();
+  const uint32_t* rank = sp.rank();
+  uint64_t K = S;
+  DBuf<uint64_t> fkeys;
+  DBuf<uint32_t> franks;
+  if (min_len > 1) {
+    const uint64_t nts = (S + TILE - 1) / TILE;
+    DBuf<uint64_t> ftiles(nts + scan_u64_scratch(nts), s);
+    LAUNCH("k_blocks_filter", s,
+           launch_blocks_filter_count(skey, ekey, S, (int32_t)min_len, ftiles.p, s));
+    LAUNCH("k_scan_tiles_u64", s,
+           launch_scan_u64(ftiles.p, nts, &hm->n_positions, ftiles.p + nts, s));
+    HIPC(hipStreamSynchronize(s));
+    K = __atomic_load_n(&hm->n_positions, __ATOMIC_ACQUIRE);
+    if (!K) { rg.synced = true; return g.release(); }
+    fkeys.reset(2 * K);
+    fkeys.bind(s);
+    franks.reset(K);
+    franks.bind(s);
+    LAUNCH("k_blocks_filter", s,
+           launch_blocks_filter_emit(skey, ekey, rank, S, (int32_t)min_len, ftiles.p, fkeys.p,
+                                     fkeys.p + K, franks.p, s));
+    skey = fkeys.p;
+    ekey = fkeys.p + K;
+    rank = franks.p;
+  }
+  const uint64_t ntk = (K + TILE - 1) / TILE, nts = (S + TILE - 1) / TILE;
+  DBuf<uint64_t> htiles(ntk + 1 + scan_u64_scratch(ntk), s);   // [ntk]: the scan's total
+  DBuf<uint64_t> bkeys(2 * K, s);                              // per block id: start, end key
+  DBuf<uint32_t> bnum(3 * K, s);                               // rank, len prefix before / after
+  DBuf<uint32_t> slot(S, s);
+  DBuf<uint64_t> otiles(nts + scan_u64_scratch(nts), s);
+  LAUNCH("k_blocks_heads", s, launch_blocks_heads(skey, ekey, K, gap_limit, htiles.p, s));
+  LAUNCH("k_scan_tiles_u64", s,
+         launch_scan_u64(htiles.p, ntk, htiles.p + ntk, htiles.p + ntk + 1, s));
+  LAUNCH("k_blocks_mark", s,
+         launch_blocks_mark(skey, ekey, rank, K, gap_limit, htiles.p, bkeys.p, bkeys.p + K,
+                            bnum.p, bnum.p + K, bnum.p + 2 * K, s));
+  HIPC(hipMemsetAsync(slot.p, 0, (size_t)S * 4, s));
+  LAUNCH("k_blocks_place", s,
+         launch_blocks_place(htiles.p + ntk, K, bnum.p, bnum.p + K, bnum.p + 2 * K,
+                             (uint32_t)min_hits, slot.p, s));
+  LAUNCH("k_blocks_order", s, launch_blocks_order_count(slot.p, S, otiles.p, s));
+  LAUNCH("k_scan_tiles_u64", s, launch_scan_u64(otiles.p, nts, &hm->n_pairs, otiles.p + nts, s));
+  HIPC(hipStreamSynchronize(s));
+  const uint64_t B = __atomic_load_n(&hm->n_pairs, __ATOMIC_ACQUIRE);
+  if (B) {
+    g->blocks.reset(4 * B);
+    LAUNCH("k_blocks_order", s,
+           launch_blocks_order_emit(slot.p, S, otiles.p, bkeys.p, bkeys.p + K, bnum.p + K,
+                                    bnum.p + 2 * K, g->blocks.p, s));
+    g->B = (int64_t)B;
+    HIPC(hipStreamSynchronize(s));
+  }
   rg.synced = true;
   return g.release();
 }
@@ -3514,6 +3633,84 @@ int kmhg_segs_free(kmhg_segs* g) {
     DeviceGuard dg(g->device);
     // the caller keeps the stream it made the segments on alive until here (as for a query)
     HIPC(hipStreamSynchronize(g->stream));
+  });
+}
+
+// -------------------------------------------------------------------------- seq.kmer.blocks
+namespace {
+
+void check_blocks_args(int64_t min_len, int64_t max_gap, int64_t min_hits, kmhg_blocks** out) {
+  if (!out) fail(KMHG_EINVAL, "null argument");
+  if (min_len < 1) fail(KMHG_EINVAL, "min_len must be a positive integer");
+  if (max_gap < 0) fail(KMHG_EINVAL, "max_gap must not be negative");
+  if (min_hits < 1) fail(KMHG_EINVAL, "min_hits must be a positive integer");
+}
+
+}  // namespace
+
+int kmhg_rows_blocks(const void* d_rows, int64_t n_rows, int64_t min_len, int64_t max_gap,
+                     int64_t min_hits, void* stream, kmhg_blocks** out, int64_t* n_blocks) {
+  return guarded([&] {
+    check_blocks_args(min_len, max_gap, min_hits, out);
+    if (n_rows < 0 || n_rows > INT32_MAX) fail(KMHG_EINVAL, "bad row count");
+    if (n_rows && !d_rows) fail(KMHG_EINVAL, "null argument");
+    *out = rows_blocks(static_cast<const int2*>(d_rows), n_rows, min_len, max_gap, min_hits,
+                       (hipStream_t)stream);
+    if (n_blocks) *n_blocks = (*out)->B;
+  });
+}
+
+int kmhg_query_blocks(kmhg_query* q, int64_t min_len, int64_t max_gap, int64_t min_hits,
+                      kmhg_blocks** out, int64_t* n_blocks) {
+  return guarded([&] {
+    if (!q) fail(KMHG_EINVAL, "null argument");
+    check_blocks_args(min_len, max_gap, min_hits, out);
+    if (q->n_runs >= 0) fail(KMHG_EINVAL, "the query holds runs (kmhg_query_runs_device)");
+    if (q->H > INT32_MAX) fail(KMHG_EINVAL, "bad row count");
+    gather_parts(q);                    // a multi-device query's rows, on its home device
+    DeviceGuard g(q->device);
+    *out = rows_blocks(q->rows.p, q->H, min_len, max_gap, min_hits, q->stream);
+    if (n_blocks) *n_blocks = (*out)->B;
+  });
+}
+
+int kmhg_blocks_device(kmhg_blocks* b, const int32_t** d_blocks, int64_t* n_blocks) {
+  return guarded([&] {
+    if (!b || !d_blocks) fail(KMHG_EINVAL, "null argument");
+    *d_blocks = b->B ? b->blocks.p : nullptr;
+    if (n_blocks) *n_blocks = b->B;
+  });
+}
+
+int kmhg_blocks_copy_device(kmhg_blocks* b, void* d_dst, void* stream) {
+  return guarded([&] {
+    if (!b) fail(KMHG_EINVAL, "null argument");
+    if (!b->B) return;
+    if (!d_dst) fail(KMHG_EINVAL, "null output");
+    DeviceGuard dg(b->device);
+    HIPC(hipMemcpyAsync(d_dst, b->blocks.p, (size_t)b->B * 16, hipMemcpyDeviceToDevice,
+                        (hipStream_t)stream));
+  });
+}
+
+int kmhg_blocks_fill(kmhg_blocks* b, int32_t* blocks) {
+  return guarded([&] {
+    if (!b) fail(KMHG_EINVAL, "null argument");
+    if (!b->B) return;
+    if (!blocks) fail(KMHG_EINVAL, "null output");
+    DeviceGuard dg(b->device);
+    d2h_host(blocks, b->blocks.p, (size_t)b->B * 16, lib_stream());
+  });
+}
+
+int kmhg_blocks_free(kmhg_blocks* b) {
+  return guarded([&] {
+    if (!b) return;
+    std::unique_ptr<kmhg_blocks> own(b);
+    if (!b->B) return;
+    DeviceGuard dg(b->device);
+    // the caller keeps the stream it made the blocks on alive until here (as for a query)
+    HIPC(hipStreamSynchronize(b->stream));
   });
 }
 

@@ -147,6 +147,35 @@ void launch_segs_filter_count(const int32_t* segs, uint64_t S, int32_t min_len,
                               uint64_t* tile_cnt, hipStream_t s);
 void launch_segs_filter_emit(const int32_t* segs, uint64_t S, int32_t min_len,
                              const uint64_t* tile_off, int32_t* out, hipStream_t s);
+// the segments merged across gaps into blocks (kmhg_rows_blocks; kmhg_blocks.hip, the arithmetic
+// in kmhg_blocks.h), from the sorted start keys / ranks / end keys of the segment pass.  filter:
+// the three arrays of the segments with len >= min_len, in order (count per TILE segments, scan,
+// emit).  heads: tile_cnt = {sum of len << 32 | block heads} per TILE segments.  mark (tile_off =
+// the scanned tile_cnt): per block id the first segment's start key, rank and the len prefix
+// before it, the last segment's end key and the len prefix after it (arrays of K entries).  place:
+// slot[rank] = id + 1 for the blocks with hits >= min_hits among the first *total & 2^32 - 1 ids
+// (*total: the heads scan's total, device memory; slot: S u32, zeroed by the caller).  order: the
+// records {i, j, span, hits} of the non-zero slots, in slot order (count per TILE slots, scan, emit;
+// out 16-byte aligned).
+void launch_blocks_filter_count(const uint64_t* skey, const uint64_t* ekey, uint64_t S,
+                                int32_t min_len, uint64_t* tile_cnt, hipStream_t s);
+void launch_blocks_filter_emit(const uint64_t* skey, const uint64_t* ekey, const uint32_t* srank,
+                               uint64_t S, int32_t min_len, const uint64_t* tile_off,
+                               uint64_t* fskey, uint64_t* fekey, uint32_t* frank, hipStream_t s);
+void launch_blocks_heads(const uint64_t* skey, const uint64_t* ekey, uint64_t K,
+                         uint32_t gap_limit, uint64_t* tile_cnt, hipStream_t s);
+void launch_blocks_mark(const uint64_t* skey, const uint64_t* ekey, const uint32_t* srank,
+                        uint64_t K, uint32_t gap_limit, const uint64_t* tile_off, uint64_t* bstart,
+                        uint64_t* bend, uint32_t* brank, uint32_t* bpre, uint32_t* bpost,
+                        hipStream_t s);
+void launch_blocks_place(const uint64_t* total, uint64_t K, const uint32_t* brank,
+                         const uint32_t* bpre, const uint32_t* bpost, uint32_t min_hits,
+                         uint32_t* slot, hipStream_t s);
+void launch_blocks_order_count(const uint32_t* slot, uint64_t S, uint64_t* tile_cnt,
+                               hipStream_t s);
+void launch_blocks_order_emit(const uint32_t* slot, uint64_t S, const uint64_t* tile_off,
+                              const uint64_t* bstart, const uint64_t* bend, const uint32_t* bpre,
+                              const uint32_t* bpost, int32_t* out, hipStream_t s);
 // exclusive u64 scan in place, *total <- sum: one workgroup up to SCAN1_MAX entries, else
 // reduce-then-scan with `scratch` = scan_u64_scratch(n) u64
 // (round 4: one workgroup up to 64 K / 256 K totals instead -- config 3 query 185 -> 162 Gbp/s,

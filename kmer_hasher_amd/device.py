@@ -475,15 +475,24 @@ def runs_expand(runs: torch.Tensor, n_rows: int, out: torch.Tensor, stream=None)
     return out
 
 
-def _segs_tensor(h: C.c_void_p, n: int, device) -> torch.Tensor:
-    """The (S, 3) int32 tensor of a kmhg_segs handle, which it owns (rows_view's contract)."""
-    g = _DeviceSegs(h)
+def _handle_tensor(kind: str, h: C.c_void_p, n: int, cols: int, device) -> torch.Tensor:
+    """The (n, cols) int32 tensor of a kmhg_segs or kmhg_blocks handle (kind "segs" or "blocks"),
+    which it owns (rows_view's contract)."""
+    g = _DeviceRecords(kind, h)
     if not n:
         g.free()
-        return torch.empty((0, 3), dtype=torch.int32, device=device)
+        return torch.empty((0, cols), dtype=torch.int32, device=device)
     d = C.c_void_p()
-    _lib.check(_lib.lib().kmhg_segs_device(h, C.byref(d), None))
-    return torch.as_tensor(_RowsBuffer(g, d.value, (n, 3)), device=device)
+    _lib.check(getattr(_lib.lib(), f"kmhg_{kind}_device")(h, C.byref(d), None))
+    return torch.as_tensor(_RowsBuffer(g, d.value, (n, cols)), device=device)
+
+
+def _segs_tensor(h: C.c_void_p, n: int, device) -> torch.Tensor:
+    return _handle_tensor("segs", h, n, 3, device)
+
+
+def _blocks_tensor(h: C.c_void_p, n: int, device) -> torch.Tensor:
+    return _handle_tensor("blocks", h, n, 4, device)
 
 
 def rows_segments(rows: torch.Tensor, min_len: int = 1, stream=None) -> torch.Tensor:
@@ -504,15 +513,35 @@ def rows_segments(rows: torch.Tensor, min_len: int = 1, stream=None) -> torch.Te
     return _segs_tensor(g, n.value, rows.device)
 
 
-class _DeviceSegs:
-    """Owner of a kmhg_segs handle (freed with the last tensor made from it)."""
+def rows_blocks(rows: torch.Tensor, max_gap: int, min_len: int = 1, min_hits: int = 1,
+                stream=None) -> torch.Tensor:
+    """kmhg_rows_blocks (seq.kmer.blocks): the segments rows_segments(rows, min_len) gives, merged
+    on every diagonal across gaps of at most max_gap windows, as a (B, 4) int32 tensor of
+    {i, j, span, hits} ordered by (i, j): span = the windows from the block's first row to its
+    last, hits = its rows.  min_hits keeps the blocks of at least that many rows
+    (include/kmhgpu.h).  Synchronous."""
+    if not (rows.is_cuda and rows.dtype == torch.int32 and rows.dim() == 2 and rows.shape[1] == 2):
+        raise TypeError("rows must be an (H, 2) torch.int32 CUDA tensor")
+    rows = rows.contiguous()
+    g = C.c_void_p()
+    n = C.c_int64()
+    with torch.cuda.device(rows.device):
+        _lib.check(_lib.lib().kmhg_rows_blocks(
+            C.c_void_p(rows.data_ptr() if rows.shape[0] else None), rows.shape[0], int(min_len),
+            int(max_gap), int(min_hits), _stream_ptr(stream), C.byref(g), C.byref(n)))
+    return _blocks_tensor(g, n.value, rows.device)
 
-    def __init__(self, h: C.c_void_p):
+
+class _DeviceRecords:
+    """Owner of a kmhg_segs or kmhg_blocks handle (freed with the last tensor made from it)."""
+
+    def __init__(self, kind: str, h: C.c_void_p):
+        self._kind = kind
         self._h = h
 
     def free(self):
         if self._h:
-            _lib.lib().kmhg_segs_free(self._h)
+            getattr(_lib.lib(), f"kmhg_{self._kind}_free")(self._h)
             self._h = C.c_void_p(0)
 
     def __del__(self):
@@ -576,6 +605,16 @@ class DeviceQuery:
         n = C.c_int64()
         _lib.check(_lib.lib().kmhg_query_segments(self._h, int(min_len), C.byref(g), C.byref(n)))
         return _segs_tensor(g, n.value, self.device)
+
+    def blocks(self, max_gap: int, min_len: int = 1, min_hits: int = 1) -> torch.Tensor:
+        """kmhg_query_blocks: this query's segments merged across gaps of at most max_gap windows,
+        (B, 4) int32 {i, j, span, hits} on the query's device (rows_blocks of its rows; a
+        KMHG_DEVICES query is gathered there first)."""
+        g = C.c_void_p()
+        n = C.c_int64()
+        _lib.check(_lib.lib().kmhg_query_blocks(self._h, int(min_len), int(max_gap), int(min_hits),
+                                                C.byref(g), C.byref(n)))
+        return _blocks_tensor(g, n.value, self.device)
 
     def runs_view(self, n_runs: int) -> torch.Tensor:
         """The (n_runs, 3) int32 runs of a runs query (kmhg_query_runs_device), as a tensor that
