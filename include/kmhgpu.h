@@ -359,6 +359,49 @@ int kmhg_blocks_copy_device(kmhg_blocks *b, void *d_dst, void *stream);
 int kmhg_blocks_fill(kmhg_blocks *b, int32_t *blocks);           /* host, 4 * n_blocks int32 */
 int kmhg_blocks_free(kmhg_blocks *b);
 
+/* seq.kmer.raster (not in the reference): the dot plot as a binned count matrix, the one product
+ * whose size does not grow with the number of hits.  The rows R are (i, j) int32 rows as for
+ * seq.kmer.segs.  A frame is six int64 {i_lo, j_lo, bin_i, bin_j, n_i, n_j} with
+ *   i_lo, j_lo >= 1;  bin_i, bin_j >= 1;  n_i, n_j >= 1;  n_i * n_j <= 2^26 cells;
+ *   i_lo + n_i * bin_i - 1 <= 2^31 - 1 and j_lo + n_j * bin_j - 1 <= 2^31 - 1.
+ * The result is n_i * n_j uint32 counts, cell (bi, bj) at index bi + n_i * bj (R's column-major
+ * order of an n_i x n_j matrix):
+ *   M[bi, bj] = #{ (i, j) in R : i_lo <= i, (i - i_lo) / bin_i == bi < n_i,
+ *                                j_lo <= j, (j - j_lo) / bin_j == bj < n_j }
+ * with integer division.  Rows outside the frame are not counted and are no error.  Integer adds
+ * commute, so the result is the same bytes on every run.
+ * Overflow rule: rows are distinct, so a cell holds at most min(H, bin_i * bin_j) of H rows; the
+ * entries refuse with KMHG_EOVERFLOW "a raster cell could exceed 2^32-1 rows" only when
+ * bin_i * bin_j >= 2^32 and H >= 2^32, and nothing saturates otherwise.
+ *
+ * All entries write into caller device memory d_out (n_i * n_j uint32) on `stream` and zero it
+ * themselves.
+ * kmhg_rows_raster: any n_rows < 2^31 rows in device memory -- rc rows, kmer.pairs rows, merged
+ * multi-GPU rows -- in ANY order: unlike segments the rows need not be sorted, there is no order
+ * check and no i, j >= 1 check (such rows lie outside every frame).  n_rows = 0 gives zeros and
+ * d_rows is not read.  Asynchronous on `stream`.
+ * kmhg_query_raster: the rows of a query handle, on its device (a KMHG_DEVICES query is gathered
+ * there first; a handle that holds runs is refused in kmhg_query_segments' words).
+ * kmhg_raster_run_device: the row-free route.  The query (d_seq, L, k; rc != 0: its reverse
+ * strand, as kmhg_query_run_rc) is probed as by kmhg_query_run_device and every hit is added into
+ * its cell straight from the per-window records: no row is written, so *n_rows, the int64 hit
+ * total, may exceed 2^31 - 1 where the query entries refuse.  It gives exactly kmhg_rows_raster of
+ * the rows kmhg_query_run[_rc] would deliver wherever those exist.  The query entries' refusals
+ * hold in their words (k / L, a counts index, a part index); query k need not be the index k;
+ * KMHG_DEVICES is not honoured (the index's own device, as the rc entries).  Synchronous.
+ * kmhg_raster_run: the same from a host string into a host buffer `out` (n_i * n_j uint32).
+ * Refusals, KMHG_EINVAL, before any device work and in this order: "null argument"; "bin widths
+ * must be positive integers"; "bin counts must be positive integers"; "a raster has at most 2^26
+ * cells"; "the frame must lie within 1..2^31-1 on both axes"; then "bad row count" (the rows
+ * entry) or the query entries' own. */
+int kmhg_rows_raster(const void *d_rows, int64_t n_rows, const int64_t frame[6], void *d_out,
+                     void *stream);
+int kmhg_query_raster(kmhg_query *q, const int64_t frame[6], void *d_out, void *stream);
+int kmhg_raster_run_device(kmhg_index *idx, const void *d_seq, size_t L, int k, int rc,
+                           const int64_t frame[6], void *d_out, void *stream, int64_t *n_rows);
+int kmhg_raster_run(kmhg_index *idx, const char *seq, size_t L, int k, int rc,
+                    const int64_t frame[6], uint32_t *out, int64_t *n_rows);
+
 /* kmer.pairs <- .Call("kmer_pair_pos", ptr_a, ptr_b)           src/kmer_hash.c:1174-1203
  * Rows (a, b) = (position in index a, position in index b) for every k-mer both indices hold:
  * a's k-mers in a's kmer.pos row order (kmhg_set_row_order), a's positions outer, b's inner;

@@ -20,6 +20,8 @@
  *   sequence_kmer_segments(ptr, seq, k, min_len, rc) (not in the reference) -> INTSXP 3 x S
  *   sequence_kmer_blocks(ptr, seq, k, max_gap, min_len, min_hits, rc) (not in the reference)
  *                                                                     -> INTSXP 4 x B
+ *   sequence_kmer_raster(ptr, seq, k, bins, rc, i_range, j_range) (not in the reference)
+ *                                                  -> named VECSXP[6], counts REALSXP n_i x n_j
  *
  * Differences, all deliberate: the finaliser frees the whole payload (the reference leaks the
  * 32-B khash_ptr, src/kmer_hash.c:56-66); a freed pointer is detected instead of dereferenced;
@@ -255,6 +257,81 @@ SEXP sequence_kmer_blocks(SEXP ptr_r, SEXP seq_r, SEXP k_r, SEXP max_gap_r, SEXP
   kmhg_blocks_free(b);
   if (rc != KMHG_OK) error("%s", kmhg_last_error());
   UNPROTECT(1);
+  return ret;
+}
+
+/* Not in the reference: the dot plot as a binned count matrix (kmhg_raster_run, include/kmhgpu.h),
+ * made on the device without writing the rows, so its size does not depend on the hit count and
+ * the query's 2^31-row limit does not apply.  bins: one or two bin counts (i, j); i_range /
+ * j_range: c(lo, hi), inclusive and 1-based, or NULL for 1..nchar(seq) and 1..the index's length.
+ * Per axis, width = ceil(range length / bins) and count = ceil(range length / width).  Returns a
+ * named list: counts, a REALSXP n_i x n_j matrix (a cell may exceed INT_MAX), i0, j0, bin_i, bin_j
+ * (integers) and n_rows, the query's hit total (a double: it may exceed INT_MAX).  The argument
+ * checks come first; the pointer must be a position index.  Exported, not registered, like
+ * sequence_kmer_segments. */
+static const char *raster_fields[6] = {"counts", "i0", "j0", "bin_i", "bin_j", "n_rows"};
+
+static int raster_range_ok(SEXP r) {
+  if (TYPEOF(r) == NILSXP) return 1;
+  return TYPEOF(r) == INTSXP && length(r) == 2 && INTEGER(r)[0] >= 1 &&
+         INTEGER(r)[1] >= INTEGER(r)[0];
+}
+
+static void raster_axis(SEXP range_r, int64_t deflt_hi, int64_t bins, int64_t *lo, int64_t *width,
+                        int64_t *n) {
+  *lo = TYPEOF(range_r) == NILSXP ? 1 : INTEGER(range_r)[0];
+  const int64_t hi = TYPEOF(range_r) == NILSXP ? (deflt_hi > 1 ? deflt_hi : 1) : INTEGER(range_r)[1];
+  const int64_t len = hi - *lo + 1;
+  *width = (len + bins - 1) / bins;
+  *n = (len + *width - 1) / *width;
+}
+
+SEXP sequence_kmer_raster(SEXP ptr_r, SEXP seq_r, SEXP k_r, SEXP bins_r, SEXP rc_r, SEXP i_range_r,
+                          SEXP j_range_r) {
+  if (TYPEOF(seq_r) != STRSXP || length(seq_r) != 1) error("seq_r should be a single sequence");
+  if (TYPEOF(k_r) != INTSXP || length(k_r) != 1) error("k should be an integer of length 1");
+  if (TYPEOF(bins_r) != INTSXP || length(bins_r) < 1 || length(bins_r) > 2 ||
+      INTEGER(bins_r)[0] < 1 || INTEGER(bins_r)[length(bins_r) - 1] < 1)
+    error("bins should be one or two positive integers");
+  if (TYPEOF(rc_r) != INTSXP || length(rc_r) != 1 ||
+      INTEGER(rc_r)[0] == INT_MIN) /* NA_integer_ (as.integer(NA)): not a silent reverse strand */
+    error("rc should be an integer of length 1");
+  if (!raster_range_ok(i_range_r)) error("i.range should be c(lo, hi) with 1 <= lo <= hi");
+  if (!raster_range_ok(j_range_r)) error("j.range should be c(lo, hi) with 1 <= lo <= hi");
+  kmhg_index *idx = gpu_index_of(ptr_r);
+  kmhg_info inf;
+  if (kmhg_index_info(idx, &inf) != KMHG_OK) error("%s", kmhg_last_error());
+  if (inf.kind != 0) error("a raster needs a position index");
+  int k = asInteger(k_r);
+  SEXP s = STRING_ELT(seq_r, 0);
+  int64_t f[6];
+  raster_axis(i_range_r, (int64_t)length(s), INTEGER(bins_r)[0], &f[0], &f[2], &f[4]);
+  raster_axis(j_range_r, inf.seq_len, INTEGER(bins_r)[length(bins_r) - 1], &f[1], &f[3], &f[5]);
+  /* (beyond 2^26 cells the library refuses before it writes: one element is enough) */
+  const size_t cells = f[4] * f[5] <= ((int64_t)1 << 26) ? (size_t)(f[4] * f[5]) : 1;
+  uint32_t *m = (uint32_t *)malloc(cells * sizeof(uint32_t));
+  if (!m) error("out of memory");
+  int64_t h = 0;
+  if (kmhg_raster_run(idx, CHAR(s), (size_t)length(s), k, INTEGER(rc_r)[0] != 0, f, m, &h) !=
+      KMHG_OK) {
+    free(m);
+    error("%s", kmhg_last_error());
+  }
+  SEXP ret = PROTECT(allocVector(VECSXP, 6));
+  SEXP nm = PROTECT(allocVector(STRSXP, 6));
+  for (int i = 0; i < 6; ++i) SET_STRING_ELT(nm, i, mkChar(raster_fields[i]));
+  setAttrib(ret, R_NamesSymbol, nm);
+  SEXP counts = SET_VECTOR_ELT(ret, 0, allocMatrix(REALSXP, (int)f[4], (int)f[5]));
+  double *c = REAL(counts);
+  for (size_t e = 0; e < cells; ++e) c[e] = (double)m[e];
+  free(m);
+  for (int i = 0; i < 4; ++i) {
+    SEXP v = SET_VECTOR_ELT(ret, 1 + i, allocVector(INTSXP, 1));
+    INTEGER(v)[0] = (int)f[i];
+  }
+  SEXP hr = SET_VECTOR_ELT(ret, 5, allocVector(REALSXP, 1));
+  REAL(hr)[0] = (double)h;
+  UNPROTECT(2);
   return ret;
 }
 

@@ -76,6 +76,25 @@ seq.kmer.blocks <- function(ex.ptr, seq, k, max.gap=k, min.len=1, min.hits=1, rc
     t(m)
 }
 
+## not in the reference: the dot plot as a binned count matrix, for results too large to hold or
+## plot as points.  The rows of seq.kmer.pos (rc=TRUE: of seq.kmer.pos.rc) are counted per cell on
+## the device and never written, so the result's size does not depend on the number of hits and
+## more than 2^31-1 hits are no obstacle.  bins: the bin count per axis, a scalar or c(i, j);
+## i.range / j.range: c(lo, hi), default 1..nchar(seq) and 1..the index's length; per axis the
+## bin width is ceiling(range length / bins).  Returns a list: counts, a numeric matrix (a cell
+## may exceed .Machine$integer.max) with counts[bi, bj] = the rows with (i - i0) %/% bin_i ==
+## bi - 1 and (j - j0) %/% bin_j == bj - 1; i0, j0, bin_i, bin_j; and n_rows, the hit total.
+## Draw it with
+##   r <- seq.kmer.raster(ptr, seq, k)
+##   image(r$j0 + r$bin_j * (0:ncol(r$counts)), r$i0 + r$bin_i * (0:nrow(r$counts)),
+##         t(log1p(r$counts)), xlab="index", ylab="seq")
+## Position indices only.
+seq.kmer.raster <- function(ex.ptr, seq, k, bins=1024, rc=FALSE, i.range=NULL, j.range=NULL){
+    .Call("sequence_kmer_raster", ex.ptr, as.character(seq), as.integer(k), as.integer(bins),
+          as.integer(rc), if(is.null(i.range)) NULL else as.integer(i.range),
+          if(is.null(j.range)) NULL else as.integer(j.range))
+}
+
 ## shared k-mers of two indices: rows (a, b) = a position in ptr.a with a position in ptr.b
 ## (the reference's version crashes, test.R:330; this one visits only live k-mers, same k)
 kmer.pairs <- function(ptr.a, ptr.b){

@@ -104,6 +104,11 @@ _PROTOS = {
     "kmhg_blocks_copy_device": (C.c_int, [vp, vp, vp]),
     "kmhg_blocks_fill": (C.c_int, [vp, vp]),
     "kmhg_blocks_free": (C.c_int, [vp]),
+    "kmhg_rows_raster": (C.c_int, [vp, C.c_int64, i64p, vp, vp]),
+    "kmhg_query_raster": (C.c_int, [vp, i64p, vp, vp]),
+    "kmhg_raster_run_device": (C.c_int, [vp, vp, C.c_size_t, C.c_int, C.c_int, i64p, vp, vp,
+                                         i64p]),
+    "kmhg_raster_run": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, i64p, vp, i64p]),
     "kmhg_count": (C.c_int, [C.POINTER(vp), C.POINTER(C.c_char_p), C.POINTER(C.c_size_t),
                              C.c_int64, C.c_int, C.c_int, C.c_int]),
     "kmhg_count_device": (C.c_int, [C.POINTER(vp), vp, C.c_size_t, C.c_int, C.c_int, C.c_int,

@@ -309,6 +309,76 @@ def seq_kmer_blocks(ex_ptr, seq, k, max_gap=None, min_len=1, min_hits=1, rc=Fals
     return blocks.reshape(-1, 4)
 
 
+def raster_axis(lo: int, hi: int, bins: int) -> tuple[int, int]:
+    """(bin width, bin count) of `bins` bins over lo..hi: width = ceil(length / bins), then
+    count = ceil(length / width) -- at most `bins`, and the last bin may reach past hi."""
+    n = hi - lo + 1
+    width = -(-n // bins)
+    return width, -(-n // width)
+
+
+def _as_range(r, default_hi: int, what: str) -> tuple[int, int]:
+    if r is None:
+        return 1, default_hi
+    if not isinstance(r, (list, tuple, np.ndarray)) or len(r) != 2:
+        raise KmerHashError(what)
+    lo, hi = _as_int(r[0], what), _as_int(r[1], what)
+    if lo < 1 or hi < lo:
+        raise KmerHashError(what)
+    return lo, hi
+
+
+def seq_kmer_raster(ex_ptr, seq, k, bins=1024, rc=False, i_range=None, j_range=None) -> dict:
+    """seq.kmer.raster (not in the reference): the dot plot of seq against the index as a binned
+    count matrix -- what one draws when the rows themselves are too many to hold or plot.
+
+    Bins the rows of seq.kmer.pos (rc=False) or seq.kmer.pos.rc (rc=True) over i_range x j_range
+    (inclusive 1-based (lo, hi) pairs; default 1..len(seq) and 1..index length) into `bins` bins
+    per axis (a scalar or an (i, j) pair): bin width = ceil(range length / bins), bin count =
+    ceil(range length / width).  Returns {"counts": int64 (n_i, n_j) matrix, "i0", "j0", "bin_i",
+    "bin_j", "n_rows"}: counts[bi, bj] is the number of rows with (i - i0) // bin_i == bi and
+    (j - j0) // bin_j == bj, n_rows the hit total of the whole query (inside the ranges or not).
+    The rows are never written, so the result's size does not depend on the hit count and
+    n_rows may exceed 2^31 - 1 where seq_kmer_pos refuses.  Only a position index
+    (make_kmer_hash) is accepted; runs on the index's device."""
+    p = _extract(ex_ptr)
+    L = _lib.lib()
+    inf = p.info()
+    if inf.kind != 0:
+        raise KmerHashError("a raster needs a position index")
+    if isinstance(seq, (list, tuple)) and len(seq) != 1:
+        raise KmerHashError("seq_r should be a single sequence")
+    b = _as_seq_bytes(seq, "seq_r should be a single sequence")
+    if isinstance(k, (list, tuple, np.ndarray)) and len(k) != 1:
+        raise KmerHashError("k should be an integer of length 1")
+    kk = _as_int(k, "k should be an integer of length 1")
+    msg = "bins should be one or two positive integers"
+    if isinstance(bins, (list, tuple, np.ndarray)):
+        if len(bins) not in (1, 2):
+            raise KmerHashError(msg)
+        nb = [_as_int(x, msg) for x in bins] * (2 if len(bins) == 1 else 1)
+    else:
+        nb = [_as_int(bins, msg)] * 2
+    if min(nb) < 1:
+        raise KmerHashError(msg)
+    i_lo, i_hi = _as_range(i_range, max(len(b), 1), "i.range should be c(lo, hi) with 1 <= lo <= hi")
+    j_lo, j_hi = _as_range(j_range, max(int(inf.seq_len), 1),
+                           "j.range should be c(lo, hi) with 1 <= lo <= hi")
+    bin_i, n_i = raster_axis(i_lo, i_hi, nb[0])
+    bin_j, n_j = raster_axis(j_lo, j_hi, nb[1])
+    frame = (C.c_int64 * 6)(i_lo, j_lo, bin_i, bin_j, n_i, n_j)
+    cells = n_i * n_j
+    out = np.empty(cells if cells <= 1 << 26 else 1, np.uint32)   # (beyond: refused, nothing written)
+    h = C.c_int64()
+    rcode = L.kmhg_raster_run(p.handle, b, len(b), kk, 1 if rc else 0, frame, out.ctypes.data,
+                              C.byref(h))
+    if rcode in (_lib.KMHG_EINVAL, _lib.KMHG_EOVERFLOW):
+        raise KmerHashError(L.kmhg_last_error().decode())
+    _lib.check(rcode)
+    return {"counts": out.astype(np.int64).reshape(n_j, n_i).T, "i0": i_lo, "j0": j_lo,
+            "bin_i": bin_i, "bin_j": bin_j, "n_rows": h.value}
+
+
 def _seq_kmer_pos(ex_ptr, seq, k, entry) -> np.ndarray:
     p = _extract(ex_ptr)
     if isinstance(seq, (list, tuple)) and len(seq) != 1:

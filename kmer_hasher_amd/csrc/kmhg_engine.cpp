@@ -3714,6 +3714,144 @@ int kmhg_blocks_free(kmhg_blocks* b) {
   });
 }
 
+// -------------------------------------------------------------------------- seq.kmer.raster
+namespace {
+
+static RasterFrame checked_frame(const int64_t* frame) {
+  const RasterFrame f = raster_frame(frame);
+  const RasterRefusal r = raster_check_frame(f);
+  if (r.code != KMHG_OK) fail(r.code, r.text);
+  return f;
+}
+
+static size_t raster_cells(const RasterFrame& f) { return (size_t)(f.n_i * f.n_j); }
+
+static void raster_rows(const int2* rows, int64_t n_rows, const RasterFrame& f, uint32_t* d_out,
+                        hipStream_t s) {
+  HIPC(hipMemsetAsync(d_out, 0, raster_cells(f) * 4, s));
+  if (n_rows)
+    LAUNCH("k_raster_rows", s, launch_raster_rows(rows, (uint64_t)n_rows, raster_dev(f), d_out, s));
+  HIPC(hipGetLastError());
+}
+
+// The row-free route: query_device's checks and probe, then every hit added into its cell from
+// the window records (k_raster_records) where query_device scans the tile totals into row
+// offsets and writes the rows.  No row buffer, no exact-size re-emit and no 2^31 limit: the tile
+// totals are summed only for the hit total, which is returned.  Synchronous.
+static uint64_t raster_device(kmhg_index* idx, const uint8_t* d_seq, const QueryCall& c,
+                              const RasterFrame& f, uint32_t* d_out, hipStream_t s) {
+  ReleaseGroup rg(s);
+  if (idx->canonical) fail(KMHG_EINVAL, "External pointer has incorrect tag");
+  if (idx->is_part != c.part)
+    fail(KMHG_EINVAL, idx->is_part ? "a part index must be assembled before it is queried"
+                                   : "not a part of an owner-computes build");
+  finish_build(idx);
+  idx->stream = s;
+  HIPC(hipMemsetAsync(d_out, 0, raster_cells(f) * 4, s));
+  const int64_t L = c.L, w0 = c.w0, w1 = c.w1, Nw = w1 - w0;
+  const int kq = c.k;
+  if (Nw <= 0) {
+    HIPC(hipStreamSynchronize(s));
+    return 0;
+  }
+  const bool aligned = (reinterpret_cast<uintptr_t>(d_seq) & 15) == 0;
+  const uint32_t nt = tiles_for(Nw);
+  const char* de = test_build_knob("KMHG_QUERY_DIAG");
+  const bool diag = diag_eligible(kq, idx->k, idx->sources, idx->L - idx->k + 1, idx->U,
+                                  idx->dcodes.p != nullptr, !(de && de[0] == '0')) &&
+                    ensure_diag(idx, s);
+  DBuf<uint32_t> qrec(Nw, s);
+  DBuf<uint2> qmulti(Nw, s);
+  DBuf<uint64_t> tiles((size_t)nt + scan_u64_scratch(nt), s);
+  PinnedRec hrec = PinnedPool::get().take();
+  GiveBack give_back{hrec, s};
+  uint64_t* total = &hrec.meta->n_kmers;
+  LAUNCH("k_query_probe", s,
+         launch_query_probe(d_seq, L, kq, idx->table.p, idx->geom, qrec.p, qmulti.p, w0, w1, aligned,
+                            tiles.p, s, diag ? idx->diag_view() : DiagIdx{nullptr, nullptr, 0},
+                            diag && tags_on() ? idx->ptag.p : nullptr, nullptr, c.rc));
+  LAUNCH("k_scan_tiles_u64", s, launch_scan_u64(tiles.p, nt, total, tiles.p + nt, s));
+  if ((uint64_t)f.bin_i * (uint64_t)f.bin_j >= (1ull << 32)) {
+    // only such a frame can overflow a cell: the total is read before any add
+    HIPC(hipStreamSynchronize(s));
+    if (raster_may_overflow(f, __atomic_load_n(total, __ATOMIC_ACQUIRE)))
+      fail(KMHG_EOVERFLOW, "a raster cell could exceed 2^32-1 rows");
+  }
+  LAUNCH("k_raster_records", s,
+         launch_raster_records(qrec.p, qmulti.p, Nw, w0, kq, idx->positions.p, raster_dev(f), d_out,
+                               s));
+  HIPC(hipStreamSynchronize(s));
+  rg.synced = true;
+  return __atomic_load_n(total, __ATOMIC_ACQUIRE);
+}
+
+}  // namespace
+
+int kmhg_rows_raster(const void* d_rows, int64_t n_rows, const int64_t frame[6], void* d_out,
+                     void* stream) {
+  return guarded([&] {
+    if (!frame || !d_out) fail(KMHG_EINVAL, "null argument");
+    const RasterFrame f = checked_frame(frame);
+    if (n_rows < 0 || n_rows > INT32_MAX) fail(KMHG_EINVAL, "bad row count");
+    if (n_rows && !d_rows) fail(KMHG_EINVAL, "null argument");
+    raster_rows(static_cast<const int2*>(d_rows), n_rows, f, static_cast<uint32_t*>(d_out),
+                (hipStream_t)stream);
+  });
+}
+
+int kmhg_query_raster(kmhg_query* q, const int64_t frame[6], void* d_out, void* stream) {
+  return guarded([&] {
+    if (!q || !frame || !d_out) fail(KMHG_EINVAL, "null argument");
+    const RasterFrame f = checked_frame(frame);
+    if (q->n_runs >= 0) fail(KMHG_EINVAL, "the query holds runs (kmhg_query_runs_device)");
+    if (q->H > INT32_MAX) fail(KMHG_EINVAL, "bad row count");
+    gather_parts(q);                    // a multi-device query's rows, on its home device
+    DeviceGuard g(q->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (s != q->stream) {               // order after the emit kernel queued on q->stream
+      hipEvent_t ev;
+      HIPC(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+      HIPC(hipEventRecord(ev, q->stream));
+      HIPC(hipStreamWaitEvent(s, ev, 0));
+      HIPC(hipEventDestroy(ev));
+    }
+    raster_rows(q->rows.p, q->H, f, static_cast<uint32_t*>(d_out), s);
+  });
+}
+
+int kmhg_raster_run_device(kmhg_index* idx, const void* d_seq, size_t L, int k, int rc,
+                           const int64_t frame[6], void* d_out, void* stream, int64_t* n_rows) {
+  return guarded([&] {
+    if (!idx || !d_seq || !frame || !d_out) fail(KMHG_EINVAL, "null argument");
+    const RasterFrame f = checked_frame(frame);
+    const QueryCall c = checked(query_call(L, k)).on_rc(rc != 0);
+    DeviceGuard g(idx->device);
+    const uint64_t H = raster_device(idx, static_cast<const uint8_t*>(d_seq), c, f,
+                                     static_cast<uint32_t*>(d_out), (hipStream_t)stream);
+    if (n_rows) *n_rows = (int64_t)H;
+  });
+}
+
+int kmhg_raster_run(kmhg_index* idx, const char* seq, size_t L, int k, int rc,
+                    const int64_t frame[6], uint32_t* out, int64_t* n_rows) {
+  return guarded([&] {
+    if (!idx || !seq || !frame || !out) fail(KMHG_EINVAL, "null argument");
+    const RasterFrame f = checked_frame(frame);
+    if (L < H2D_SCAN_MIN || k < 1 || k > 31 || L >= (size_t)INT32_MAX) {
+      L = effective_len(seq, L);             // (as kmhg_query_run)
+      check_query_args(L, k);
+    }
+    DeviceGuard g(idx->device);
+    hipStream_t s = lib_stream();
+    DBuf<uint8_t> d(L + 16, s);
+    DBuf<uint32_t> m(raster_cells(f), s);
+    L = h2d_cstring(d.p, seq, L, s);
+    const uint64_t H = raster_device(idx, d.p, checked(query_call(L, k)).on_rc(rc != 0), f, m.p, s);
+    d2h_host(out, m.p, raster_cells(f) * 4, s);
+    if (n_rows) *n_rows = (int64_t)H;
+  });
+}
+
 int kmhg_image_sizes_get(const kmhg_index* cidx, kmhg_image_sizes* sz, int64_t header[8]) {
   return guarded([&] {
     if (!cidx || !sz || !header) fail(KMHG_EINVAL, "null argument");

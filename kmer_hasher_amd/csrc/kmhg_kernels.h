@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "kmhg_common.h"
 #include "kmhg_plan.h"
+#include "kmhg_raster.h"
 
 namespace kmhg {
 
@@ -176,6 +177,15 @@ void launch_blocks_order_count(const uint32_t* slot, uint64_t S, uint64_t* tile_
 void launch_blocks_order_emit(const uint32_t* slot, uint64_t S, const uint64_t* tile_off,
                               const uint64_t* bstart, const uint64_t* bend, const uint32_t* bpre,
                               const uint32_t* bpost, int32_t* out, hipStream_t s);
+// seq.kmer.raster (kmhg_raster.hip, the arithmetic in kmhg_raster.h): out[cell] += the rows of
+// each cell of the checked frame f; out = n_i * n_j u32, zeroed by the caller.  rows: n plain
+// (i, j) rows in any order.  records: the rows of a probed query (qrec / qmulti of Nw windows from
+// w0, launch_query_probe), never written.
+void launch_raster_rows(const int2* rows, uint64_t n, const RasterDev& f, uint32_t* out,
+                        hipStream_t s);
+void launch_raster_records(const uint32_t* qrec, const uint2* qmulti, int64_t Nw, int64_t w0,
+                           int kq, const int32_t* positions, const RasterDev& f, uint32_t* out,
+                           hipStream_t s);
 // exclusive u64 scan in place, *total <- sum: one workgroup up to SCAN1_MAX entries, else
 // reduce-then-scan with `scratch` = scan_u64_scratch(n) u64
 // (round 4: one workgroup up to 64 K / 256 K totals instead -- config 3 query 185 -> 162 Gbp/s,

@@ -181,6 +181,22 @@ class DeviceIndex:
             return "rows", dq.rows_view(), h.value
         return "runs", dq.runs_view(nr.value), h.value
 
+    def raster(self, seq: torch.Tensor, k: int, frame, rc: bool = False,
+               out: torch.Tensor | None = None, stream=None) -> tuple[torch.Tensor, int]:
+        """kmhg_raster_run_device (seq.kmer.raster, the row-free route): the rows of query(seq, k)
+        -- of query_rc(seq, k) with rc -- binned into the frame (i_lo, j_lo, bin_i, bin_j, n_i,
+        n_j) without ever being written: (int64 (n_i, n_j) counts, n_rows), n_rows the hit total,
+        which may exceed 2^31 - 1 where query() refuses.  Equal to rows_raster of the query's
+        rows wherever those exist.  Synchronous."""
+        _check_seq(seq)
+        fr, f, out = _raster_args(frame, out, seq.device)
+        h = C.c_int64()
+        with torch.cuda.device(seq.device):
+            _lib.check(_lib.lib().kmhg_raster_run_device(
+                self._h, C.c_void_p(seq.data_ptr()), seq.numel(), k, 1 if rc else 0, fr,
+                C.c_void_p(out.data_ptr()), _stream_ptr(stream), C.byref(h)))
+        return _raster_matrix(out, f), h.value
+
     def positions(self, opt: int, stream=None) -> dict:
         """kmer.pos into device tensors: {'kmer': uint8 (U, k+1), 'pos': int32 (N, 2),
         'pair.pos': int32 (P, 3), 'count': int32 (U,)} for the requested bits."""
@@ -532,6 +548,46 @@ def rows_blocks(rows: torch.Tensor, max_gap: int, min_len: int = 1, min_hits: in
     return _blocks_tensor(g, n.value, rows.device)
 
 
+def _raster_args(frame, out, device):
+    """The int64[6] frame {i_lo, j_lo, bin_i, bin_j, n_i, n_j} and the int32 tensor of n_i * n_j
+    elements the library fills with u32 bits (`out`, or a new one).  A frame the library will
+    refuse gets a one-element buffer: the refusal comes before anything is written."""
+    f = [int(x) for x in frame]
+    if len(f) != 6:
+        raise ValueError("frame must be (i_lo, j_lo, bin_i, bin_j, n_i, n_j)")
+    cells = f[4] * f[5] if 1 <= f[4] and 1 <= f[5] and f[4] * f[5] <= 1 << 26 else 1
+    if out is None:
+        out = torch.empty(cells, dtype=torch.int32, device=device)
+    if not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and
+            out.numel() >= cells):
+        raise ValueError(f"out must be a contiguous int32 CUDA tensor of >= {cells} elements")
+    return (C.c_int64 * 6)(*f), f, out
+
+
+def _raster_matrix(out: torch.Tensor, f) -> torch.Tensor:
+    """The u32 counts as an int64 (n_i, n_j) tensor (cell (bi, bj) at bi + n_i * bj)."""
+    n_i, n_j = f[4], f[5]
+    return (out[:n_i * n_j].to(torch.int64) & 0xFFFFFFFF).view(n_j, n_i).T
+
+
+def rows_raster(rows: torch.Tensor, frame, out: torch.Tensor | None = None,
+                stream=None) -> torch.Tensor:
+    """kmhg_rows_raster (seq.kmer.raster): (H, 2) int32 device rows, in any order, binned into the
+    frame (i_lo, j_lo, bin_i, bin_j, n_i, n_j): an int64 (n_i, n_j) tensor whose cell [bi, bj]
+    counts the rows with (i - i_lo) // bin_i == bi and (j - j_lo) // bin_j == bj; rows outside
+    the frame are not counted (include/kmhgpu.h).  `out`: the int32 tensor of n_i * n_j elements
+    the library fills (u32 bits)."""
+    if not (rows.is_cuda and rows.dtype == torch.int32 and rows.dim() == 2 and rows.shape[1] == 2):
+        raise TypeError("rows must be an (H, 2) torch.int32 CUDA tensor")
+    rows = rows.contiguous()
+    fr, f, out = _raster_args(frame, out, rows.device)
+    with torch.cuda.device(rows.device):
+        _lib.check(_lib.lib().kmhg_rows_raster(
+            C.c_void_p(rows.data_ptr() if rows.shape[0] else None), rows.shape[0], fr,
+            C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
+    return _raster_matrix(out, f)
+
+
 class _DeviceRecords:
     """Owner of a kmhg_segs or kmhg_blocks handle (freed with the last tensor made from it)."""
 
@@ -615,6 +671,15 @@ class DeviceQuery:
         _lib.check(_lib.lib().kmhg_query_blocks(self._h, int(min_len), int(max_gap), int(min_hits),
                                                 C.byref(g), C.byref(n)))
         return _blocks_tensor(g, n.value, self.device)
+
+    def raster(self, frame, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """kmhg_query_raster: this query's rows binned into `frame`, an int64 (n_i, n_j) tensor on
+        the query's device (rows_raster of its rows; a KMHG_DEVICES query is gathered first)."""
+        fr, f, out = _raster_args(frame, out, self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().kmhg_query_raster(self._h, fr, C.c_void_p(out.data_ptr()),
+                                                    _stream_ptr(stream)))
+        return _raster_matrix(out, f)
 
     def runs_view(self, n_runs: int) -> torch.Tensor:
         """The (n_runs, 3) int32 runs of a runs query (kmhg_query_runs_device), as a tensor that
