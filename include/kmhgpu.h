@@ -308,11 +308,34 @@ int kmhg_query_free(kmhg_query *q);
  * (also for a repeated row); "rows must have i, j >= 1".  The kmhg_segs handle owns the result:
  * kmhg_segs_device gives its device pointer (valid until kmhg_segs_free), kmhg_segs_copy_device
  * copies it into caller device memory on `stream`, kmhg_segs_fill into host memory (3 * n_segs
- * int32).  kmhg_segs_free(NULL) is a no-op. */
+ * int32).  kmhg_segs_free(NULL) is a no-op.
+ *
+ * kmhg_segments_run_device: the row-free route.  The query (d_seq, L, k; rc != 0: its reverse
+ * strand, as kmhg_query_run_rc) is probed as by kmhg_query_run_device, and the segments' first
+ * and last rows are found straight from the per-window records: hit j of window s starts a
+ * segment iff s is the first window, j == 1, or j - 1 is no hit of window s - 1, and ends one iff
+ * s is the last window, j == 2^31 - 1, or j + 1 is no hit of window s + 1 -- the definition above
+ * with each lookup confined to one neighbour window's hits.  No row is written and no buffer
+ * grows with the number of hits, so *n_rows, the int64 hit total, may exceed 2^31 - 1 where
+ * kmhg_rows_segments / kmhg_query_segments refuse ("bad row count").  The result is exactly what
+ * kmhg_query_segments gives on the rows of the same query, byte for byte, wherever those are
+ * accepted; *n_rows = 0 gives an empty handle and is no error.  Refusals, in this order,
+ * KMHG_EINVAL: "null argument"; "min_len must be a positive integer"; the query entries' own for
+ * k / L (KMHG_EOVERFLOW for L >= 2^31 - 1); a counts index made by the .sh route and a part
+ * index in the query entries' words; any other index with sources: "segments need a position
+ * index".  Then, once the totals are known: KMHG_EOVERFLOW "result has more than 2^31-1
+ * segments".  Query k need not be the index k; KMHG_DEVICES is not honoured (the index's own
+ * device, as the rc entries); there is no range variant.  Synchronous on `stream`.
+ * kmhg_segments_run: the same from a host string (read as by kmhg_raster_run). */
 typedef struct kmhg_segs kmhg_segs;
 int kmhg_rows_segments(const void *d_rows, int64_t n_rows, int64_t min_len, void *stream,
                        kmhg_segs **out, int64_t *n_segs);
 int kmhg_query_segments(kmhg_query *q, int64_t min_len, kmhg_segs **out, int64_t *n_segs);
+int kmhg_segments_run_device(kmhg_index *idx, const void *d_seq, size_t L, int k, int rc,
+                             int64_t min_len, void *stream, kmhg_segs **out, int64_t *n_segs,
+                             int64_t *n_rows);
+int kmhg_segments_run(kmhg_index *idx, const char *seq, size_t L, int k, int rc, int64_t min_len,
+                      kmhg_segs **out, int64_t *n_segs, int64_t *n_rows);
 int kmhg_segs_device(kmhg_segs *g, const int32_t **d_segs, int64_t *n_segs);
 int kmhg_segs_copy_device(kmhg_segs *g, void *d_dst, void *stream);
 int kmhg_segs_fill(kmhg_segs *g, int32_t *segs);                 /* host, 3 * n_segs int32 */
@@ -348,12 +371,25 @@ int kmhg_segs_free(kmhg_segs *g);
  * "bad row count".  The row faults keep seq.kmer.segs' words.  min_len, max_gap or min_hits beyond
  * int32 are legal: they give an empty result, or "any gap".  The kmhg_blocks handle owns the
  * result as a kmhg_segs handle does (kmhg_blocks_fill: 4 * n_blocks int32);
- * kmhg_blocks_free(NULL) is a no-op. */
+ * kmhg_blocks_free(NULL) is a no-op.
+ *
+ * kmhg_blocks_run_device / kmhg_blocks_run: the row-free route, kmhg_segments_run_device's front
+ * half followed by the same block passes: exactly what kmhg_query_blocks gives on the rows of the
+ * same query, byte for byte, wherever those are accepted, and defined beyond 2^31 - 1 rows (a
+ * block lies on one diagonal, so its hits stay below 2^31 whatever *n_rows, the hit total, is).
+ * Refusals as kmhg_segments_run_device's, with the three parameter refusals above after "null
+ * argument" and "blocks need a position index" for an index with sources. */
 typedef struct kmhg_blocks kmhg_blocks;
 int kmhg_rows_blocks(const void *d_rows, int64_t n_rows, int64_t min_len, int64_t max_gap,
                      int64_t min_hits, void *stream, kmhg_blocks **out, int64_t *n_blocks);
 int kmhg_query_blocks(kmhg_query *q, int64_t min_len, int64_t max_gap, int64_t min_hits,
                       kmhg_blocks **out, int64_t *n_blocks);
+int kmhg_blocks_run_device(kmhg_index *idx, const void *d_seq, size_t L, int k, int rc,
+                           int64_t min_len, int64_t max_gap, int64_t min_hits, void *stream,
+                           kmhg_blocks **out, int64_t *n_blocks, int64_t *n_rows);
+int kmhg_blocks_run(kmhg_index *idx, const char *seq, size_t L, int k, int rc, int64_t min_len,
+                    int64_t max_gap, int64_t min_hits, kmhg_blocks **out, int64_t *n_blocks,
+                    int64_t *n_rows);
 int kmhg_blocks_device(kmhg_blocks *b, const int32_t **d_blocks, int64_t *n_blocks);
 int kmhg_blocks_copy_device(kmhg_blocks *b, void *d_dst, void *stream);
 int kmhg_blocks_fill(kmhg_blocks *b, int32_t *blocks);           /* host, 4 * n_blocks int32 */

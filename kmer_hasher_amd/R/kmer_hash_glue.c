@@ -20,6 +20,8 @@
  *   sequence_kmer_segments(ptr, seq, k, min_len, rc) (not in the reference) -> INTSXP 3 x S
  *   sequence_kmer_blocks(ptr, seq, k, max_gap, min_len, min_hits, rc) (not in the reference)
  *                                                                     -> INTSXP 4 x B
+ *   sequence_kmer_segments_rf, sequence_kmer_blocks_rf (not in the reference): the two above by
+ *                                                  the route that never writes the positions
  *   sequence_kmer_raster(ptr, seq, k, bins, rc, i_range, j_range) (not in the reference)
  *                                                  -> named VECSXP[6], counts REALSXP n_i x n_j
  *
@@ -181,7 +183,8 @@ SEXP sequence_kmer_positions_rc(SEXP ptr_r, SEXP seq_r, SEXP k_r) {
  * come first, in argument order after the sequence's and k's own words; the pointer must be a
  * position index (a count.kmers pointer's "positions" are count vectors).  Exported, not
  * registered, like sequence_kmer_positions_rc. */
-SEXP sequence_kmer_segments(SEXP ptr_r, SEXP seq_r, SEXP k_r, SEXP min_len_r, SEXP rc_r) {
+static SEXP segments_by(int row_free, SEXP ptr_r, SEXP seq_r, SEXP k_r, SEXP min_len_r,
+                        SEXP rc_r) {
   if (TYPEOF(seq_r) != STRSXP || length(seq_r) != 1) error("seq_r should be a single sequence");
   if (TYPEOF(k_r) != INTSXP || length(k_r) != 1) error("k should be an integer of length 1");
   if (TYPEOF(min_len_r) != INTSXP || length(min_len_r) != 1 || INTEGER(min_len_r)[0] < 1)
@@ -196,11 +199,17 @@ SEXP sequence_kmer_segments(SEXP ptr_r, SEXP seq_r, SEXP k_r, SEXP min_len_r, SE
   kmhg_query *q = NULL;
   kmhg_segs *g = NULL;
   int64_t h = 0, n = 0;
-  if ((INTEGER(rc_r)[0] ? kmhg_query_run_rc : kmhg_query_run)(idx, CHAR(s), (size_t)length(s), k,
-                                                              &q, &h) != KMHG_OK)
-    error("%s", kmhg_last_error());
-  int rc = kmhg_query_segments(q, INTEGER(min_len_r)[0], &g, &n);
-  kmhg_query_free(q);
+  int rc;
+  if (row_free) {
+    rc = kmhg_segments_run(idx, CHAR(s), (size_t)length(s), k, INTEGER(rc_r)[0] != 0,
+                           INTEGER(min_len_r)[0], &g, &n, &h);
+  } else {
+    if ((INTEGER(rc_r)[0] ? kmhg_query_run_rc : kmhg_query_run)(idx, CHAR(s), (size_t)length(s), k,
+                                                                &q, &h) != KMHG_OK)
+      error("%s", kmhg_last_error());
+    rc = kmhg_query_segments(q, INTEGER(min_len_r)[0], &g, &n);
+    kmhg_query_free(q);
+  }
   if (rc != KMHG_OK) error("%s", kmhg_last_error());
   if (n > INT_MAX) {
     kmhg_segs_free(g);
@@ -214,6 +223,17 @@ SEXP sequence_kmer_segments(SEXP ptr_r, SEXP seq_r, SEXP k_r, SEXP min_len_r, SE
   return ret;
 }
 
+SEXP sequence_kmer_segments(SEXP ptr_r, SEXP seq_r, SEXP k_r, SEXP min_len_r, SEXP rc_r) {
+  return segments_by(0, ptr_r, seq_r, k_r, min_len_r, rc_r);
+}
+
+/* sequence_kmer_segments by the route that never writes the positions (kmhg_segments_run,
+ * include/kmhgpu.h): the same arguments, checks and INTSXP 3 x S, byte for byte, and defined where
+ * the positions are more than 2^31-1.  Exported, not registered. */
+SEXP sequence_kmer_segments_rf(SEXP ptr_r, SEXP seq_r, SEXP k_r, SEXP min_len_r, SEXP rc_r) {
+  return segments_by(1, ptr_r, seq_r, k_r, min_len_r, rc_r);
+}
+
 /* Not in the reference: the segments of sequence_kmer_segments merged, on every diagonal, across
  * gaps of at most max_gap windows (kmhg_query_blocks, include/kmhgpu.h).  Returns INTSXP 4 x B of
  * (i, j, span, hits), ordered by (i, j): span = the windows from the block's first row to its
@@ -221,8 +241,8 @@ SEXP sequence_kmer_segments(SEXP ptr_r, SEXP seq_r, SEXP k_r, SEXP min_len_r, SE
  * least min_hits rows are kept.  The argument checks come first, in the C-ABI's words and order
  * after the sequence's and k's own; the pointer must be a position index.  Exported, not
  * registered, like sequence_kmer_segments. */
-SEXP sequence_kmer_blocks(SEXP ptr_r, SEXP seq_r, SEXP k_r, SEXP max_gap_r, SEXP min_len_r,
-                          SEXP min_hits_r, SEXP rc_r) {
+static SEXP blocks_by(int row_free, SEXP ptr_r, SEXP seq_r, SEXP k_r, SEXP max_gap_r,
+                      SEXP min_len_r, SEXP min_hits_r, SEXP rc_r) {
   if (TYPEOF(seq_r) != STRSXP || length(seq_r) != 1) error("seq_r should be a single sequence");
   if (TYPEOF(k_r) != INTSXP || length(k_r) != 1) error("k should be an integer of length 1");
   if (TYPEOF(min_len_r) != INTSXP || length(min_len_r) != 1 || INTEGER(min_len_r)[0] < 1)
@@ -241,12 +261,19 @@ SEXP sequence_kmer_blocks(SEXP ptr_r, SEXP seq_r, SEXP k_r, SEXP max_gap_r, SEXP
   kmhg_query *q = NULL;
   kmhg_blocks *b = NULL;
   int64_t h = 0, n = 0;
-  if ((INTEGER(rc_r)[0] ? kmhg_query_run_rc : kmhg_query_run)(idx, CHAR(s), (size_t)length(s), k,
-                                                              &q, &h) != KMHG_OK)
-    error("%s", kmhg_last_error());
-  int rc = kmhg_query_blocks(q, INTEGER(min_len_r)[0], INTEGER(max_gap_r)[0],
-                             INTEGER(min_hits_r)[0], &b, &n);
-  kmhg_query_free(q);
+  int rc;
+  if (row_free) {
+    rc = kmhg_blocks_run(idx, CHAR(s), (size_t)length(s), k, INTEGER(rc_r)[0] != 0,
+                         INTEGER(min_len_r)[0], INTEGER(max_gap_r)[0], INTEGER(min_hits_r)[0], &b,
+                         &n, &h);
+  } else {
+    if ((INTEGER(rc_r)[0] ? kmhg_query_run_rc : kmhg_query_run)(idx, CHAR(s), (size_t)length(s), k,
+                                                                &q, &h) != KMHG_OK)
+      error("%s", kmhg_last_error());
+    rc = kmhg_query_blocks(q, INTEGER(min_len_r)[0], INTEGER(max_gap_r)[0],
+                           INTEGER(min_hits_r)[0], &b, &n);
+    kmhg_query_free(q);
+  }
   if (rc != KMHG_OK) error("%s", kmhg_last_error());
   if (n > INT_MAX) {
     kmhg_blocks_free(b);
@@ -258,6 +285,18 @@ SEXP sequence_kmer_blocks(SEXP ptr_r, SEXP seq_r, SEXP k_r, SEXP max_gap_r, SEXP
   if (rc != KMHG_OK) error("%s", kmhg_last_error());
   UNPROTECT(1);
   return ret;
+}
+
+SEXP sequence_kmer_blocks(SEXP ptr_r, SEXP seq_r, SEXP k_r, SEXP max_gap_r, SEXP min_len_r,
+                          SEXP min_hits_r, SEXP rc_r) {
+  return blocks_by(0, ptr_r, seq_r, k_r, max_gap_r, min_len_r, min_hits_r, rc_r);
+}
+
+/* sequence_kmer_blocks by the route that never writes the positions (kmhg_blocks_run), as
+ * sequence_kmer_segments_rf.  Exported, not registered. */
+SEXP sequence_kmer_blocks_rf(SEXP ptr_r, SEXP seq_r, SEXP k_r, SEXP max_gap_r, SEXP min_len_r,
+                             SEXP min_hits_r, SEXP rc_r) {
+  return blocks_by(1, ptr_r, seq_r, k_r, max_gap_r, min_len_r, min_hits_r, rc_r);
 }
 
 /* Not in the reference: the dot plot as a binned count matrix (kmhg_raster_run, include/kmhgpu.h),

@@ -59,6 +59,19 @@ seq.kmer.segs <- function(ex.ptr, seq, k, min.len=1, rc=FALSE){
     t(m)
 }
 
+## row.free=TRUE takes the route that never writes seq.kmer.pos's rows: the same matrix, also
+## where the rows are more than 2^31-1 and the function above stops.  The function above stays
+## the rows route; the name is bound again to a dispatcher over the two.
+.seq.kmer.segs.rows <- seq.kmer.segs
+seq.kmer.segs <- function(ex.ptr, seq, k, min.len=1, rc=FALSE, row.free=FALSE){
+    if(length(row.free) != 1 || is.na(row.free)) stop("row.free should be TRUE or FALSE")
+    if(!row.free) return(.seq.kmer.segs.rows(ex.ptr, seq, k, min.len, rc))
+    m <- .Call("sequence_kmer_segments_rf", ex.ptr, as.character(seq), as.integer(k),
+               as.integer(min.len), as.integer(rc))
+    rownames(m) <- c("i", "j", "len")
+    t(m)
+}
+
 ## not in the reference: seq.kmer.segs' segments merged across small gaps.  On every diagonal,
 ## neighbouring segments whose gap -- the windows between the end of one and the start of the
 ## next -- is at most max.gap form one block.  Returns a matrix with columns i, j, span, hits,
@@ -71,6 +84,18 @@ seq.kmer.segs <- function(ex.ptr, seq, k, min.len=1, rc=FALSE){
 ## min.hits keeps the blocks of at least that many rows.  Position indices only.
 seq.kmer.blocks <- function(ex.ptr, seq, k, max.gap=k, min.len=1, min.hits=1, rc=FALSE){
     m <- .Call("sequence_kmer_blocks", ex.ptr, as.character(seq), as.integer(k),
+               as.integer(max.gap), as.integer(min.len), as.integer(min.hits), as.integer(rc))
+    rownames(m) <- c("i", "j", "span", "hits")
+    t(m)
+}
+
+## row.free=TRUE: as in seq.kmer.segs.
+.seq.kmer.blocks.rows <- seq.kmer.blocks
+seq.kmer.blocks <- function(ex.ptr, seq, k, max.gap=k, min.len=1, min.hits=1, rc=FALSE,
+                            row.free=FALSE){
+    if(length(row.free) != 1 || is.na(row.free)) stop("row.free should be TRUE or FALSE")
+    if(!row.free) return(.seq.kmer.blocks.rows(ex.ptr, seq, k, max.gap, min.len, min.hits, rc))
+    m <- .Call("sequence_kmer_blocks_rf", ex.ptr, as.character(seq), as.integer(k),
                as.integer(max.gap), as.integer(min.len), as.integer(min.hits), as.integer(rc))
     rownames(m) <- c("i", "j", "span", "hits")
     t(m)

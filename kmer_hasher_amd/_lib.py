@@ -93,6 +93,10 @@ _PROTOS = {
     "kmhg_query_free": (C.c_int, [vp]),
     "kmhg_rows_segments": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.POINTER(vp), i64p]),
     "kmhg_query_segments": (C.c_int, [vp, C.c_int64, C.POINTER(vp), i64p]),
+    "kmhg_segments_run_device": (C.c_int, [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int64, vp,
+                                           C.POINTER(vp), i64p, i64p]),
+    "kmhg_segments_run": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int64,
+                                    C.POINTER(vp), i64p, i64p]),
     "kmhg_segs_device": (C.c_int, [vp, C.POINTER(vp), i64p]),
     "kmhg_segs_copy_device": (C.c_int, [vp, vp, vp]),
     "kmhg_segs_fill": (C.c_int, [vp, vp]),
@@ -100,6 +104,10 @@ _PROTOS = {
     "kmhg_rows_blocks": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp,
                                    C.POINTER(vp), i64p]),
     "kmhg_query_blocks": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, C.POINTER(vp), i64p]),
+    "kmhg_blocks_run_device": (C.c_int, [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int64, C.c_int64,
+                                         C.c_int64, vp, C.POINTER(vp), i64p, i64p]),
+    "kmhg_blocks_run": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int64,
+                                  C.c_int64, C.c_int64, C.POINTER(vp), i64p, i64p]),
     "kmhg_blocks_device": (C.c_int, [vp, C.POINTER(vp), i64p]),
     "kmhg_blocks_copy_device": (C.c_int, [vp, vp, vp]),
     "kmhg_blocks_fill": (C.c_int, [vp, vp]),

@@ -219,7 +219,7 @@ def seq_kmer_pos_rc(ex_ptr, seq, k) -> np.ndarray:
     return _seq_kmer_pos(ex_ptr, seq, k, "kmhg_query_run_rc")
 
 
-def seq_kmer_segs(ex_ptr, seq, k, min_len=1, rc=False) -> np.ndarray:
+def seq_kmer_segs(ex_ptr, seq, k, min_len=1, rc=False, row_free=False) -> np.ndarray:
     """seq.kmer.segs (not in the reference): the dot plot of seq against the index as maximal
     diagonal segments instead of points.
 
@@ -229,12 +229,24 @@ def seq_kmer_segs(ex_ptr, seq, k, min_len=1, rc=False) -> np.ndarray:
     counts windows; the exact match covers len + k - 1 bases.  min_len keeps the segments of at
     least that many rows; with min_len = 1 the segments expand back to exactly the rows.  Only a
     position index (make_kmer_hash) is accepted: a counts index's "positions" are count vectors,
-    not ascending."""
+    not ascending.
+
+    row_free=True takes the route that never writes the rows (kmhg_segments_run): the same
+    matrix, byte for byte, also where the query has more than 2^31 - 1 rows and the default
+    route refuses; it runs on the index's device."""
     L = _lib.lib()
-    q, _, (ml,) = _dot_plot_query(ex_ptr, seq, k, rc, "segments need a position index",
-                                  [(min_len, "min_len must be a positive integer")])
+    need, ints = "segments need a position index", [(min_len, "min_len must be a positive integer")]
     g = C.c_void_p()
     n = C.c_int64()
+    if row_free:
+        p, b, kk, (ml,) = _dot_plot_args(ex_ptr, seq, k, need, ints)
+        try:
+            rcode = L.kmhg_segments_run(p.handle, b, len(b), kk, 1 if rc else 0, ml, C.byref(g),
+                                        C.byref(n), None)
+            return _records_matrix(L, rcode, L.kmhg_segs_fill, g, n.value, 3)
+        finally:
+            L.kmhg_segs_free(g)
+    q, _, (ml,) = _dot_plot_query(ex_ptr, seq, k, rc, need, ints)
     try:
         rcode = L.kmhg_query_segments(q, ml, C.byref(g), C.byref(n))
         if rcode == _lib.KMHG_EINVAL:
@@ -249,13 +261,22 @@ def seq_kmer_segs(ex_ptr, seq, k, min_len=1, rc=False) -> np.ndarray:
     return segs.reshape(-1, 3)
 
 
-def _dot_plot_query(ex_ptr, seq, k, rc, need, ints):
-    """The query handle of seq.kmer.pos (rc=False) or seq.kmer.pos.rc (rc=True) of one sequence
-    against a position index (`need`: the message for any other index), which the caller frees;
-    with it k and the integers of `ints`, (value, message) pairs converted after k and before the
-    query runs (a value of None stands for k)."""
+def _records_matrix(L, rcode, fill, handle, n, cols) -> np.ndarray:
+    """The (n, cols) int32 matrix of a segs / blocks handle a row-free entry returned with rcode."""
+    if rcode in (_lib.KMHG_EINVAL, _lib.KMHG_EOVERFLOW):
+        raise KmerHashError(L.kmhg_last_error().decode())
+    _lib.check(rcode)
+    out = np.empty(cols * n, np.int32)
+    if n:
+        _lib.check(fill(handle, out.ctypes.data))
+    return out.reshape(-1, cols)
+
+
+def _dot_plot_args(ex_ptr, seq, k, need, ints):
+    """What the dot-plot summaries check before any query runs: a position index (`need`: the
+    message for any other index), one sequence, k, then the integers of `ints`, (value, message)
+    pairs (a value of None stands for k).  Returns (index, sequence bytes, k, integers)."""
     p = _extract(ex_ptr)
-    L = _lib.lib()
     if p.info().kind != 0:
         raise KmerHashError(need)
     if isinstance(seq, (list, tuple)) and len(seq) != 1:
@@ -265,6 +286,16 @@ def _dot_plot_query(ex_ptr, seq, k, rc, need, ints):
         raise KmerHashError("k should be an integer of length 1")
     kk = _as_int(k, "k should be an integer of length 1")
     vals = [kk if v is None else _as_int(v, msg) for v, msg in ints]
+    return p, b, kk, vals
+
+
+def _dot_plot_query(ex_ptr, seq, k, rc, need, ints):
+    """The query handle of seq.kmer.pos (rc=False) or seq.kmer.pos.rc (rc=True) of one sequence
+    against a position index (`need`: the message for any other index), which the caller frees;
+    with it k and the integers of `ints`, (value, message) pairs converted after k and before the
+    query runs (a value of None stands for k)."""
+    p, b, kk, vals = _dot_plot_args(ex_ptr, seq, k, need, ints)
+    L = _lib.lib()
     q = C.c_void_p()
     h = C.c_int64()
     rcode = (L.kmhg_query_run_rc if rc else L.kmhg_query_run)(p.handle, b, len(b), kk,
@@ -275,7 +306,8 @@ def _dot_plot_query(ex_ptr, seq, k, rc, need, ints):
     return q, kk, vals
 
 
-def seq_kmer_blocks(ex_ptr, seq, k, max_gap=None, min_len=1, min_hits=1, rc=False) -> np.ndarray:
+def seq_kmer_blocks(ex_ptr, seq, k, max_gap=None, min_len=1, min_hits=1, rc=False,
+                    row_free=False) -> np.ndarray:
     """seq.kmer.blocks (not in the reference): the dot plot of seq against the index as diagonal
     segments merged across small gaps.
 
@@ -287,14 +319,25 @@ def seq_kmer_blocks(ex_ptr, seq, k, max_gap=None, min_len=1, min_hits=1, rc=Fals
     its gaps).  min_hits keeps the blocks with at least that many rows.  max_gap=None means k: one
     isolated substitution removes k consecutive windows from a diagonal, and a gap of k bridges
     it.  max_gap = 0 gives the segments themselves as (i, j, len, len).  Only a position index
-    (make_kmer_hash) is accepted."""
+    (make_kmer_hash) is accepted.
+
+    row_free=True takes the route that never writes the rows (kmhg_blocks_run), as in
+    seq_kmer_segs: the same matrix, byte for byte, also beyond 2^31 - 1 rows."""
     L = _lib.lib()
-    q, _, (ml, mg, mh) = _dot_plot_query(
-        ex_ptr, seq, k, rc, "blocks need a position index",
-        [(min_len, "min_len must be a positive integer"), (max_gap, "max_gap must not be negative"),
-         (min_hits, "min_hits must be a positive integer")])
+    need = "blocks need a position index"
+    ints = [(min_len, "min_len must be a positive integer"), (max_gap, "max_gap must not be negative"),
+            (min_hits, "min_hits must be a positive integer")]
     g = C.c_void_p()
     n = C.c_int64()
+    if row_free:
+        p, b, kk, (ml, mg, mh) = _dot_plot_args(ex_ptr, seq, k, need, ints)
+        try:
+            rcode = L.kmhg_blocks_run(p.handle, b, len(b), kk, 1 if rc else 0, ml, mg, mh,
+                                      C.byref(g), C.byref(n), None)
+            return _records_matrix(L, rcode, L.kmhg_blocks_fill, g, n.value, 4)
+        finally:
+            L.kmhg_blocks_free(g)
+    q, _, (ml, mg, mh) = _dot_plot_query(ex_ptr, seq, k, rc, need, ints)
     try:
         rcode = L.kmhg_query_blocks(q, ml, mg, mh, C.byref(g), C.byref(n))
         if rcode == _lib.KMHG_EINVAL:

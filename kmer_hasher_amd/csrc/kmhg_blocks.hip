@@ -10,8 +10,12 @@
 //              three arrays compacted in that order (a dropped segment's neighbours become
 //              neighbours, so the gap between them spans it)
 //   B_heads    segment m opens a block if m == 0 or blk_head(end[m - 1], start[m]); per tile the
-//              head count and the sum of len packed in one u64 {len << 32 | heads} (both < 2^31),
-//              so one launch_scan_u64 gives both exclusive prefixes
+//              head count and the sum of len packed in one u64 {len << 32 | heads}, so one
+//              launch_scan_u64 gives both exclusive prefixes.  heads < 2^31 never carries into
+//              the upper half; the len half is a sum modulo 2^32 (what leaves bit 63 is dropped):
+//              the lens sum to the hit total, which the row-free route takes beyond 2^32, and
+//              only differences of two prefixes are used -- a block's hits, below 2^31 because
+//              a block lies on one diagonal -- which are exact modulo 2^32
 //   B_mark     the same pair scanned inside the tile: block id = heads before m.  A head writes
 //              its block's start key, rank and the len prefix before it; a tail (the last segment,
 //              or the one before the next head) the end key and the len prefix after it
@@ -102,7 +106,7 @@ k_blocks_heads(const uint64_t* __restrict__ skey, const uint64_t* __restrict__ e
     const uint64_t m = t0 + (uint64_t)j * BLOCK + threadIdx.x;
     if (m < K) v += head_and_len(skey, ekey, m, gap_limit);
   }
-  v = wave_sum(v);                      // (a tile's lens sum to < 2^31: no carry out of a half)
+  v = wave_sum(v);                      // (heads never carry up; the len half is modulo 2^32)
   if (lane_id() == 0) wc[threadIdx.x >> 6] = v;
   __syncthreads();
   if (threadIdx.x == 0) {

@@ -34,6 +34,7 @@
 #include "kmhg_pool.h"
 #include "kmhg_reads.h"
 #include "kmhg_querycall.h"
+#include "kmhg_segrec.h"
 #include "kmhg_parts_read.h"
 #include "kmhg_fastx.h"
 #include "kmhg_khash.h"
@@ -3399,7 +3400,76 @@ struct SegPairs {
   const uint64_t* skey() const { return keys.p + 2 * S; }
   const uint64_t* ekey() const { return keys.p + 3 * S; }
   const uint32_t* rank() const { return ranks.p + S; }
+  // where an emit kernel writes the keys (ranks: ranks.p) before sort_seg_pairs
+  uint64_t* skey_in() { return keys.p; }
+  uint64_t* ekey_in() { return keys.p + S; }
+  void alloc(uint64_t n_segs, hipStream_t s) {
+    S = n_segs;
+    keys.reset(4 * S);
+    keys.bind(s);
+    ranks.reset(2 * S);
+    ranks.bind(s);
+  }
 };
+
+// Both key arrays ascending, the starts' ranks carried (kmhg_segs.hip).
+void sort_seg_pairs(SegPairs& sp, hipStream_t s) {
+  const uint64_t S = sp.S;
+  size_t tb = 0;
+  HIPC(segs_sort_temp_bytes(S, &tb));
+  DBuf<uint8_t> temp(std::max<size_t>(tb, 16), s);
+  hipError_t sort_err = hipSuccess;
+  LAUNCH("k_segs_sort", s,
+         sort_err = launch_segs_sort(sp.skey_in(), sp.ranks.p, sp.ekey_in(), S, sp.keys.p + 2 * S,
+                                     sp.ranks.p + S, sp.keys.p + 3 * S, temp.p, tb, s));
+  HIPC(sort_err);
+}
+
+// What the row-free routes (segs_pairs_from_records, raster_device) refuse of an index before
+// they probe it, query_device's checks; then its pending build is finished.  positions_only: the
+// refusal of an index with sources (a counts index), or null where the route takes one.
+void records_index(kmhg_index* idx, const QueryCall& c, hipStream_t s, const char* positions_only) {
+  if (idx->canonical) fail(KMHG_EINVAL, "External pointer has incorrect tag");
+  if (idx->is_part != c.part)
+    fail(KMHG_EINVAL, idx->is_part ? "a part index must be assembled before it is queried"
+                                   : "not a part of an owner-computes build");
+  if (positions_only && idx->sources) fail(KMHG_EINVAL, positions_only);
+  finish_build(idx);
+  idx->stream = s;
+}
+
+// The per-window records of a probed query (put_qrec) and the probe's per-tile hit totals.
+struct QueryRecords {
+  DBuf<uint32_t> qrec;
+  DBuf<uint2> qmulti;
+  DBuf<uint64_t> tiles;
+};
+
+// query_device's probe of the c.w1 - c.w0 > 0 windows, without the emit list, and the scan of
+// the tile totals: *total (pinned) <- the hit total once `s` has been waited for.
+void probe_records(kmhg_index* idx, const uint8_t* d_seq, const QueryCall& c, uint64_t* total,
+                   hipStream_t s, QueryRecords& r) {
+  const int64_t Nw = c.w1 - c.w0;
+  const int kq = c.k;
+  const bool aligned = (reinterpret_cast<uintptr_t>(d_seq) & 15) == 0;
+  const uint32_t nt = tiles_for(Nw);
+  const char* de = test_build_knob("KMHG_QUERY_DIAG");
+  const bool diag = diag_eligible(kq, idx->k, idx->sources, idx->L - idx->k + 1, idx->U,
+                                  idx->dcodes.p != nullptr, !(de && de[0] == '0')) &&
+                    ensure_diag(idx, s);
+  r.qrec.reset(Nw);
+  r.qrec.bind(s);
+  r.qmulti.reset(Nw);
+  r.qmulti.bind(s);
+  r.tiles.reset((size_t)nt + scan_u64_scratch(nt));
+  r.tiles.bind(s);
+  LAUNCH("k_query_probe", s,
+         launch_query_probe(d_seq, c.L, kq, idx->table.p, idx->geom, r.qrec.p, r.qmulti.p, c.w0, c.w1,
+                            aligned, r.tiles.p, s,
+                            diag ? idx->diag_view() : DiagIdx{nullptr, nullptr, 0},
+                            diag && tags_on() ? idx->ptag.p : nullptr, nullptr, c.rc));
+  LAUNCH("k_scan_tiles_u64", s, launch_scan_u64(r.tiles.p, nt, total, r.tiles.p + nt, s));
+}
 
 // Classifies and counts the starts and ends of n ascending rows, waits for `s` once (the number
 // of segments sizes the sort) and answers the two row faults; then, with `pair`, emits the
@@ -3426,39 +3496,52 @@ void segs_sorted_pairs(const int2* rows, uint64_t n, bool pair, BuildMeta* hm, h
   // on every diagonal starts and ends alternate, so there are as many of each
   if (!S || (both >> 32) != S) fail(KMHG_EDEVICE, "segment starts and ends do not pair");
   if (!pair) return;
-  sp.S = S;
-  sp.keys.reset(4 * S);
-  sp.keys.bind(s);
-  sp.ranks.reset(2 * S);
-  sp.ranks.bind(s);
-  uint64_t *skey = sp.keys.p, *ekey = sp.keys.p + S, *skey_o = sp.keys.p + 2 * S,
-           *ekey_o = sp.keys.p + 3 * S;
+  sp.alloc(S, s);
   LAUNCH("k_segs_emit", s,
-         launch_segs_emit(rows, n, smask, emask, tiles.p, skey, sp.ranks.p, ekey, s));
-  size_t tb = 0;
-  HIPC(segs_sort_temp_bytes(S, &tb));
-  DBuf<uint8_t> temp(std::max<size_t>(tb, 16), s);
-  hipError_t sort_err = hipSuccess;
-  LAUNCH("k_segs_sort", s, sort_err = launch_segs_sort(skey, sp.ranks.p, ekey, S, skey_o,
-                                                       sp.ranks.p + S, ekey_o, temp.p, tb, s));
-  HIPC(sort_err);
+         launch_segs_emit(rows, n, smask, emask, tiles.p, sp.skey_in(), sp.ranks.p, sp.ekey_in(), s));
+  sort_seg_pairs(sp, s);
 }
 
-// The maximal diagonal segments of n_rows ascending rows on the current device (kmhg_segs.hip;
-// include/kmhgpu.h has the definition).  Waits for `s` twice (the number of segments sizes the
-// sort; min_len > 1: the number kept sizes the result) and once more at the end.
-kmhg_segs* rows_segments(const int2* rows, int64_t n_rows, int64_t min_len, hipStream_t s) {
-  auto g = std::make_unique<kmhg_segs>();
-  if (!n_rows) return g.release();      // (no device call: an empty result is host-only)
-  HIPC(hipGetDevice(&g->device));
-  g->stream = s;
-  ReleaseGroup rg(s);
-  PinnedRec hrec = PinnedPool::get().take();
-  GiveBack give_back{hrec, s};
-  BuildMeta* hm = hrec.meta;
-  SegPairs sp;
-  segs_sorted_pairs(rows, (uint64_t)n_rows, min_len <= INT32_MAX, hm, s, sp);
-  if (min_len > INT32_MAX) return g.release();            // no segment has that many rows
+// The same front half without rows (kmhg_segrec.hip): probes the query as raster_device does,
+// counts the starts and ends of every tile from the window records, waits for `s` once (the hit
+// total, and the number of segments, which sizes the sort), then emits the pairing keys from the
+// records again and sorts them.  Returns the hit total H, which may exceed 2^31 - 1; H = 0 leaves
+// sp empty.  Scratch is O(Nw + Nw / TILE + S): nothing grows with H.  hm: the caller's pinned
+// record (n_kmers: H; n_positions / n_pairs: the starts and the ends).
+uint64_t segs_pairs_from_records(kmhg_index* idx, const uint8_t* d_seq, const QueryCall& c,
+                                 BuildMeta* hm, hipStream_t s, SegPairs& sp) {
+  const int64_t Nw = c.w1 - c.w0;
+  if (Nw <= 0) return 0;
+  const uint32_t nt = tiles_for(Nw);
+  QueryRecords r;
+  probe_records(idx, d_seq, c, &hm->n_kmers, s, r);
+  const size_t per = (size_t)nt + scan_u64_scratch(nt);
+  DBuf<uint64_t> cnt(2 * per, s);                   // per tile: starts, ends (each with its scan's)
+  DBuf<uint32_t> wstarts(Nw, s);                    // per window: starts
+  uint64_t *ts = cnt.p, *te = cnt.p + per;
+  LAUNCH("k_segrec_count", s,
+         launch_segrec_count(r.qrec.p, r.qmulti.p, Nw, idx->positions.p, ts, te, wstarts.p, s));
+  LAUNCH("k_scan_tiles_u64", s, launch_scan_u64(ts, nt, &hm->n_positions, ts + nt, s));
+  LAUNCH("k_scan_tiles_u64", s, launch_scan_u64(te, nt, &hm->n_pairs, te + nt, s));
+  HIPC(hipStreamSynchronize(s));
+  const uint64_t H = __atomic_load_n(&hm->n_kmers, __ATOMIC_ACQUIRE);
+  if (!H) return 0;
+  const uint64_t S = __atomic_load_n(&hm->n_positions, __ATOMIC_ACQUIRE);
+  const SegrecRefusal rf = segrec_check_totals(S, __atomic_load_n(&hm->n_pairs, __ATOMIC_ACQUIRE));
+  if (rf.code != KMHG_OK) fail(rf.code, rf.text);
+  sp.alloc(S, s);
+  LAUNCH("k_segrec_emit", s,
+         launch_segrec_emit(r.qrec.p, r.qmulti.p, Nw, c.w0, c.k, idx->positions.p, wstarts.p, ts, te,
+                            S, sp.skey_in(), sp.ranks.p, sp.ekey_in(), s));
+  sort_seg_pairs(sp, s);
+  return H;
+}
+
+// The back half of the segment pass: {i, j, len} of the sorted pairs at their starts' ranks, the
+// segments with len >= min_len (<= INT32_MAX) kept, into g.  Waits for `s` (min_len > 1: the
+// number kept sizes the result) and once more at the end.  hm: the caller's pinned record.
+void pairs_segments(const SegPairs& sp, int64_t min_len, BuildMeta* hm, hipStream_t s,
+                    kmhg_segs* g) {
   const uint64_t S = sp.S;
   if (min_len == 1) {
     g->segs.reset(3 * S);
@@ -3481,30 +3564,34 @@ kmhg_segs* rows_segments(const int2* rows, int64_t n_rows, int64_t min_len, hipS
     g->S = (int64_t)K;
   }
   HIPC(hipStreamSynchronize(s));
-  rg.synced = true;
-  return g.release();
 }
 
-// The blocks of n_rows ascending rows on the current device (kmhg_blocks.hip; include/kmhgpu.h
-// has the definition): the segment pass's sorted keys, filtered by min_len, then heads / mark /
-// place / order.  Waits for `s` where a count sizes an allocation -- the number of segments (the
-// sort), min_len > 1: the number kept, and the number of blocks (the result) -- and once more at
-// the end.  The number of blocks before min_hits stays on the device.
-kmhg_blocks* rows_blocks(const int2* rows, int64_t n_rows, int64_t min_len, int64_t max_gap,
-                         int64_t min_hits, hipStream_t s) {
-  auto g = std::make_unique<kmhg_blocks>();
+// The maximal diagonal segments of n_rows ascending rows on the current device (kmhg_segs.hip;
+// include/kmhgpu.h has the definition).  Waits for `s` twice (the number of segments sizes the
+// sort; min_len > 1: the number kept sizes the result) and once more at the end.
+kmhg_segs* rows_segments(const int2* rows, int64_t n_rows, int64_t min_len, hipStream_t s) {
+  auto g = std::make_unique<kmhg_segs>();
   if (!n_rows) return g.release();      // (no device call: an empty result is host-only)
   HIPC(hipGetDevice(&g->device));
   g->stream = s;
   ReleaseGroup rg(s);
   PinnedRec hrec = PinnedPool::get().take();
   GiveBack give_back{hrec, s};
-  BuildMeta* hm = hrec.meta;            // n_positions: segments kept; n_pairs: blocks
-  // no segment has 2^31 rows and no block 2^31 hits
-  const bool any = min_len <= INT32_MAX && min_hits <= INT32_MAX;
+  BuildMeta* hm = hrec.meta;
   SegPairs sp;
-  segs_sorted_pairs(rows, (uint64_t)n_rows, any, hm, s, sp);
-  if (!any) return g.release();
+  segs_sorted_pairs(rows, (uint64_t)n_rows, min_len <= INT32_MAX, hm, s, sp);
+  if (min_len > INT32_MAX) return g.release();            // no segment has that many rows
+  pairs_segments(sp, min_len, hm, s, g.get());
+  rg.synced = true;
+  return g.release();
+}
+
+// The back half of the block pass: the sorted pairs filtered by min_len, then heads / mark /
+// place / order, into g (min_len, min_hits <= INT32_MAX).  Waits for `s` where a count sizes an
+// allocation -- min_len > 1: the number of segments kept, and the number of blocks (the result)
+// -- and once more at the end: `s` is idle when it returns.  hm: the caller's pinned record.
+void pairs_blocks(const SegPairs& sp, int64_t min_len, int64_t max_gap, int64_t min_hits,
+                  BuildMeta* hm, hipStream_t s, kmhg_blocks* g) {
   const uint64_t S = sp.S;
   const uint32_t gap_limit = blk_gap_limit(max_gap);
   const uint64_t *skey = sp.skey(), *ekey = sp.ekey();
@@ -3521,7 +3608,7 @@ kmhg_blocks* rows_blocks(const int2* rows, int64_t n_rows, int64_t min_len, int6
            launch_scan_u64(ftiles.p, nts, &hm->n_positions, ftiles.p + nts, s));
     HIPC(hipStreamSynchronize(s));
     K = __atomic_load_n(&hm->n_positions, __ATOMIC_ACQUIRE);
-    if (!K) { rg.synced = true; return g.release(); }
+    if (!K) return;
     fkeys.reset(2 * K);
     fkeys.bind(s);
     franks.reset(K);
@@ -3561,6 +3648,29 @@ kmhg_blocks* rows_blocks(const int2* rows, int64_t n_rows, int64_t min_len, int6
     g->B = (int64_t)B;
     HIPC(hipStreamSynchronize(s));
   }
+}
+
+// The blocks of n_rows ascending rows on the current device (kmhg_blocks.hip; include/kmhgpu.h
+// has the definition): the segment pass's sorted keys, filtered by min_len, then heads / mark /
+// place / order.  Waits for `s` where a count sizes an allocation -- the number of segments (the
+// sort), min_len > 1: the number kept, and the number of blocks (the result) -- and once more at
+// the end.  The number of blocks before min_hits stays on the device.
+kmhg_blocks* rows_blocks(const int2* rows, int64_t n_rows, int64_t min_len, int64_t max_gap,
+                         int64_t min_hits, hipStream_t s) {
+  auto g = std::make_unique<kmhg_blocks>();
+  if (!n_rows) return g.release();      // (no device call: an empty result is host-only)
+  HIPC(hipGetDevice(&g->device));
+  g->stream = s;
+  ReleaseGroup rg(s);
+  PinnedRec hrec = PinnedPool::get().take();
+  GiveBack give_back{hrec, s};
+  BuildMeta* hm = hrec.meta;            // n_positions: segments kept; n_pairs: blocks
+  // no segment has 2^31 rows and no block 2^31 hits
+  const bool any = min_len <= INT32_MAX && min_hits <= INT32_MAX;
+  SegPairs sp;
+  segs_sorted_pairs(rows, (uint64_t)n_rows, any, hm, s, sp);
+  if (!any) return g.release();
+  pairs_blocks(sp, min_len, max_gap, min_hits, hm, s, g.get());
   rg.synced = true;
   return g.release();
 }
@@ -3568,6 +3678,26 @@ kmhg_blocks* rows_blocks(const int2* rows, int64_t n_rows, int64_t min_len, int6
 void check_segs_args(int64_t min_len, kmhg_segs** out) {
   if (!out) fail(KMHG_EINVAL, "null argument");
   if (min_len < 1) fail(KMHG_EINVAL, "min_len must be a positive integer");
+}
+
+// seq.kmer.segs without rows: the records front half, then the same back half.  *H <- the hit
+// total; H = 0 gives an empty handle.
+kmhg_segs* records_segments(kmhg_index* idx, const uint8_t* d_seq, const QueryCall& c,
+                            int64_t min_len, hipStream_t s, uint64_t* H) {
+  auto g = std::make_unique<kmhg_segs>();
+  ReleaseGroup rg(s);
+  records_index(idx, c, s, "segments need a position index");
+  PinnedRec hrec = PinnedPool::get().take();
+  GiveBack give_back{hrec, s};
+  BuildMeta* hm = hrec.meta;
+  SegPairs sp;
+  *H = segs_pairs_from_records(idx, d_seq, c, hm, s, sp);
+  if (!*H || min_len > INT32_MAX) return g.release();     // no segment has that many rows
+  HIPC(hipGetDevice(&g->device));
+  g->stream = s;
+  pairs_segments(sp, min_len, hm, s, g.get());
+  rg.synced = true;
+  return g.release();
 }
 
 }  // namespace
@@ -3593,6 +3723,42 @@ int kmhg_query_segments(kmhg_query* q, int64_t min_len, kmhg_segs** out, int64_t
     DeviceGuard g(q->device);
     *out = rows_segments(q->rows.p, q->H, min_len, q->stream);
     if (n_segs) *n_segs = (*out)->S;
+  });
+}
+
+int kmhg_segments_run_device(kmhg_index* idx, const void* d_seq, size_t L, int k, int rc,
+                             int64_t min_len, void* stream, kmhg_segs** out, int64_t* n_segs,
+                             int64_t* n_rows) {
+  return guarded([&] {
+    if (!idx || !d_seq) fail(KMHG_EINVAL, "null argument");
+    check_segs_args(min_len, out);
+    const QueryCall c = checked(query_call(L, k)).on_rc(rc != 0);
+    DeviceGuard g(idx->device);
+    uint64_t H = 0;
+    *out = records_segments(idx, static_cast<const uint8_t*>(d_seq), c, min_len,
+                            (hipStream_t)stream, &H);
+    if (n_segs) *n_segs = (*out)->S;
+    if (n_rows) *n_rows = (int64_t)H;
+  });
+}
+
+int kmhg_segments_run(kmhg_index* idx, const char* seq, size_t L, int k, int rc, int64_t min_len,
+                      kmhg_segs** out, int64_t* n_segs, int64_t* n_rows) {
+  return guarded([&] {
+    if (!idx || !seq) fail(KMHG_EINVAL, "null argument");
+    check_segs_args(min_len, out);
+    if (L < H2D_SCAN_MIN || k < 1 || k > 31 || L >= (size_t)INT32_MAX) {
+      L = effective_len(seq, L);             // (as kmhg_query_run)
+      check_query_args(L, k);
+    }
+    DeviceGuard g(idx->device);
+    hipStream_t s = lib_stream();
+    DBuf<uint8_t> d(L + 16, s);
+    L = h2d_cstring(d.p, seq, L, s);
+    uint64_t H = 0;
+    *out = records_segments(idx, d.p, checked(query_call(L, k)).on_rc(rc != 0), min_len, s, &H);
+    if (n_segs) *n_segs = (*out)->S;
+    if (n_rows) *n_rows = (int64_t)H;
   });
 }
 
@@ -3646,7 +3812,67 @@ void check_blocks_args(int64_t min_len, int64_t max_gap, int64_t min_hits, kmhg_
   if (min_hits < 1) fail(KMHG_EINVAL, "min_hits must be a positive integer");
 }
 
+// seq.kmer.blocks without rows: the records front half, then the same back half.  *H <- the hit
+// total; H = 0 gives an empty handle.
+kmhg_blocks* records_blocks(kmhg_index* idx, const uint8_t* d_seq, const QueryCall& c,
+                            int64_t min_len, int64_t max_gap, int64_t min_hits, hipStream_t s,
+                            uint64_t* H) {
+  auto g = std::make_unique<kmhg_blocks>();
+  ReleaseGroup rg(s);
+  records_index(idx, c, s, "blocks need a position index");
+  PinnedRec hrec = PinnedPool::get().take();
+  GiveBack give_back{hrec, s};
+  BuildMeta* hm = hrec.meta;            // n_positions: segments kept; n_pairs: blocks
+  SegPairs sp;
+  *H = segs_pairs_from_records(idx, d_seq, c, hm, s, sp);
+  // no segment has 2^31 rows and no block 2^31 hits
+  if (!*H || min_len > INT32_MAX || min_hits > INT32_MAX) return g.release();
+  HIPC(hipGetDevice(&g->device));
+  g->stream = s;
+  pairs_blocks(sp, min_len, max_gap, min_hits, hm, s, g.get());
+  rg.synced = true;
+  return g.release();
+}
+
 }  // namespace
+
+int kmhg_blocks_run_device(kmhg_index* idx, const void* d_seq, size_t L, int k, int rc,
+                           int64_t min_len, int64_t max_gap, int64_t min_hits, void* stream,
+                           kmhg_blocks** out, int64_t* n_blocks, int64_t* n_rows) {
+  return guarded([&] {
+    if (!idx || !d_seq) fail(KMHG_EINVAL, "null argument");
+    check_blocks_args(min_len, max_gap, min_hits, out);
+    const QueryCall c = checked(query_call(L, k)).on_rc(rc != 0);
+    DeviceGuard g(idx->device);
+    uint64_t H = 0;
+    *out = records_blocks(idx, static_cast<const uint8_t*>(d_seq), c, min_len, max_gap, min_hits,
+                          (hipStream_t)stream, &H);
+    if (n_blocks) *n_blocks = (*out)->B;
+    if (n_rows) *n_rows = (int64_t)H;
+  });
+}
+
+int kmhg_blocks_run(kmhg_index* idx, const char* seq, size_t L, int k, int rc, int64_t min_len,
+                    int64_t max_gap, int64_t min_hits, kmhg_blocks** out, int64_t* n_blocks,
+                    int64_t* n_rows) {
+  return guarded([&] {
+    if (!idx || !seq) fail(KMHG_EINVAL, "null argument");
+    check_blocks_args(min_len, max_gap, min_hits, out);
+    if (L < H2D_SCAN_MIN || k < 1 || k > 31 || L >= (size_t)INT32_MAX) {
+      L = effective_len(seq, L);             // (as kmhg_query_run)
+      check_query_args(L, k);
+    }
+    DeviceGuard g(idx->device);
+    hipStream_t s = lib_stream();
+    DBuf<uint8_t> d(L + 16, s);
+    L = h2d_cstring(d.p, seq, L, s);
+    uint64_t H = 0;
+    *out = records_blocks(idx, d.p, checked(query_call(L, k)).on_rc(rc != 0), min_len, max_gap,
+                          min_hits, s, &H);
+    if (n_blocks) *n_blocks = (*out)->B;
+    if (n_rows) *n_rows = (int64_t)H;
+  });
+}
 
 int kmhg_rows_blocks(const void* d_rows, int64_t n_rows, int64_t min_len, int64_t max_gap,
                      int64_t min_hits, void* stream, kmhg_blocks** out, int64_t* n_blocks) {
@@ -3741,36 +3967,18 @@ static void raster_rows(const int2* rows, int64_t n_rows, const RasterFrame& f, 
 static uint64_t raster_device(kmhg_index* idx, const uint8_t* d_seq, const QueryCall& c,
                               const RasterFrame& f, uint32_t* d_out, hipStream_t s) {
   ReleaseGroup rg(s);
-  if (idx->canonical) fail(KMHG_EINVAL, "External pointer has incorrect tag");
-  if (idx->is_part != c.part)
-    fail(KMHG_EINVAL, idx->is_part ? "a part index must be assembled before it is queried"
-                                   : "not a part of an owner-computes build");
-  finish_build(idx);
-  idx->stream = s;
+  records_index(idx, c, s, nullptr);
   HIPC(hipMemsetAsync(d_out, 0, raster_cells(f) * 4, s));
-  const int64_t L = c.L, w0 = c.w0, w1 = c.w1, Nw = w1 - w0;
-  const int kq = c.k;
+  const int64_t Nw = c.w1 - c.w0;
   if (Nw <= 0) {
     HIPC(hipStreamSynchronize(s));
     return 0;
   }
-  const bool aligned = (reinterpret_cast<uintptr_t>(d_seq) & 15) == 0;
-  const uint32_t nt = tiles_for(Nw);
-  const char* de = test_build_knob("KMHG_QUERY_DIAG");
-  const bool diag = diag_eligible(kq, idx->k, idx->sources, idx->L - idx->k + 1, idx->U,
-                                  idx->dcodes.p != nullptr, !(de && de[0] == '0')) &&
-                    ensure_diag(idx, s);
-  DBuf<uint32_t> qrec(Nw, s);
-  DBuf<uint2> qmulti(Nw, s);
-  DBuf<uint64_t> tiles((size_t)nt + scan_u64_scratch(nt), s);
+  QueryRecords r;
   PinnedRec hrec = PinnedPool::get().take();
   GiveBack give_back{hrec, s};
   uint64_t* total = &hrec.meta->n_kmers;
-  LAUNCH("k_query_probe", s,
-         launch_query_probe(d_seq, L, kq, idx->table.p, idx->geom, qrec.p, qmulti.p, w0, w1, aligned,
-                            tiles.p, s, diag ? idx->diag_view() : DiagIdx{nullptr, nullptr, 0},
-                            diag && tags_on() ? idx->ptag.p : nullptr, nullptr, c.rc));
-  LAUNCH("k_scan_tiles_u64", s, launch_scan_u64(tiles.p, nt, total, tiles.p + nt, s));
+  probe_records(idx, d_seq, c, total, s, r);
   if ((uint64_t)f.bin_i * (uint64_t)f.bin_j >= (1ull << 32)) {
     // only such a frame can overflow a cell: the total is read before any add
     HIPC(hipStreamSynchronize(s));
@@ -3778,8 +3986,8 @@ static uint64_t raster_device(kmhg_index* idx, const uint8_t* d_seq, const Query
       fail(KMHG_EOVERFLOW, "a raster cell could exceed 2^32-1 rows");
   }
   LAUNCH("k_raster_records", s,
-         launch_raster_records(qrec.p, qmulti.p, Nw, w0, kq, idx->positions.p, raster_dev(f), d_out,
-                               s));
+         launch_raster_records(r.qrec.p, r.qmulti.p, Nw, c.w0, c.k, idx->positions.p, raster_dev(f),
+                               d_out, s));
   HIPC(hipStreamSynchronize(s));
   rg.synced = true;
   return __atomic_load_n(total, __ATOMIC_ACQUIRE);

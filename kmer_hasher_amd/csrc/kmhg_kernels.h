@@ -186,6 +186,19 @@ void launch_raster_rows(const int2* rows, uint64_t n, const RasterDev& f, uint32
 void launch_raster_records(const uint32_t* qrec, const uint2* qmulti, int64_t Nw, int64_t w0,
                            int kq, const int32_t* positions, const RasterDev& f, uint32_t* out,
                            hipStream_t s);
+// the segment pass's pairing keys straight from a probed query's records (kmhg_segrec.hip, the
+// arithmetic in kmhg_segrec.h; qrec / qmulti of Nw windows from w0, launch_query_probe), no row
+// written.  count: per tile of TILE windows the starts and the ends as full u64 (tile_starts,
+// tile_ends), per window its starts (win_starts: Nw u32).  emit (tile_soff / tile_eoff = the two
+// arrays scanned, S = either total, <= 2^31 - 1): the starts' keys with their ranks in (window,
+// hit) order -- launch_segs_emit's ranks -- and the ends' keys in any order.
+void launch_segrec_count(const uint32_t* qrec, const uint2* qmulti, int64_t Nw,
+                         const int32_t* positions, uint64_t* tile_starts, uint64_t* tile_ends,
+                         uint32_t* win_starts, hipStream_t s);
+void launch_segrec_emit(const uint32_t* qrec, const uint2* qmulti, int64_t Nw, int64_t w0, int kq,
+                        const int32_t* positions, const uint32_t* win_starts,
+                        const uint64_t* tile_soff, const uint64_t* tile_eoff, uint64_t S,
+                        uint64_t* skey, uint32_t* srank, uint64_t* ekey, hipStream_t s);
 // exclusive u64 scan in place, *total <- sum: one workgroup up to SCAN1_MAX entries, else
 // reduce-then-scan with `scratch` = scan_u64_scratch(n) u64
 // (round 4: one workgroup up to 64 K / 256 K totals instead -- config 3 query 185 -> 162 Gbp/s,

@@ -197,6 +197,38 @@ class DeviceIndex:
                 C.c_void_p(out.data_ptr()), _stream_ptr(stream), C.byref(h)))
         return _raster_matrix(out, f), h.value
 
+    def segments(self, seq: torch.Tensor, k: int, min_len: int = 1, rc: bool = False,
+                 stream=None) -> tuple[torch.Tensor, int]:
+        """kmhg_segments_run_device (seq.kmer.segs, the row-free route): the maximal diagonal
+        segments of query(seq, k) -- of query_rc(seq, k) with rc -- found from the per-window
+        records without the rows ever being written: ((S, 3) int32 {i, j, len}, n_rows), n_rows
+        the hit total, which may exceed 2^31 - 1 where DeviceQuery.segments refuses.  Equal to
+        query(seq, k).segments(min_len), byte for byte, wherever that exists.  Synchronous."""
+        _check_seq(seq)
+        g = C.c_void_p()
+        n, h = C.c_int64(), C.c_int64()
+        with torch.cuda.device(seq.device):
+            _lib.check(_lib.lib().kmhg_segments_run_device(
+                self._h, C.c_void_p(seq.data_ptr()), seq.numel(), k, 1 if rc else 0, int(min_len),
+                _stream_ptr(stream), C.byref(g), C.byref(n), C.byref(h)))
+        return _segs_tensor(g, n.value, seq.device), h.value
+
+    def blocks(self, seq: torch.Tensor, k: int, max_gap: int, min_len: int = 1, min_hits: int = 1,
+               rc: bool = False, stream=None) -> tuple[torch.Tensor, int]:
+        """kmhg_blocks_run_device (seq.kmer.blocks, the row-free route): segments()'s front half
+        followed by the block passes: ((B, 4) int32 {i, j, span, hits}, n_rows).  Equal to
+        query(seq, k).blocks(max_gap, min_len, min_hits), byte for byte, wherever that exists.
+        Synchronous."""
+        _check_seq(seq)
+        g = C.c_void_p()
+        n, h = C.c_int64(), C.c_int64()
+        with torch.cuda.device(seq.device):
+            _lib.check(_lib.lib().kmhg_blocks_run_device(
+                self._h, C.c_void_p(seq.data_ptr()), seq.numel(), k, 1 if rc else 0, int(min_len),
+                int(max_gap), int(min_hits), _stream_ptr(stream), C.byref(g), C.byref(n),
+                C.byref(h)))
+        return _blocks_tensor(g, n.value, seq.device), h.value
+
     def positions(self, opt: int, stream=None) -> dict:
         """kmer.pos into device tensors: {'kmer': uint8 (U, k+1), 'pos': int32 (N, 2),
         'pair.pos': int32 (P, 3), 'count': int32 (U,)} for the requested bits."""
