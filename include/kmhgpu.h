@@ -444,7 +444,18 @@ int kmhg_raster_run(kmhg_index *idx, const char *seq, size_t L, int k, int rc,
  * the result is a query handle holding 2 x n_rows int32, read like a seq.kmer.pos result.
  * Defined where the reference is broken: only a's live k-mers are visited (the reference reads
  * empty buckets and calls kh_exist(b, kh_end(b)), src/kmer_hash.c:1182-1185; test.R:330 "This
- * crashes"), and both indices must have the same k ("the two indices must have the same k"). */
+ * crashes"), and both indices must have the same k ("the two indices must have the same k").
+ * Either index may be a counts index: its count vectors are read where a position index has
+ * positions (zeros included), as kmer.pos reads them.
+ * Refusals, KMHG_EINVAL, in this order: "null argument"; "External pointer has incorrect tag"
+ * (a suffix hash as a or b); "a part index must be assembled before it is read" (a part of an
+ * owner-computes build as a or b, refused before its build is waited for); "the two indices
+ * must have the same k"; "the two indices must be on the same device".  More than 2^31-1 rows
+ * are not refused here: n_rows is exact and the handle holds every row on the device; the host
+ * matrix (kmer.pairs) is what refuses them.
+ * kmhg_pairs_run is synchronous on the library's stream.  kmhg_pairs_run_device runs on `stream`
+ * and does not synchronise it: n_rows is final when it returns, the rows are complete in stream
+ * order (the caller synchronises `stream` before reading them from another stream or the host). */
 int kmhg_pairs_run(kmhg_index *a, kmhg_index *b, kmhg_query **q, int64_t *n_rows);
 int kmhg_pairs_run_device(kmhg_index *a, kmhg_index *b, void *stream, kmhg_query **q,
                           int64_t *n_rows);

@@ -1368,6 +1368,10 @@ void prepare_readout(kmhg_index* idx, hipStream_t s);
 kmhg_query* pairs_device(kmhg_index* a, kmhg_index* b, hipStream_t s) {
   ReleaseGroup rg(s);
   if (a->canonical || b->canonical) fail(KMHG_EINVAL, "External pointer has incorrect tag");
+  // (the probe hashes over b's own bucket count and the readout walks a's own slots: a part
+  // would answer for the wrong buckets without a word)
+  if (a->is_part || b->is_part)
+    fail(KMHG_EINVAL, "a part index must be assembled before it is read");
   finish_build(a);
   finish_build(b);
   if (a->k != b->k) fail(KMHG_EINVAL, "the two indices must have the same k");
