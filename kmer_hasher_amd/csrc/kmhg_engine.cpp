@@ -102,8 +102,9 @@ int guarded(F&& f) {
 }
 
 // ============================================================================ device pool
-// BlockPool (kmhg_pool.h) over HIP.  Events carry no timing; an out-of-memory answer is cleared
-// from the runtime's last-error slot, since the pool trims its cache and asks again.
+// BlockPool (kmhg_pool.h) over HIP.  Events carry no timing and no system-scope fence; an
+// out-of-memory answer is cleared from the runtime's last-error slot, since the pool trims its
+// cache and asks again.
 struct HipDev {
   static PoolKnobs knobs() {          // test build: KMHG_POOL_DEPTH / _BESTFIT / _TRACE
     PoolKnobs kn;
@@ -123,8 +124,16 @@ struct HipDev {
     return PoolAlloc::error;
   }
   void free(void* p) { (void)hipFree(p); }
+  // No system-scope fence at the record (like the timing events below): a release event only
+  // gates the reuse of device blocks, by later device work and by the pool's hipEventQuery /
+  // hipEventSynchronize on the host.  Nothing is read through it, so no cache has to be written
+  // back or invalidated for it.  A runtime that refuses the flag gets the plain event.
   void* event() {
     hipEvent_t ev = nullptr;
+    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming | hipEventDisableSystemFence) ==
+        hipSuccess)
+      return ev;
+    (void)hipGetLastError();
     return hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess ? ev : nullptr;
   }
   bool record(void* ev, void* s) {
@@ -207,6 +216,9 @@ class PinnedPool {
       for (int i = 0; i < kSlots; ++i) {
         PinnedRec r;
         r.meta = blk + i;
+        // with its system-scope fence, unlike the pool's release events: the host reads the
+        // record behind this event.  (Without it the 10 Mbp build measured 0.1744 against 0.1771
+        // ms, the two sets of runs overlapping: not kept)
         HIPC(hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
         free_.push_back(r);
       }
@@ -1035,6 +1047,8 @@ kmhg_index* build_device_v2(const BuildRequest& rq, const StreamPtrs& in, hipStr
       LAUNCH("k_v2_hll", s, launch_v2_hll(hll_rows.p, ntiles, hll_regs.p,
                                           &hrec.meta->distinct_est, n_valid,
                                           &hrec.meta->n_positions, s));
+      // a pinned record's event keeps its system-scope fence: the host reads the estimate
+      // through it below, mid-build
       HIPC(hipEventRecord(hrec.ev, s));
     }
     const BoundsFuse lv = level_of(p, 1u);              // (pass 0 has none: never fused)
@@ -1108,7 +1122,11 @@ kmhg_index* build_device_v2(const BuildRequest& rq, const StreamPtrs& in, hipStr
   idx->tags_built = tg != nullptr;
   LAUNCH("k_v2_stats", s, launch_v2_stats(idx->bstats.p, gb.nb, n_valid, meta, idx->rec.meta, s));
   idx->bstats_nb = gb.nb;
+  // the build's one marker: finish_build() waits on it for the totals, and the scratch buffers
+  // above wait behind it too (nothing below launches on s).  Every earlier exit, a throw
+  // included, leaves the group to record an event of its own.
   HIPC(hipEventRecord(idx->rec.ev, s));
+  rg.adopt(idx->rec.ev);
 #ifdef KMHG_STAMPS
   if (const char* f = std::getenv("KMHG_STAMP_FILE")) {
     HIPC(hipStreamSynchronize(s));
@@ -2370,13 +2388,15 @@ void free_index(kmhg_index* idx) {
   for (auto& kv : idx->replicas) free_index(kv.second);
   idx->replicas.clear();
   DeviceGuard g(idx->device);
-  if (idx->pending) {                  // never used: no need to wait, the record is recycled
-    PinnedPool::get().give(idx->rec, true);   // once the build's event has completed
-    idx->pending = false;
-  }
   // stream-ordered release: the buffers return to the pool once work queued on the index's
   // last stream has finished (queries on other streams are synchronised by their callers)
   ReleaseGroup rg(idx->stream);
+  if (idx->pending) {                  // never used: no need to wait, the record is recycled
+    // only the build has touched the buffers, and its event is already behind it: no second one
+    rg.adopt(idx->rec.ev);
+    PinnedPool::get().give(idx->rec, true);   // once the build's event has completed
+    idx->pending = false;
+  }
   idx->bind_all(idx->stream);
   delete idx;
 }

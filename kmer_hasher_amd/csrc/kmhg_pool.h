@@ -5,7 +5,12 @@
 // Stream-ordered releases inside one host call (one build, query, ...) share ONE event: every
 // ordered release on the group's stream is deferred to the group's end, where a single event is
 // recorded for all of them.  (Each event record is a marker packet the command processor drains
-// the stream for; a build used to record ~14 of them back to back.)
+// the stream for; a build used to record ~14 of them back to back.)  A group whose owner has
+// already recorded an event of its own behind the group's last work hands that one over
+// (ReleaseGroupT::adopt) and the pool records none: the blocks wait for the owner's event, which
+// the pool only polls and waits for -- it never records, recycles or keeps it.  The owner keeps
+// the event alive, and does not destroy it, for as long as blocks may be pending behind it; it may
+// record it again (the entries then wait for that later work too, which is safe).
 //
 // The device sits behind `Dev`, a small backend whose stream and event handles are opaque
 // pointers (the engine's HipDev; a fake of malloc'ed blocks and scripted events in
@@ -150,8 +155,15 @@ class BlockPool {
   }
   // blocks still used by work queued on `stream`: one event recorded for all of them.  Where no
   // event can be made or recorded, the stream is waited for instead and they go straight back.
-  void release_behind(void* const* ps, size_t n, void* stream) {
+  // With `adopted`, an event the caller owns and has recorded on `stream` behind that work, none
+  // is recorded: the blocks wait for the caller's event and no entry owns it.
+  void release_behind(void* const* ps, size_t n, void* stream, void* adopted = nullptr) {
     if (n == 0) return;
+    if (adopted) {
+      std::lock_guard<std::mutex> g(mu_);
+      for (size_t i = 0; i < n; ++i) retire(ps[i], adopted);
+      return;
+    }
     void* ev = recorded_event(stream);
     std::lock_guard<std::mutex> g(mu_);
     const size_t before = pending_.size();
@@ -277,13 +289,18 @@ struct ReleaseGroupT {
   // set after a synchronize of `s` with no launch behind it: the blocks go straight back to the
   // pool, no event (a synchronous call's last step)
   bool synced = false;
+  // the owner's event, recorded on `s` behind the last work that uses the group's blocks (adopt)
+  void* adopted = nullptr;
   ReleaseGroupT(BlockPool<Dev>& pl, void* stream) : pool(pl), s(stream), prev(open) { open = this; }
   explicit ReleaseGroupT(void* stream) : ReleaseGroupT(BlockPool<Dev>::get(), stream) {}
   ~ReleaseGroupT() {
     open = prev;
     if (synced) pool.release_now(ps.data(), ps.size());
-    else pool.release_behind(ps.data(), ps.size(), s);
+    else pool.release_behind(ps.data(), ps.size(), s, adopted);
   }
+  // The group's blocks wait for `ev` instead of an event of the pool's: the caller has recorded it
+  // on `s`, launches nothing more that uses the blocks before the group ends, and keeps it alive.
+  void adopt(void* ev) { adopted = ev; }
   ReleaseGroupT(const ReleaseGroupT&) = delete;
   ReleaseGroupT& operator=(const ReleaseGroupT&) = delete;
 };

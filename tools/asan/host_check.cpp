@@ -70,6 +70,9 @@
 //                                             release <name>|null|unknown [<stream>]   with a
 //                                                                     stream: stream-ordered
 //                                             group_begin <stream> | synced | group_end
+//                                             own_event <stream>      an event of the caller's,
+//                                                                     made and recorded (counted)
+//                                             adopt <event>           the open group adopts it
 //                                             complete <event>        the event has completed
 //                                             fail alloc-oom|alloc-error|event|record <n>   the
 //                                                                     next n such calls fail
@@ -588,6 +591,13 @@ static int cmd_block_pool(const char* path) {
       groups.back()->synced = true;
     } else if (op == "group_end" && !groups.empty()) {
       groups.pop_back();
+    } else if (op == "own_event" && a.size() == 2) {   // made and recorded by the caller, not the pool
+      FakeDev d{&f};
+      void* ev = d.event();
+      if (!ev || !d.record(ev, stream(a[1]))) return 2;
+      ret = std::to_string((uintptr_t)ev);
+    } else if (op == "adopt" && a.size() == 2 && !groups.empty()) {
+      groups.back()->adopt(reinterpret_cast<void*>((uintptr_t)atoi(a[1].c_str())));
     } else if (op == "complete" && a.size() == 2) {
       std::lock_guard<std::mutex> g(f.mu);
       f.done.at((size_t)atoi(a[1].c_str())) = 1;
