@@ -395,6 +395,85 @@ int kmhg_blocks_copy_device(kmhg_blocks *b, void *d_dst, void *stream);
 int kmhg_blocks_fill(kmhg_blocks *b, int32_t *blocks);           /* host, 4 * n_blocks int32 */
 int kmhg_blocks_free(kmhg_blocks *b);
 
+/* seq.kmer.chains (not in the reference): the blocks linked across diagonals into chains.  A
+ * substitution stays on its diagonal and seq.kmer.blocks bridges it; an indel shifts the diagonal
+ * and splits an alignment into blocks, which this step joins again.
+ * Input: B blocks {i, j, span, hits} as seq.kmer.blocks returns them, in strictly ascending (i, j)
+ * order -- the index b = 0 .. B - 1 is that order -- and three parameters, max_dist >= 0,
+ * max_drift >= 0, min_hits >= 1.  For block b, ei = i + span - 1 and ej = j + span - 1 are its last
+ * row.
+ *  1. Candidates.  a may precede b when, with gi = i_b - ei_a - 1 and gj = j_b - ej_a - 1:
+ *     gi >= 0 and gj >= 0 (the blocks do not overlap in either coordinate);
+ *     max(gi, gj) <= max_dist; and |gj - gi| <= max_drift (|gj - gi| is the diagonal shift).
+ *  2. Cost.  cost(a, b) = gi + gj, below 2^32.  Keys are the u64 cost << 32 | index.
+ *  3. Predecessor.  pred(b) is the candidate a with the smallest key cost(a, b) << 32 | a; none
+ *     if b has no candidate.
+ *  4. Child.  Among all b with pred(b) = a, child(a) is the one with the smallest key
+ *     cost(a, b) << 32 | b.
+ *  5. Links.  Link a -> b exists iff pred(b) = a and child(a) = b.  Every block then has at most
+ *     one link in and at most one link out; the links form disjoint paths, and those paths are the
+ *     chains.  A block that lost the contest for its predecessor starts a chain of its own: it
+ *     does not fall back to a second choice.
+ *  6. A chain's record is six int32 {i, j, i.end, j.end, hits, blocks}: i, j of its first block;
+ *     i.end, j.end the ei, ej of its last block; hits the sum of its blocks' hits (a chain's blocks
+ *     are disjoint in i, so the sum stays below 2^31); blocks the count of its blocks.
+ *  7. Chains with hits >= min_hits are kept, ordered by the (i, j) of their first block.
+ *  8. Membership.  chain[b] is the 1-based index of block b's chain among the kept chains, 0 if
+ *     that chain was dropped: what lets a caller draw a chain as a polyline.
+ * So max_dist = 0 gives every block as its own chain {i, j, ei, ej, hits, 1} (two blocks with
+ * gi = gj = 0 would be one block); max_drift = 0 with max_dist = D >= max_gap reproduces
+ * seq.kmer.blocks(max_gap = D) on the same segments, {i, j, i.end - i + 1, hits} being those
+ * blocks' {i, j, span, hits}; at min_hits = 1 the chains' hits sum to the blocks' hits and their
+ * block counts to B.  This is greedy nearest-neighbour chaining, not the optimal-score dynamic
+ * program of minimap2.  The result is 6 x C int32 in R's column-major order plus B int32, and the
+ * same bytes on every run: every reduction is an integer minimum or sum.
+ *
+ * kmhg_blocks_chains chains any such blocks in device memory (16-byte aligned), on `stream`, which
+ * it waits for.  Refusals, KMHG_EINVAL, before any device work and in this order: "null argument"
+ * (out); "max_dist must not be negative"; "max_drift must not be negative"; "min_hits must be a
+ * positive integer"; "bad block count" (n_blocks < 0 or > 2^31 - 1); "null argument" (d_blocks
+ * with n_blocks > 0); "blocks must be 16-byte aligned" (d_blocks, whose records are read as one
+ * 16-byte load each).  max_dist and max_drift beyond int32 are legal and mean "any"; a min_hits
+ * beyond int32 keeps no chain.  Then, from the device: "blocks are not in ascending (i, j) order"
+ * (also for a repeated block); "blocks must have i, j >= 1, 1 <= hits <= span and ends within
+ * 2^31 - 1".  n_blocks = 0 gives an empty handle and d_blocks is not read.
+ *
+ * kmhg_chains_run_device / kmhg_chains_run: the query (as kmhg_blocks_run_device /
+ * kmhg_blocks_run name it) to chains in one call.  Its blocks are those of kmhg_query_blocks on
+ * the query's rows (row_free = 0) or of kmhg_blocks_run_device (row_free != 0), with min_len and
+ * max_gap as given and every block kept (min_hits applies to the chains); they stay in the handle,
+ * where chain[b] refers to them.  Refusals as those entries', with "max_dist must not be negative",
+ * "max_drift must not be negative" after max_gap's.  *n_rows <- the hit total.  KMHG_DEVICES is
+ * not honoured.
+ *
+ * The kmhg_chains handle owns the result.  kmhg_chains_device gives the device pointers (valid
+ * until kmhg_chains_free): the chains, chain[] (d_member) and the blocks (d_blocks: NULL from
+ * kmhg_blocks_chains, whose blocks are the caller's); every output but d_chains is optional.
+ * kmhg_chains_copy_device copies the chains (6 * n_chains int32), chain[] (n_blocks int32) and,
+ * where d_blocks is not NULL, the handle's blocks into caller device memory on `stream`;
+ * kmhg_chains_fill the chains into host memory;
+ * kmhg_chains_member_fill chain[] and, where `blocks` is not NULL, the handle's blocks (4 *
+ * n_blocks int32; "the handle holds no blocks" after kmhg_blocks_chains).
+ * kmhg_chains_free(NULL) is a no-op. */
+typedef struct kmhg_chains kmhg_chains;
+int kmhg_blocks_chains(const void *d_blocks, int64_t n_blocks, int64_t max_dist, int64_t max_drift,
+                       int64_t min_hits, void *stream, kmhg_chains **out, int64_t *n_chains);
+int kmhg_chains_run_device(kmhg_index *idx, const void *d_seq, size_t L, int k, int rc,
+                           int row_free, int64_t min_len, int64_t max_gap, int64_t max_dist,
+                           int64_t max_drift, int64_t min_hits, void *stream, kmhg_chains **out,
+                           int64_t *n_chains, int64_t *n_blocks, int64_t *n_rows);
+int kmhg_chains_run(kmhg_index *idx, const char *seq, size_t L, int k, int rc, int row_free,
+                    int64_t min_len, int64_t max_gap, int64_t max_dist, int64_t max_drift,
+                    int64_t min_hits, kmhg_chains **out, int64_t *n_chains, int64_t *n_blocks,
+                    int64_t *n_rows);
+int kmhg_chains_device(kmhg_chains *c, const int32_t **d_chains, int64_t *n_chains,
+                       const int32_t **d_member, const int32_t **d_blocks, int64_t *n_blocks);
+int kmhg_chains_copy_device(kmhg_chains *c, void *d_chains, void *d_member, void *d_blocks,
+                            void *stream);
+int kmhg_chains_fill(kmhg_chains *c, int32_t *chains);           /* host, 6 * n_chains int32 */
+int kmhg_chains_member_fill(kmhg_chains *c, int32_t *member, int32_t *blocks);
+int kmhg_chains_free(kmhg_chains *c);
+
 /* seq.kmer.raster (not in the reference): the dot plot as a binned count matrix, the one product
  * whose size does not grow with the number of hits.  The rows R are (i, j) int32 rows as for
  * seq.kmer.segs.  A frame is six int64 {i_lo, j_lo, bin_i, bin_j, n_i, n_j} with

@@ -22,6 +22,9 @@
  *                                                                     -> INTSXP 4 x B
  *   sequence_kmer_segments_rf, sequence_kmer_blocks_rf (not in the reference): the two above by
  *                                                  the route that never writes the positions
+ *   sequence_kmer_chains(ptr, seq, k, max_dist, max_drift, max_gap, min_len, min_hits, rc,
+ *                        row_free) (not in the reference)
+ *                                  -> named VECSXP[3]: INTSXP 6 x C, INTSXP 4 x B, INTSXP B
  *   sequence_kmer_raster(ptr, seq, k, bins, rc, i_range, j_range) (not in the reference)
  *                                                  -> named VECSXP[6], counts REALSXP n_i x n_j
  *
@@ -297,6 +300,66 @@ SEXP sequence_kmer_blocks(SEXP ptr_r, SEXP seq_r, SEXP k_r, SEXP max_gap_r, SEXP
 SEXP sequence_kmer_blocks_rf(SEXP ptr_r, SEXP seq_r, SEXP k_r, SEXP max_gap_r, SEXP min_len_r,
                              SEXP min_hits_r, SEXP rc_r) {
   return blocks_by(1, ptr_r, seq_r, k_r, max_gap_r, min_len_r, min_hits_r, rc_r);
+}
+
+/* Not in the reference: the blocks of sequence_kmer_blocks linked across diagonals into chains
+ * (kmhg_chains_run, include/kmhgpu.h).  Returns a named list: chains, INTSXP 6 x C of (i, j,
+ * i.end, j.end, hits, blocks) ordered by (i, j); blocks, INTSXP 4 x B of (i, j, span, hits), the
+ * blocks at min_hits = 1; chain, INTSXP B, the 1-based chain of every block (0: its chain was
+ * dropped by min_hits).  row_free != 0 takes the blocks by the route that never writes the
+ * positions.  The argument checks come first, in the C-ABI's words and order after the sequence's
+ * and k's own; the pointer must be a position index.  Exported, not registered, like
+ * sequence_kmer_blocks. */
+static const char *chains_fields[3] = {"chains", "blocks", "chain"};
+
+SEXP sequence_kmer_chains(SEXP ptr_r, SEXP seq_r, SEXP k_r, SEXP max_dist_r, SEXP max_drift_r,
+                          SEXP max_gap_r, SEXP min_len_r, SEXP min_hits_r, SEXP rc_r,
+                          SEXP row_free_r) {
+  if (TYPEOF(seq_r) != STRSXP || length(seq_r) != 1) error("seq_r should be a single sequence");
+  if (TYPEOF(k_r) != INTSXP || length(k_r) != 1) error("k should be an integer of length 1");
+  if (TYPEOF(min_len_r) != INTSXP || length(min_len_r) != 1 || INTEGER(min_len_r)[0] < 1)
+    error("min_len must be a positive integer");
+  if (TYPEOF(max_gap_r) != INTSXP || length(max_gap_r) != 1 || INTEGER(max_gap_r)[0] < 0)
+    error("max_gap must not be negative");
+  if (TYPEOF(max_dist_r) != INTSXP || length(max_dist_r) != 1 || INTEGER(max_dist_r)[0] < 0)
+    error("max_dist must not be negative");
+  if (TYPEOF(max_drift_r) != INTSXP || length(max_drift_r) != 1 || INTEGER(max_drift_r)[0] < 0)
+    error("max_drift must not be negative");
+  if (TYPEOF(min_hits_r) != INTSXP || length(min_hits_r) != 1 || INTEGER(min_hits_r)[0] < 1)
+    error("min_hits must be a positive integer");
+  if (TYPEOF(rc_r) != INTSXP || length(rc_r) != 1) error("rc should be an integer of length 1");
+  if (TYPEOF(row_free_r) != INTSXP || length(row_free_r) != 1)
+    error("row_free should be an integer of length 1");
+  kmhg_index *idx = gpu_index_of(ptr_r);
+  kmhg_info inf;
+  if (kmhg_index_info(idx, &inf) != KMHG_OK) error("%s", kmhg_last_error());
+  if (inf.kind != 0) error("blocks need a position index");
+  int k = asInteger(k_r);
+  SEXP s = STRING_ELT(seq_r, 0);
+  kmhg_chains *c = NULL;
+  int64_t nc = 0, nb = 0;
+  if (kmhg_chains_run(idx, CHAR(s), (size_t)length(s), k, INTEGER(rc_r)[0] != 0,
+                      INTEGER(row_free_r)[0] != 0, INTEGER(min_len_r)[0], INTEGER(max_gap_r)[0],
+                      INTEGER(max_dist_r)[0], INTEGER(max_drift_r)[0], INTEGER(min_hits_r)[0], &c,
+                      &nc, &nb, NULL) != KMHG_OK)
+    error("%s", kmhg_last_error());
+  if (nb > INT_MAX) {
+    kmhg_chains_free(c);
+    error("result has more than 2^31-1 columns (R matrix limit)");
+  }
+  SEXP ret = PROTECT(allocVector(VECSXP, 3));
+  SEXP nm = PROTECT(allocVector(STRSXP, 3));
+  for (int i = 0; i < 3; ++i) SET_STRING_ELT(nm, i, mkChar(chains_fields[i]));
+  setAttrib(ret, R_NamesSymbol, nm);
+  SEXP chains = SET_VECTOR_ELT(ret, 0, allocMatrix(INTSXP, 6, (int)nc));
+  SEXP blocks = SET_VECTOR_ELT(ret, 1, allocMatrix(INTSXP, 4, (int)nb));
+  SEXP chain = SET_VECTOR_ELT(ret, 2, allocVector(INTSXP, (int)nb));
+  int rc = kmhg_chains_fill(c, INTEGER(chains));
+  if (rc == KMHG_OK) rc = kmhg_chains_member_fill(c, INTEGER(chain), nb ? INTEGER(blocks) : NULL);
+  kmhg_chains_free(c);
+  if (rc != KMHG_OK) error("%s", kmhg_last_error());
+  UNPROTECT(2);
+  return ret;
 }
 
 /* Not in the reference: the dot plot as a binned count matrix (kmhg_raster_run, include/kmhgpu.h),

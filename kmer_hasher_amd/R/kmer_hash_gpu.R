@@ -101,6 +101,31 @@ seq.kmer.blocks <- function(ex.ptr, seq, k, max.gap=k, min.len=1, min.hits=1, rc
     t(m)
 }
 
+## not in the reference: seq.kmer.blocks' blocks linked across diagonals into chains.  An indel
+## shifts the diagonal and splits one alignment into several blocks.  Block a may precede block b
+## when b starts after a's last row in both coordinates, the larger of the two gaps (in windows) is
+## at most max.dist and their difference -- the diagonal shift -- at most max.drift (minimap2's -g
+## and -r).  Every block takes its nearest such predecessor, every block keeps the nearest of the
+## blocks that chose it, and the links both ends agree on form the chains (greedy nearest-neighbour
+## chaining, not minimap2's dynamic program).  Returns a list: chains, a matrix with columns i, j,
+## i.end, j.end, hits, blocks, ordered by (i, j); blocks, the matrix seq.kmer.blocks(ex.ptr, seq,
+## k, max.gap, min.len, 1, rc, row.free) gives; chain, per block the row of chains it belongs to (0
+## where min.hits dropped its chain).  min.hits keeps the chains of at least that many rows.  Draw
+## one chain as a polyline through its blocks:
+##   r <- seq.kmer.chains(ptr, seq, k); b <- r$blocks[r$chain == 1, , drop=FALSE]
+##   lines(c(rbind(b[,"j"], b[,"j"] + b[,"span"] - 1)), c(rbind(b[,"i"], b[,"i"] + b[,"span"] - 1)))
+## Position indices only.
+seq.kmer.chains <- function(ex.ptr, seq, k, max.dist=5000, max.drift=500, max.gap=k, min.len=1,
+                            min.hits=1, rc=FALSE, row.free=FALSE){
+    if(length(row.free) != 1 || is.na(row.free)) stop("row.free should be TRUE or FALSE")
+    r <- .Call("sequence_kmer_chains", ex.ptr, as.character(seq), as.integer(k),
+               as.integer(max.dist), as.integer(max.drift), as.integer(max.gap),
+               as.integer(min.len), as.integer(min.hits), as.integer(rc), as.integer(row.free))
+    rownames(r$chains) <- c("i", "j", "i.end", "j.end", "hits", "blocks")
+    rownames(r$blocks) <- c("i", "j", "span", "hits")
+    list(chains=t(r$chains), blocks=t(r$blocks), chain=r$chain)
+}
+
 ## not in the reference: the dot plot as a binned count matrix, for results too large to hold or
 ## plot as points.  The rows of seq.kmer.pos (rc=TRUE: of seq.kmer.pos.rc) are counted per cell on
 ## the device and never written, so the result's size does not depend on the number of hits and

@@ -8,11 +8,12 @@ kmer.spec.sh.n, count.kmers.fq.sh, kmer.spec.sh).
 from .api import (FIELDS, KMER_HASH_TAG, SUFFIX_HASH_N_TAG, SUFFIX_HASH_TAG, ExtPtr, KmerHashError,
                   count_kmers, count_kmers_fq_sh, count_kmers_fq_sh_rp, counts_table, kmer_pairs,
                   kmer_pos, kmer_spec_sh, kmer_spec_sh_n, make_kmer_hash, seq_kmer_depth_sh,
-                  seq_kmer_blocks, seq_kmer_pos, seq_kmer_pos_rc, seq_kmer_raster, seq_kmer_segs,
+                  seq_kmer_blocks, seq_kmer_chains, seq_kmer_pos, seq_kmer_pos_rc, seq_kmer_raster,
+                  seq_kmer_segs,
                   set_row_order)
 
 __all__ = ["make_kmer_hash", "kmer_pos", "seq_kmer_pos", "seq_kmer_pos_rc", "seq_kmer_segs",
-           "seq_kmer_blocks", "seq_kmer_raster",
+           "seq_kmer_blocks", "seq_kmer_chains", "seq_kmer_raster",
            "kmer_pairs", "count_kmers",
            "count_kmers_fq_sh_rp", "seq_kmer_depth_sh", "kmer_spec_sh_n", "count_kmers_fq_sh",
            "kmer_spec_sh", "counts_table", "set_row_order", "ExtPtr",

@@ -112,6 +112,19 @@ _PROTOS = {
     "kmhg_blocks_copy_device": (C.c_int, [vp, vp, vp]),
     "kmhg_blocks_fill": (C.c_int, [vp, vp]),
     "kmhg_blocks_free": (C.c_int, [vp]),
+    "kmhg_blocks_chains": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp,
+                                     C.POINTER(vp), i64p]),
+    "kmhg_chains_run_device": (C.c_int, [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int64,
+                                         C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp,
+                                         C.POINTER(vp), i64p, i64p, i64p]),
+    "kmhg_chains_run": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int64,
+                                  C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(vp), i64p,
+                                  i64p, i64p]),
+    "kmhg_chains_device": (C.c_int, [vp, C.POINTER(vp), i64p, C.POINTER(vp), C.POINTER(vp), i64p]),
+    "kmhg_chains_copy_device": (C.c_int, [vp, vp, vp, vp, vp]),
+    "kmhg_chains_fill": (C.c_int, [vp, vp]),
+    "kmhg_chains_member_fill": (C.c_int, [vp, vp, vp]),
+    "kmhg_chains_free": (C.c_int, [vp]),
     "kmhg_rows_raster": (C.c_int, [vp, C.c_int64, i64p, vp, vp]),
     "kmhg_query_raster": (C.c_int, [vp, i64p, vp, vp]),
     "kmhg_raster_run_device": (C.c_int, [vp, vp, C.c_size_t, C.c_int, C.c_int, i64p, vp, vp,

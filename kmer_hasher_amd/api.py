@@ -352,6 +352,50 @@ def seq_kmer_blocks(ex_ptr, seq, k, max_gap=None, min_len=1, min_hits=1, rc=Fals
     return blocks.reshape(-1, 4)
 
 
+def seq_kmer_chains(ex_ptr, seq, k, max_dist=5000, max_drift=500, max_gap=None, min_len=1,
+                    min_hits=1, rc=False, row_free=False) -> dict:
+    """seq.kmer.chains (not in the reference): the blocks of seq_kmer_blocks linked across
+    diagonals into chains.
+
+    An indel shifts the diagonal and splits one alignment into several blocks.  Block a may precede
+    block b when b starts after a ends in both coordinates, the larger of the two gaps (in windows)
+    is at most max_dist and their difference -- the diagonal shift -- at most max_drift (minimap2's
+    -g and -r).  Every block chooses its nearest such predecessor (the smallest sum of the two
+    gaps, then the lower block), every block keeps the nearest of the blocks that chose it, and the
+    links both ends agree on form the chains (include/kmhgpu.h has the definition; this is greedy
+    nearest-neighbour chaining, not minimap2's dynamic program).
+
+    Returns {"chains": (C, 6) int32 with columns (i, j, i.end, j.end, hits, blocks), ordered by
+    (i, j); "blocks": the (B, 4) int32 blocks seq_kmer_blocks(ex_ptr, seq, k, max_gap, min_len, 1,
+    rc) gives; "chain": (B,) int32, the 1-based row of `chains` each block belongs to, 0 where
+    min_hits dropped its chain}.  min_hits keeps the chains of at least that many rows.  max_gap
+    and row_free are seq_kmer_blocks'.  Only a position index (make_kmer_hash) is accepted."""
+    L = _lib.lib()
+    need = "blocks need a position index"
+    ints = [(min_len, "min_len must be a positive integer"), (max_gap, "max_gap must not be negative"),
+            (max_dist, "max_dist must not be negative"), (max_drift, "max_drift must not be negative"),
+            (min_hits, "min_hits must be a positive integer")]
+    p, b, kk, (ml, mg, md, mr, mh) = _dot_plot_args(ex_ptr, seq, k, need, ints)
+    g = C.c_void_p()
+    nc, nb = C.c_int64(), C.c_int64()
+    try:
+        rcode = L.kmhg_chains_run(p.handle, b, len(b), kk, 1 if rc else 0, 1 if row_free else 0, ml,
+                                  mg, md, mr, mh, C.byref(g), C.byref(nc), C.byref(nb), None)
+        if rcode in (_lib.KMHG_EINVAL, _lib.KMHG_EOVERFLOW):
+            raise KmerHashError(L.kmhg_last_error().decode())
+        _lib.check(rcode)
+        chains = np.empty(6 * nc.value, np.int32)
+        blocks = np.empty(4 * nb.value, np.int32)
+        member = np.empty(nb.value, np.int32)
+        if nc.value:
+            _lib.check(L.kmhg_chains_fill(g, chains.ctypes.data))
+        if nb.value:
+            _lib.check(L.kmhg_chains_member_fill(g, member.ctypes.data, blocks.ctypes.data))
+    finally:
+        L.kmhg_chains_free(g)
+    return {"chains": chains.reshape(-1, 6), "blocks": blocks.reshape(-1, 4), "chain": member}
+
+
 def raster_axis(lo: int, hi: int, bins: int) -> tuple[int, int]:
     """(bin width, bin count) of `bins` bins over lo..hi: width = ceil(length / bins), then
     count = ceil(length / width) -- at most `bins`, and the last bin may reach past hi."""

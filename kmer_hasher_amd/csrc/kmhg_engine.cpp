@@ -28,6 +28,7 @@
 
 #include "kmhg_common.h"
 #include "kmhg_blocks.h"
+#include "kmhg_chains.h"
 #include "kmhg_kernels.h"
 #include "kmhg_plan.h"
 #include "kmhg_hostwork.h"
@@ -646,6 +647,17 @@ struct kmhg_blocks {
   hipStream_t stream = nullptr;
   int64_t B = 0;
   DBuf<int32_t> blocks;
+};
+
+// seq.kmer.chains: the {i, j, i.end, j.end, hits, blocks} chains of B blocks and chain[b], the
+// 1-based chain of every block (kmhg_blocks_chains), complete when the handle is returned;
+// `blocks` holds the blocks themselves where the handle made them (kmhg_chains_run*).
+struct kmhg_chains {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  int64_t C = 0, B = 0;
+  DBuf<int32_t> chains, member, blocks;
+  bool holds_blocks = false;
 };
 
 namespace {
@@ -3961,6 +3973,248 @@ int kmhg_blocks_free(kmhg_blocks* b) {
     DeviceGuard dg(b->device);
     // the caller keeps the stream it made the blocks on alive until here (as for a query)
     HIPC(hipStreamSynchronize(b->stream));
+  });
+}
+
+// -------------------------------------------------------------------------- seq.kmer.chains
+namespace {
+
+void check_chain_params(int64_t max_dist, int64_t max_drift, int64_t min_hits) {
+  const ChainRefusal r = chain_check_params(max_dist, max_drift, min_hits);
+  if (r.code != KMHG_OK) fail(r.code, r.text);
+}
+
+// The chains of n_blocks > 0 blocks on the current device (kmhg_chains.hip; include/kmhgpu.h has
+// the definition), into g: keys / sort / prep / pred / link / jump / sum / count, then emit and
+// member.  Scratch is O(B) on `s`.  Waits for `s` once where the number of chains sizes the result
+// -- the input faults are answered there too: no pass leaves [0, B) whatever the blocks hold --
+// and once more at the end: `s` is idle when it returns.
+void chain_blocks(const int32_t* blocks, int64_t n_blocks, int64_t max_dist, int64_t max_drift,
+                  int64_t min_hits, hipStream_t s, kmhg_chains* g) {
+  const uint32_t B = (uint32_t)n_blocks;
+  const uint32_t dist = chain_limit(max_dist), drift = chain_limit(max_drift);
+  const uint32_t mh = chain_min_hits(min_hits);
+  HIPC(hipGetDevice(&g->device));
+  g->stream = s;
+  ReleaseGroup rg(s);
+  PinnedRec hrec = PinnedPool::get().take();
+  GiveBack give_back{hrec, s};
+  BuildMeta* hm = hrec.meta;            // n_small / n_large: the faults; n_pairs: chains
+  const uint64_t nt = ((uint64_t)B + TILE - 1) / TILE;
+  size_t tb = 0;
+  HIPC(chains_sort_temp_bytes(B, &tb));
+  DBuf<uint64_t> keys(2 * (size_t)B, s);            // {ei << 32 | b}: as made, sorted
+  DBuf<uint8_t> temp(std::max<size_t>(tb, 16), s);
+  DBuf<uint64_t> links(2 * (size_t)B, s);           // pred, child
+  DBuf<uint32_t> win(2 * (size_t)B, s);             // {lo, hi} per block
+  DBuf<int32_t> sej((size_t)B, s);                  // ej by sorted rank
+  DBuf<int32_t> ends(2 * (size_t)B, s);             // {ei, ej} of the last block, per first block
+  DBuf<uint32_t> nums(4 * (size_t)B, s);            // up; hits, count, cid (zeroed)
+  DBuf<uint64_t> tiles(nt + scan_u64_scratch(nt), s);
+  uint64_t *skey = keys.p + B, *pred = links.p, *child = links.p + B;
+  uint32_t *up = nums.p, *hits = nums.p + B, *count = nums.p + 2 * (size_t)B,
+           *cid = nums.p + 3 * (size_t)B;
+  __atomic_store_n(&hm->n_small, 0u, __ATOMIC_RELEASE);
+  __atomic_store_n(&hm->n_large, 0u, __ATOMIC_RELEASE);
+  LAUNCH("k_chains_keys", s, launch_chains_keys(blocks, B, keys.p, &hm->n_small, &hm->n_large, s));
+  hipError_t sort_err = hipSuccess;
+  LAUNCH("k_chains_sort", s, sort_err = launch_chains_sort(keys.p, B, skey, temp.p, tb, s));
+  HIPC(sort_err);
+  LAUNCH("k_chains_prep", s, launch_chains_prep(blocks, B, skey, dist, sej.p, win.p, s));
+  HIPC(hipMemsetAsync(child, 0xFF, (size_t)B * 8, s));
+  HIPC(hipMemsetAsync(hits, 0, (size_t)B * 12, s));
+  LAUNCH("k_chains_pred", s,
+         launch_chains_pred(blocks, B, skey, sej.p, win.p, dist, drift, pred, child, s));
+  LAUNCH("k_chains_link", s, launch_chains_link(B, pred, child, up, s));
+  for (int r = chain_rounds(B); r > 0; --r) LAUNCH("k_chains_jump", s, launch_chains_jump(B, up, s));
+  LAUNCH("k_chains_sum", s, launch_chains_sum(blocks, B, up, child, hits, count, ends.p, s));
+  LAUNCH("k_chains_order", s, launch_chains_count(B, up, hits, mh, tiles.p, s));
+  LAUNCH("k_scan_tiles_u64", s, launch_scan_u64(tiles.p, nt, &hm->n_pairs, tiles.p + nt, s));
+  HIPC(hipStreamSynchronize(s));
+  const ChainRefusal rf = chain_fault_refusal(
+      (__atomic_load_n(&hm->n_small, __ATOMIC_ACQUIRE) ? CHAIN_UNSORTED : 0u) |
+      (__atomic_load_n(&hm->n_large, __ATOMIC_ACQUIRE) ? CHAIN_BAD_BLOCK : 0u));
+  if (rf.code != KMHG_OK) fail(rf.code, rf.text);
+  const uint64_t C = __atomic_load_n(&hm->n_pairs, __ATOMIC_ACQUIRE);
+  if (C > B) fail(KMHG_EDEVICE, "more chains than blocks");
+  g->member.reset(B);
+  if (C) {
+    g->chains.reset(6 * (size_t)C);
+    LAUNCH("k_chains_order", s,
+           launch_chains_emit(blocks, B, up, hits, count, ends.p, mh, tiles.p, C, g->chains.p, cid,
+                              s));
+  }
+  LAUNCH("k_chains_member", s, launch_chains_member(B, up, cid, g->member.p, s));
+  HIPC(hipStreamSynchronize(s));
+  g->C = (int64_t)C;
+  g->B = (int64_t)B;
+  rg.synced = true;
+}
+
+struct QueryFree {
+  void operator()(kmhg_query* q) const {
+    try { free_query(q); } catch (const Error&) {}
+  }
+};
+
+// seq.kmer.chains of a query on the index's device: the blocks by the rows route (query_device,
+// then rows_blocks) or the row-free one (records_blocks), at min_hits = 1, kept in the handle and
+// chained.  *H <- the hit total.  No block gives an empty handle.
+kmhg_chains* query_chains(kmhg_index* idx, const uint8_t* d_seq, const QueryCall& c, bool row_free,
+                          int64_t min_len, int64_t max_gap, int64_t max_dist, int64_t max_drift,
+                          int64_t min_hits, hipStream_t s, uint64_t* H) {
+  auto g = std::make_unique<kmhg_chains>();
+  std::unique_ptr<kmhg_blocks> b;
+  if (row_free) {
+    b.reset(records_blocks(idx, d_seq, c, min_len, max_gap, 1, s, H));
+  } else {
+    if (!idx->canonical && idx->is_part == c.part && idx->sources)
+      fail(KMHG_EINVAL, "blocks need a position index");
+    std::unique_ptr<kmhg_query, QueryFree> q(query_device(idx, d_seq, c, s));
+    *H = (uint64_t)q->H;
+    if (q->H > INT32_MAX) fail(KMHG_EINVAL, "bad row count");
+    b.reset(rows_blocks(q->rows.p, q->H, min_len, max_gap, 1, s));
+    q.reset();                          // (the rows' stream is idle: rows_blocks ended in a wait)
+  }
+  g->holds_blocks = true;
+  if (!b->B) return g.release();
+  g->blocks.swap_with(b->blocks);
+  chain_blocks(g->blocks.p, b->B, max_dist, max_drift, min_hits, s, g.get());
+  return g.release();
+}
+
+void check_chains_args(int64_t min_len, int64_t max_gap, int64_t max_dist, int64_t max_drift,
+                       int64_t min_hits, kmhg_chains** out) {
+  if (!out) fail(KMHG_EINVAL, "null argument");
+  if (min_len < 1) fail(KMHG_EINVAL, "min_len must be a positive integer");
+  if (max_gap < 0) fail(KMHG_EINVAL, "max_gap must not be negative");
+  check_chain_params(max_dist, max_drift, min_hits);
+}
+
+}  // namespace
+
+int kmhg_blocks_chains(const void* d_blocks, int64_t n_blocks, int64_t max_dist, int64_t max_drift,
+                       int64_t min_hits, void* stream, kmhg_chains** out, int64_t* n_chains) {
+  return guarded([&] {
+    if (!out) fail(KMHG_EINVAL, "null argument");
+    check_chain_params(max_dist, max_drift, min_hits);
+    const ChainRefusal r = chain_check_count(n_blocks);
+    if (r.code != KMHG_OK) fail(r.code, r.text);
+    if (n_blocks && !d_blocks) fail(KMHG_EINVAL, "null argument");
+    if (n_blocks && (reinterpret_cast<uintptr_t>(d_blocks) & 15))
+      fail(KMHG_EINVAL, "blocks must be 16-byte aligned");
+    auto g = std::make_unique<kmhg_chains>();
+    if (n_blocks)                         // (none: no device call, an empty result is host-only)
+      chain_blocks(static_cast<const int32_t*>(d_blocks), n_blocks, max_dist, max_drift, min_hits,
+                   (hipStream_t)stream, g.get());
+    *out = g.release();
+    if (n_chains) *n_chains = (*out)->C;
+  });
+}
+
+int kmhg_chains_run_device(kmhg_index* idx, const void* d_seq, size_t L, int k, int rc,
+                           int row_free, int64_t min_len, int64_t max_gap, int64_t max_dist,
+                           int64_t max_drift, int64_t min_hits, void* stream, kmhg_chains** out,
+                           int64_t* n_chains, int64_t* n_blocks, int64_t* n_rows) {
+  return guarded([&] {
+    if (!idx || !d_seq) fail(KMHG_EINVAL, "null argument");
+    check_chains_args(min_len, max_gap, max_dist, max_drift, min_hits, out);
+    const QueryCall c = checked(query_call(L, k)).on_rc(rc != 0);
+    DeviceGuard g(idx->device);
+    uint64_t H = 0;
+    *out = query_chains(idx, static_cast<const uint8_t*>(d_seq), c, row_free != 0, min_len,
+                        max_gap, max_dist, max_drift, min_hits, (hipStream_t)stream, &H);
+    if (n_chains) *n_chains = (*out)->C;
+    if (n_blocks) *n_blocks = (*out)->B;
+    if (n_rows) *n_rows = (int64_t)H;
+  });
+}
+
+int kmhg_chains_run(kmhg_index* idx, const char* seq, size_t L, int k, int rc, int row_free,
+                    int64_t min_len, int64_t max_gap, int64_t max_dist, int64_t max_drift,
+                    int64_t min_hits, kmhg_chains** out, int64_t* n_chains, int64_t* n_blocks,
+                    int64_t* n_rows) {
+  return guarded([&] {
+    if (!idx || !seq) fail(KMHG_EINVAL, "null argument");
+    check_chains_args(min_len, max_gap, max_dist, max_drift, min_hits, out);
+    if (L < H2D_SCAN_MIN || k < 1 || k > 31 || L >= (size_t)INT32_MAX) {
+      L = effective_len(seq, L);             // (as kmhg_query_run)
+      check_query_args(L, k);
+    }
+    DeviceGuard g(idx->device);
+    hipStream_t s = lib_stream();
+    DBuf<uint8_t> d(L + 16, s);
+    L = h2d_cstring(d.p, seq, L, s);
+    uint64_t H = 0;
+    *out = query_chains(idx, d.p, checked(query_call(L, k)).on_rc(rc != 0), row_free != 0, min_len,
+                        max_gap, max_dist, max_drift, min_hits, s, &H);
+    if (n_chains) *n_chains = (*out)->C;
+    if (n_blocks) *n_blocks = (*out)->B;
+    if (n_rows) *n_rows = (int64_t)H;
+  });
+}
+
+int kmhg_chains_device(kmhg_chains* c, const int32_t** d_chains, int64_t* n_chains,
+                       const int32_t** d_member, const int32_t** d_blocks, int64_t* n_blocks) {
+  return guarded([&] {
+    if (!c || !d_chains) fail(KMHG_EINVAL, "null argument");
+    *d_chains = c->C ? c->chains.p : nullptr;
+    if (n_chains) *n_chains = c->C;
+    if (d_member) *d_member = c->B ? c->member.p : nullptr;
+    if (d_blocks) *d_blocks = c->B && c->holds_blocks ? c->blocks.p : nullptr;
+    if (n_blocks) *n_blocks = c->B;
+  });
+}
+
+int kmhg_chains_copy_device(kmhg_chains* c, void* d_chains, void* d_member, void* d_blocks,
+                            void* stream) {
+  return guarded([&] {
+    if (!c) fail(KMHG_EINVAL, "null argument");
+    if (d_blocks && !c->holds_blocks) fail(KMHG_EINVAL, "the handle holds no blocks");
+    if (!c->B) return;
+    if ((c->C && !d_chains) || !d_member) fail(KMHG_EINVAL, "null output");
+    DeviceGuard dg(c->device);
+    if (c->C)
+      HIPC(hipMemcpyAsync(d_chains, c->chains.p, (size_t)c->C * 24, hipMemcpyDeviceToDevice,
+                          (hipStream_t)stream));
+    HIPC(hipMemcpyAsync(d_member, c->member.p, (size_t)c->B * 4, hipMemcpyDeviceToDevice,
+                        (hipStream_t)stream));
+    if (d_blocks)
+      HIPC(hipMemcpyAsync(d_blocks, c->blocks.p, (size_t)c->B * 16, hipMemcpyDeviceToDevice,
+                          (hipStream_t)stream));
+  });
+}
+
+int kmhg_chains_fill(kmhg_chains* c, int32_t* chains) {
+  return guarded([&] {
+    if (!c) fail(KMHG_EINVAL, "null argument");
+    if (!c->C) return;
+    if (!chains) fail(KMHG_EINVAL, "null output");
+    DeviceGuard dg(c->device);
+    d2h_host(chains, c->chains.p, (size_t)c->C * 24, lib_stream());
+  });
+}
+
+int kmhg_chains_member_fill(kmhg_chains* c, int32_t* member, int32_t* blocks) {
+  return guarded([&] {
+    if (!c) fail(KMHG_EINVAL, "null argument");
+    if (blocks && !c->holds_blocks) fail(KMHG_EINVAL, "the handle holds no blocks");
+    if (!c->B) return;
+    if (!member) fail(KMHG_EINVAL, "null output");
+    DeviceGuard dg(c->device);
+    d2h_host(member, c->member.p, (size_t)c->B * 4, lib_stream());
+    if (blocks) d2h_host(blocks, c->blocks.p, (size_t)c->B * 16, lib_stream());
+  });
+}
+
+int kmhg_chains_free(kmhg_chains* c) {
+  return guarded([&] {
+    if (!c) return;
+    std::unique_ptr<kmhg_chains> own(c);
+    if (!c->B) return;
+    DeviceGuard dg(c->device);
+    // the caller keeps the stream it made the chains on alive until here (as for a query)
+    HIPC(hipStreamSynchronize(c->stream));
   });
 }
 

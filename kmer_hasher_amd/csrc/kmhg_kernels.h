@@ -177,6 +177,43 @@ void launch_blocks_order_count(const uint32_t* slot, uint64_t S, uint64_t* tile_
 void launch_blocks_order_emit(const uint32_t* slot, uint64_t S, const uint64_t* tile_off,
                               const uint64_t* bstart, const uint64_t* bend, const uint32_t* bpre,
                               const uint32_t* bpost, int32_t* out, hipStream_t s);
+// the blocks linked across diagonals into chains (kmhg_blocks_chains; kmhg_chains.hip, the
+// arithmetic in kmhg_chains.h), from B records {i, j, span, hits} in (i, j) order, 16-byte aligned.
+// keys: {ei << 32 | b} per block, *unsorted / *bad <- 1 (host-visible words, zeroed by the
+// caller) on the input faults.  sort: the keys ascending (temp: chains_sort_temp_bytes).  prep: ej
+// of the block at every sorted rank, and per block its window {lo, hi} of the sorted order (win:
+// 2 B u32, 8-byte aligned).  pred: per block the minimum key {cost << 32 | a} of its candidates
+// (all ones: none), and child[a] = the minimum {cost << 32 | b} over the blocks that chose a
+// (child: B u64, all ones from the caller).  link: up[b] = pred(b) where the link survives, else
+// b.  jump: up <- up^4 in place (chain_rounds(B) launches reach every chain's first block).  sum:
+// per first block the chain's hits and block count (both zeroed by the caller) and {ei, ej} of
+// its last block (ends: 2 B int32, 8-byte aligned).  count / emit (tile_off = the scanned
+// tile_cnt, C its total): the records {i, j, i.end, j.end, hits, blocks} of the first blocks with
+// hits >= min_hits, in block order, and cid[first block] = its record's index + 1 (cid zeroed by
+// the caller; out 8-byte aligned).  member: member[b] = cid[up[b]].
+void launch_chains_keys(const int32_t* blocks, uint32_t B, uint64_t* keys, uint32_t* unsorted,
+                        uint32_t* bad, hipStream_t s);
+hipError_t chains_sort_temp_bytes(uint32_t B, size_t* bytes);
+hipError_t launch_chains_sort(const uint64_t* keys, uint32_t B, uint64_t* skey, void* temp,
+                              size_t temp_bytes, hipStream_t s);
+void launch_chains_prep(const int32_t* blocks, uint32_t B, const uint64_t* skey, uint32_t max_dist,
+                        int32_t* sej, uint32_t* win, hipStream_t s);
+void launch_chains_pred(const int32_t* blocks, uint32_t B, const uint64_t* skey, const int32_t* sej,
+                        const uint32_t* win, uint32_t max_dist, uint32_t max_drift, uint64_t* pred,
+                        uint64_t* child, hipStream_t s);
+void launch_chains_link(uint32_t B, const uint64_t* pred, const uint64_t* child, uint32_t* up,
+                        hipStream_t s);
+void launch_chains_jump(uint32_t B, uint32_t* up, hipStream_t s);
+void launch_chains_sum(const int32_t* blocks, uint32_t B, const uint32_t* up, const uint64_t* child,
+                       uint32_t* hits, uint32_t* count, int32_t* ends, hipStream_t s);
+void launch_chains_count(uint32_t B, const uint32_t* up, const uint32_t* hits, uint32_t min_hits,
+                         uint64_t* tile_cnt, hipStream_t s);
+void launch_chains_emit(const int32_t* blocks, uint32_t B, const uint32_t* up, const uint32_t* hits,
+                        const uint32_t* count, const int32_t* ends, uint32_t min_hits,
+                        const uint64_t* tile_off, uint64_t C, int32_t* out, uint32_t* cid,
+                        hipStream_t s);
+void launch_chains_member(uint32_t B, const uint32_t* up, const uint32_t* cid, int32_t* member,
+                          hipStream_t s);
 // seq.kmer.raster (kmhg_raster.hip, the arithmetic in kmhg_raster.h): out[cell] += the rows of
 // each cell of the checked frame f; out = n_i * n_j u32, zeroed by the caller.  rows: n plain
 // (i, j) rows in any order.  records: the rows of a probed query (qrec / qmulti of Nw windows from

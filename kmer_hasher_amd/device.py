@@ -229,6 +229,24 @@ class DeviceIndex:
                 C.byref(h)))
         return _blocks_tensor(g, n.value, seq.device), h.value
 
+    def chains(self, seq: torch.Tensor, k: int, max_dist: int = 5000, max_drift: int = 500,
+               max_gap: int | None = None, min_len: int = 1, min_hits: int = 1, rc: bool = False,
+               row_free: bool = False, stream=None):
+        """kmhg_chains_run_device (seq.kmer.chains): the blocks of query(seq, k).blocks(max_gap,
+        min_len) -- of blocks(seq, k, max_gap, min_len) with row_free -- chained by blocks_chains:
+        ((C, 6) int32 chains, (B, 4) int32 blocks, (B,) int32 chain[b], n_rows).  max_gap=None
+        means k; min_hits applies to the chains.  Synchronous."""
+        _check_seq(seq)
+        g = C.c_void_p()
+        nc, nb, h = C.c_int64(), C.c_int64(), C.c_int64()
+        with torch.cuda.device(seq.device):
+            _lib.check(_lib.lib().kmhg_chains_run_device(
+                self._h, C.c_void_p(seq.data_ptr()), seq.numel(), k, 1 if rc else 0,
+                1 if row_free else 0, int(min_len), int(k if max_gap is None else max_gap),
+                int(max_dist), int(max_drift), int(min_hits), _stream_ptr(stream), C.byref(g),
+                C.byref(nc), C.byref(nb), C.byref(h)))
+        return _chains_tensors(g, nc.value, nb.value, seq.device, True, stream) + (h.value,)
+
     def positions(self, opt: int, stream=None) -> dict:
         """kmer.pos into device tensors: {'kmer': uint8 (U, k+1), 'pos': int32 (N, 2),
         'pair.pos': int32 (P, 3), 'count': int32 (U,)} for the requested bits."""
@@ -580,6 +598,53 @@ def rows_blocks(rows: torch.Tensor, max_gap: int, min_len: int = 1, min_hits: in
     return _blocks_tensor(g, n.value, rows.device)
 
 
+def _chains_tensors(h: C.c_void_p, n_chains: int, n_blocks: int, device, with_blocks: bool,
+                    stream=None):
+    """The tensors of a kmhg_chains handle, copied out of it on `stream`; the handle is freed.
+    ((C, 6) int32 chains, (B,) int32 chain[b]) and, with_blocks, the (B, 4) int32 blocks."""
+    L = _lib.lib()
+    try:
+        chains = torch.empty((n_chains, 6), dtype=torch.int32, device=device)
+        member = torch.empty((n_blocks,), dtype=torch.int32, device=device)
+        blocks = torch.empty((n_blocks, 4), dtype=torch.int32, device=device) if with_blocks \
+            else None
+        if n_blocks:
+            with torch.cuda.device(device):
+                _lib.check(L.kmhg_chains_copy_device(
+                    h, C.c_void_p(chains.data_ptr() if n_chains else None),
+                    C.c_void_p(member.data_ptr()),
+                    C.c_void_p(blocks.data_ptr()) if with_blocks else None, _stream_ptr(stream)))
+    finally:
+        L.kmhg_chains_free(h)             # (waits for the stream the chains were made on)
+    return (chains, blocks, member) if with_blocks else (chains, member)
+
+
+def blocks_chains(blocks: torch.Tensor, max_dist: int, max_drift: int, min_hits: int = 1,
+                  stream=None) -> tuple[torch.Tensor, torch.Tensor]:
+    """kmhg_blocks_chains (seq.kmer.chains): the (B, 4) int32 device blocks {i, j, span, hits} of
+    rows_blocks -- strictly ascending by (i, j) -- linked across diagonals: block a may precede
+    block b when b starts after a's last row in both coordinates, the larger gap is at most
+    max_dist and the two gaps differ by at most max_drift; every block takes its nearest such
+    predecessor, and a link holds where the predecessor's nearest follower is that block
+    (include/kmhgpu.h).  Returns (chains, member): (C, 6) int32 {i, j, i.end, j.end, hits, blocks}
+    of the chains with hits >= min_hits, ordered by (i, j), and (B,) int32, the 1-based chain of
+    every block (0: dropped).  Synchronous."""
+    if not (blocks.is_cuda and blocks.dtype == torch.int32 and blocks.dim() == 2 and
+            blocks.shape[1] == 4):
+        raise TypeError("blocks must be a (B, 4) torch.int32 CUDA tensor")
+    blocks = blocks.contiguous()
+    if blocks.shape[0] and blocks.data_ptr() % 16:
+        blocks = blocks.clone()
+    g = C.c_void_p()
+    n = C.c_int64()
+    with torch.cuda.device(blocks.device):
+        _lib.check(_lib.lib().kmhg_blocks_chains(
+            C.c_void_p(blocks.data_ptr() if blocks.shape[0] else None), blocks.shape[0],
+            int(max_dist), int(max_drift), int(min_hits), _stream_ptr(stream), C.byref(g),
+            C.byref(n)))
+    return _chains_tensors(g, n.value, blocks.shape[0], blocks.device, False, stream)
+
+
 def _raster_args(frame, out, device):
     """The int64[6] frame {i_lo, j_lo, bin_i, bin_j, n_i, n_j} and the int32 tensor of n_i * n_j
     elements the library fills with u32 bits (`out`, or a new one).  A frame the library will
@@ -703,6 +768,15 @@ class DeviceQuery:
         _lib.check(_lib.lib().kmhg_query_blocks(self._h, int(min_len), int(max_gap), int(min_hits),
                                                 C.byref(g), C.byref(n)))
         return _blocks_tensor(g, n.value, self.device)
+
+    def chains(self, max_dist: int = 5000, max_drift: int = 500, max_gap: int = 0,
+               min_len: int = 1, min_hits: int = 1):
+        """This query's blocks(max_gap, min_len) chained by blocks_chains(max_dist, max_drift,
+        min_hits): ((C, 6) int32 chains, (B, 4) int32 blocks, (B,) int32 chain[b]) on the query's
+        device.  (The query does not know its k: max_gap is the caller's, 0 = the segments.)"""
+        blocks = self.blocks(max_gap, min_len)
+        chains, member = blocks_chains(blocks, max_dist, max_drift, min_hits)
+        return chains, blocks, member
 
     def raster(self, frame, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
         """kmhg_query_raster: this query's rows binned into `frame`, an int64 (n_i, n_j) tensor on
