@@ -52,8 +52,8 @@
 // between equivalent paths and change no result; fault injection (KMHG_TEST_DISORDER); and the
 // A/B-only switches (KMHG_D2H, KMHG_D2H_HUGE, KMHG_HOST_RUNS, KMHG_HOST_PAIRS, KMHG_HOST_POOL,
 // KMHG_COUNT_BID, KMHG_RK_CAP, KMHG_SH_SPAN (the span_max given to read_batches, kmhg_reads.h),
-// KMHG_POOL_DEPTH, KMHG_POOL_BESTFIT, KMHG_POOL_TRACE (the pool's: PoolKnobs, kmhg_pool.h, filled
-// once by HipDev::knobs below)).
+// KMHG_POOL_DEPTH, KMHG_POOL_AHEAD, KMHG_POOL_STREAM, KMHG_POOL_BESTFIT, KMHG_POOL_TRACE (the
+// pool's: PoolKnobs, kmhg_pool.h, filled once by HipDev::knobs below)).
 namespace kmhg {
 inline const char* test_build_knob(const char* name) {
 #ifdef KMHG_TEST_BUILD
@@ -107,10 +107,13 @@ int guarded(F&& f) {
 // out-of-memory answer is cleared from the runtime's last-error slot, since the pool trims its
 // cache and asks again.
 struct HipDev {
-  static PoolKnobs knobs() {          // test build: KMHG_POOL_DEPTH / _BESTFIT / _TRACE
+  static PoolKnobs knobs() {   // test build: KMHG_POOL_DEPTH / _AHEAD / _STREAM / _BESTFIT / _TRACE
     PoolKnobs kn;
     if (const char* e = test_build_knob("KMHG_POOL_DEPTH"))
       kn.depth = (size_t)std::max(1, std::min(8, std::atoi(e)));
+    if (const char* e = test_build_knob("KMHG_POOL_AHEAD"))
+      kn.ahead = (size_t)std::max(1, std::min(8, std::atoi(e)));
+    if (const char* e = test_build_knob("KMHG_POOL_STREAM")) kn.same_stream = e[0] != '0';
     if (const char* e = test_build_knob("KMHG_POOL_BESTFIT")) kn.best_fit = e[0] != '0';
     kn.trace = test_build_knob("KMHG_POOL_TRACE") != nullptr;
     return kn;
@@ -151,6 +154,14 @@ struct HipDev {
 using DevicePool = BlockPool<HipDev>;
 using ReleaseGroup = ReleaseGroupT<HipDev>;
 
+// The stream a new buffer is first used on: every first touch of it is a kernel, memset or copy
+// queued on `s`.  The pool may then hand out a block that earlier work of `s` still uses, with
+// no host wait (kmhg_pool.h, same-stream reuse).  A buffer first touched by the host, by a copy
+// with no stream or by another stream is made without it.
+struct FirstUseOn {
+  hipStream_t s;
+};
+
 // RAII device buffer from the pool.  A buffer bound to a stream is released stream-ordered
 // (kernels still queued on that stream may use it after the C++ object dies).
 template <class T>
@@ -162,6 +173,7 @@ struct DBuf {
   DBuf() = default;
   explicit DBuf(size_t count) { reset(count); }
   DBuf(size_t count, hipStream_t stream) { reset(count); bind(stream); }
+  DBuf(size_t count, FirstUseOn on) { reset(count, on); }
   ~DBuf() { free(); }
   DBuf(const DBuf&) = delete;
   DBuf& operator=(const DBuf&) = delete;
@@ -170,6 +182,13 @@ struct DBuf {
     free();
     n = count;
     p = static_cast<T*>(DevicePool::get().alloc(std::max<size_t>(count, 1) * sizeof(T)));
+  }
+  // first used on on.s, and bound to it: released stream-ordered from here on
+  void reset(size_t count, FirstUseOn on) {
+    free();
+    n = count;
+    p = static_cast<T*>(DevicePool::get().alloc(std::max<size_t>(count, 1) * sizeof(T), on.s));
+    bind(on.s);
   }
   void free() {
     if (p) DevicePool::get().release(p, s, ordered);
@@ -198,18 +217,10 @@ class PinnedPool {
     static PinnedPool p;
     return p;
   }
+  // At most PoolKnobs::ahead builds freed unwaited are unfinished when this returns (RecordPool,
+  // kmhg_pool.h): a further take waits for the oldest one's event.
   PinnedRec take() {
-    std::lock_guard<std::mutex> g(mu_);
-    for (size_t i = 0; i < pending_.size();) {
-      if (hipEventQuery(pending_[i].ev) == hipSuccess) {
-        free_.push_back(pending_[i]);
-        pending_[i] = pending_.back();
-        pending_.pop_back();
-      } else {
-        ++i;
-      }
-    }
-    if (free_.empty()) {
+    PinnedRec r = recs_.take([](std::vector<PinnedRec>& out) {
       constexpr int kSlots = 64;
       BuildMeta* blk = nullptr;
       HIPC(hipHostMalloc(reinterpret_cast<void**>(&blk), sizeof(BuildMeta) * kSlots,
@@ -221,23 +232,19 @@ class PinnedPool {
         // record behind this event.  (Without it the 10 Mbp build measured 0.1744 against 0.1771
         // ms, the two sets of runs overlapping: not kept)
         HIPC(hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
-        free_.push_back(r);
+        out.push_back(r);
       }
-    }
-    PinnedRec r = free_.back();
-    free_.pop_back();
+    });
     std::memset(r.meta, 0, sizeof(*r.meta));
     return r;
   }
   void give(PinnedRec r, bool in_flight) {
     if (!r.meta) return;
-    std::lock_guard<std::mutex> g(mu_);
-    (in_flight ? pending_ : free_).push_back(r);
+    recs_.give(r, in_flight);
   }
 
  private:
-  std::mutex mu_;
-  std::vector<PinnedRec> free_, pending_;
+  RecordPool<HipDev, PinnedRec> recs_{HipDev::knobs().ahead};
 };
 // returns a record taken for a host round trip that the scope waited for (any exit path)
 // On an exception path the device may still write into the record (a queued scan's total), so
@@ -873,6 +880,10 @@ struct StreamPtrs {
 
 kmhg_index* build_device_v2(const BuildRequest& rq, const StreamPtrs& in, hipStream_t s) {
   ReleaseGroup rg(s);             // the scratch buffers below: one release event
+  // Every buffer of the build, the index's own included, is first touched by a kernel, memset or
+  // copy queued on s: a build queued behind another on one stream takes over its blocks while
+  // that one still runs, with no host wait in between.
+  const FirstUseOn on{s};
   const BuildKnobs kn = read_build_knobs();
   const BuildPlan P = plan_build(rq, kn, bucket_round_of_current_device());
   if (P.err != KMHG_OK) fail(P.err, P.msg);
@@ -902,8 +913,7 @@ kmhg_index* build_device_v2(const BuildRequest& rq, const StreamPtrs& in, hipStr
   const uint8_t* d_seq = in.d_seq;
   DBuf<uint8_t> aligned_copy;
   if (!from_keys && (reinterpret_cast<uintptr_t>(d_seq) & 15) != 0) {
-    aligned_copy.reset((size_t)L);
-    aligned_copy.bind(s);
+    aligned_copy.reset((size_t)L, on);
     HIPC(hipMemcpyAsync(aligned_copy.p, d_seq, (size_t)L, hipMemcpyDeviceToDevice, s));
     d_seq = aligned_copy.p;
   }
@@ -911,18 +921,18 @@ kmhg_index* build_device_v2(const BuildRequest& rq, const StreamPtrs& in, hipStr
   // two (first array, position array) buffer pairs, stream p on side P.side(p), each side as
   // wide as the plan says (+ pad)
   auto kwords = [&](int sd) { return ((uint64_t)(Nw + PTILE) * P.key_bytes[sd] + 7) / 8; };
-  DBuf<uint64_t> kA(kwords(0), s), kB(kwords(1), s);
-  DBuf<uint32_t> pA(P.pos_array[0] ? Nw + PTILE : 1, s), pB(P.pos_array[1] ? Nw + PTILE : 1, s);
+  DBuf<uint64_t> kA(kwords(0), on), kB(kwords(1), on);
+  DBuf<uint32_t> pA(P.pos_array[0] ? Nw + PTILE : 1, on), pB(P.pos_array[1] ? Nw + PTILE : 1, on);
   auto kptr = [&](int p) -> void* {
     return p < 0 && from_keys ? const_cast<uint64_t*>(d_keys) : P.side(p) ? kB.p : kA.p;
   };
   auto pptr = [&](int p) { return P.side(p) ? pB.p : pA.p; };
   const uint32_t pad = (uint32_t)Nw;
-  DBuf<uint32_t> hist(nhist, s);
-  DBuf<uint32_t> start((uint64_t)nb + 1, s);
-  DBuf<uint32_t> segb(P.pack8 ? (uint64_t)R * (P.nseg8 + 1) : 1, s);
+  DBuf<uint32_t> hist(nhist, on);
+  DBuf<uint32_t> start((uint64_t)nb + 1, on);
+  DBuf<uint32_t> segb(P.pack8 ? (uint64_t)R * (P.nseg8 + 1) : 1, on);
   // one digit buffer: pass p's histogram has read it before pass p rewrites it for pass p + 1
-  DBuf<uint16_t> dsb(P.ds_on ? ((uint64_t)Nw + PTILE + 8) / (P.ds8 ? 2 : 1) + 8 : 1, s);
+  DBuf<uint16_t> dsb(P.ds_on ? ((uint64_t)Nw + PTILE + 8) / (P.ds8 ? 2 : 1) + 8 : 1, on);
   uint8_t* ds8p = P.ds8 ? reinterpret_cast<uint8_t*>(dsb.p) : nullptr;
   uint16_t* ds16p = P.ds8 ? nullptr : dsb.p;
   const Pack8 pk8{P.pack8 ? P.sh8 : 0, segb.p, P.nseg8, mk_digit(1, R)};
@@ -930,31 +940,31 @@ kmhg_index* build_device_v2(const BuildRequest& rq, const StreamPtrs& in, hipStr
   const size_t off_meta = 64, off_status = 128;
   const uint32_t n_status = P.scan_tiles + 1;               // look-back words + ticket
   const size_t scratch_bytes = off_status + (size_t)n_status * 8;
-  DBuf<uint8_t> scratch(scratch_bytes, s);
+  DBuf<uint8_t> scratch(scratch_bytes, on);
   uint8_t* sc = scratch.p;
   uint32_t* n_valid = reinterpret_cast<uint32_t*>(sc);
   BuildMeta* meta = reinterpret_cast<BuildMeta*>(sc + off_meta);
   uint64_t* status = reinterpret_cast<uint64_t*>(sc + off_status);
   idx->rec = PinnedPool::get().take();                     // V_stats writes the totals here
-  if (!co_auto) idx->table.reset(idx->slots());
-  idx->positions.reset(P.no_pos ? 1 : Nw);
-  idx->bstats.reset(nb);            // kept: a batch index's walk takes its row offsets from it
+  if (!co_auto) idx->table.reset(idx->slots(), on);
+  idx->positions.reset(P.no_pos ? 1 : Nw, on);
+  idx->bstats.reset(nb, on);          // kept: a batch index's walk takes its row offsets from it
   // co_auto: HLL rows of the first histogram pass, V_hll's registers + ticket, its pinned record
-  DBuf<uint32_t> hll_rows(co_auto ? (size_t)ntiles * (HLL_REGS / 4) : 1, s);
-  DBuf<uint32_t> hll_regs(co_auto ? HLL_PART_WORDS : 1, s);
+  DBuf<uint32_t> hll_rows(co_auto ? (size_t)ntiles * (HLL_REGS / 4) : 1, on);
+  DBuf<uint32_t> hll_regs(co_auto ? HLL_PART_WORDS : 1, on);
   PinnedRec hrec;
   if (co_auto) hrec = PinnedPool::get().take();
 
   // bucket starts straight from the histograms (V_bounds_lo), one level per pass p >= 1:
   // lo_save = pass 0's digit starts (saved by pass 1's V_hist), lvA / lvB = S_p of the passes
   // before the last (3+ passes), the last level writes `start`
-  DBuf<uint32_t> lo_save(passes >= 2 ? R : 1, s);
+  DBuf<uint32_t> lo_save(passes >= 2 ? R : 1, on);
   uint64_t r_top = 1;                                   // R^(passes - 1)
   for (uint32_t i = 1; i < passes; ++i) r_top *= R;
-  DBuf<uint32_t> lvA(passes >= 3 ? r_top + 1 : 1, s), lvB(passes >= 4 ? r_top + 1 : 1, s);
+  DBuf<uint32_t> lvA(passes >= 3 ? r_top + 1 : 1, on), lvB(passes >= 4 ? r_top + 1 : 1, on);
   uint32_t div = 1;
   DiagBlock db{nullptr, nullptr, nullptr};
-  DBuf<uint32_t> tcnt(partc ? ntiles : 1, s);
+  DBuf<uint32_t> tcnt(partc ? ntiles : 1, on);
   if (from_keys) {   // pass 0 reads the caller's key stream in place (positions implicit)
     HIPC(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(n_valid), (int)Nw, 1, s));
     HIPC(hipMemsetAsync(meta, 0, sizeof(BuildMeta), s));
@@ -962,7 +972,7 @@ kmhg_index* build_device_v2(const BuildRequest& rq, const StreamPtrs& in, hipStr
     // a position index keeps its sequence's code words + window bits for the diagonal query
     // path (code words + N flags, 0.5 B per window with the first query's bits; V_hist0 writes them)
     if (rq.codes) {
-      idx->dcodes.reset(diag_block_words(Nw));
+      idx->dcodes.reset(diag_block_words(Nw), on);
       db = idx->diag_block_of();
     }
     LAUNCH("k_v2_hist0", s,
@@ -1005,8 +1015,7 @@ kmhg_index* build_device_v2(const BuildRequest& rq, const StreamPtrs& in, hipStr
     C = std::max<uint32_t>(1u, (uint32_t)(((uint64_t)nv + PTILE - 1) / PTILE));
     nh = (uint64_t)R * C;
     nst = tiles_for(nh) + 1;
-    hist1.reset(nh);
-    hist1.bind(s);
+    hist1.reset(nh, on);
     hp = hist1.p;
     // pass 0's digit starts (its scanned column 0), which pass 1's V_hist saves otherwise
     if (!partc)
@@ -1085,7 +1094,7 @@ kmhg_index* build_device_v2(const BuildRequest& rq, const StreamPtrs& in, hipStr
     idx->co_spread = co_spread_for(idx->co_est, n_keys_valid, kn.co_spread);
     gb = Geom{nb / (uint32_t)idx->co_spread, V2_CAPW};
     idx->geom = gb;
-    idx->table.reset(idx->slots());
+    idx->table.reset(idx->slots(), on);
   }
   if (passes == 1) {
     // one pass (pass 0 reads chars or the caller's keys): the starts are the scanned column 0
@@ -1113,8 +1122,7 @@ kmhg_index* build_device_v2(const BuildRequest& rq, const StreamPtrs& in, hipStr
   uint32_t* rep = nullptr;
   if (P.want_tags) {
     try {
-      idx->ptag.reset(idx->slots() + 32);    // + the 32-B span the last probe group reads
-      idx->ptag.bind(s);
+      idx->ptag.reset(idx->slots() + 32, on);    // + the 32-B span the last probe group reads
       tg = idx->ptag.p;
       rep = db.uniq;
       HIPC(hipMemsetAsync(rep, 0, diag_uniq_words(Nw) * 4, s));

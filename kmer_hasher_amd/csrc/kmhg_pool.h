@@ -12,6 +12,22 @@
 // the event alive, and does not destroy it, for as long as blocks may be pending behind it; it may
 // record it again (the entries then wait for that later work too, which is safe).
 //
+// Same-stream reuse: a pending block remembers the stream its release was ordered behind, and a
+// request that names the stream its block is first used on (alloc(bytes, stream)) takes a pending
+// block of its class released behind that very stream at once -- no host wait, no event query.
+// Stream order already puts every use the new owner queues behind the work the block was released
+// behind, so back-to-back builds on one stream reuse each other's blocks while the device is
+// still busy with the earlier one, and the host enqueues build i + 1 while build i runs.  Such a
+// request polls the pending events only when neither the free list nor that path serves it.  A
+// block's first use must then be work queued on that stream: a block first touched by the host
+// or by another stream is asked for without one (alloc(bytes)) and waits as before.  A taken
+// block that owned its batch's event passes the event on to a block still pending behind it,
+// and recycles it only when it was the last (a recycled event may be recorded on another stream,
+// so it must not return while a block still waits behind it).  Streams are told apart by their
+// handles: a caller that destroys a stream with blocks still pending behind it trims the pool
+// first.  How far the host may run ahead of the device is bounded by RecordPool below, not by
+// the pool's depth.
+//
 // The device sits behind `Dev`, a small backend whose stream and event handles are opaque
 // pointers (the engine's HipDev; a fake of malloc'ed blocks and scripted events in
 // tools/asan/host_check).  A Dev provides
@@ -27,7 +43,7 @@
 //   static PoolKnobs knobs()                (only for BlockPool::get())
 // All control flow is here; nothing here reads the environment.  tools/asan/host_check runs the
 // pool under ASan + UBSan against literal scenarios and host_check_tsan runs it from four threads
-// (tests/test_pool_host.py).
+// (tests/test_pool_host.py, tests/test_pool_stream_reuse.py).
 #pragma once
 #include <stdint.h>
 
@@ -54,8 +70,12 @@ inline size_t pool_size_class(size_t b) {
 
 // The test build's switches of the pool (defaults = the product).
 struct PoolKnobs {
-  size_t depth = 1;       // KMHG_POOL_DEPTH, 1..8: blocks of a class before a request waits for
-                          // one (depth 2 measured: no gain)
+  size_t depth = 1;       // KMHG_POOL_DEPTH, 1..8: blocks of a class before a request with no
+                          // stream (or another stream's) waits for one; same-stream requests take
+                          // a pending block without waiting and never grow past it either
+  size_t ahead = 2;       // KMHG_POOL_AHEAD, 1..8: builds freed unwaited that may be unfinished
+                          // before the host waits for the oldest (RecordPool)
+  bool same_stream = true;   // KMHG_POOL_STREAM=0: off (A/B: every request waits as before)
   bool best_fit = true;   // KMHG_POOL_BESTFIT=0: off
   bool trace = false;     // KMHG_POOL_TRACE: a stderr line per device allocation
 };
@@ -69,7 +89,7 @@ template <class Dev>
 class BlockPool {
  public:
   using Key = std::pair<int, size_t>;          // (device, size class)
-  struct Block { void* p; Key key; void* ev; bool owns_ev; };
+  struct Block { void* p; Key key; void* ev; bool owns_ev; void* stream = nullptr; };
   struct Snapshot {                            // for tests: every block the pool knows, by state
     std::vector<Block> live, free, pending;
     size_t idle_events, cached;
@@ -83,20 +103,31 @@ class BlockPool {
     return p;
   }
 
-  void* alloc(size_t bytes) {
+  // A block first touched by the host or by a stream unknown here: never one that queued work
+  // may still use.
+  void* alloc(size_t bytes) { return alloc_for(bytes, false, nullptr); }
+  // A block whose first use is work queued on `stream` (nullptr: the null stream): it may be one
+  // released behind earlier work of that stream, taken without waiting for that work.
+  void* alloc(size_t bytes, void* stream) { return alloc_for(bytes, kn_.same_stream, stream); }
+
+ private:
+  void* alloc_for(size_t bytes, bool on_stream, void* stream) {
     if (bytes == 0) bytes = 256;
     const Key key{dev_.current(), pool_size_class(bytes)};
     const size_t sz = key.second;
     {
       std::unique_lock<std::mutex> g(mu_);
+      if (on_stream) {              // a free block, else the stream's own pending one: no poll
+        auto fl = free_.find(key);
+        if (fl != free_.end() && !fl->second.empty()) return take(fl);
+        if (void* p = take_pending_of(key, stream)) return p;
+      }
       poll_pending();
       auto fl = free_.find(key);
       if (fl != free_.end() && !fl->second.empty()) return take(fl);
-      // a block of this size still in use by queued work: wait for it rather than grow the
-      // pool -- the back-pressure that bounds how far asynchronous builds run ahead.  Up to
-      // depth blocks of a size class exist before a request waits.  (Depth 2, so that the host
-      // enqueues build i + 1 while build i runs, measured no faster at 10 / 100 / 500 Mbp:
-      // the gaps between a build's kernels are the device's, not the host's enqueue.)
+      // a block of this size still in use by queued work (of another stream, or the request
+      // names none): wait for it rather than grow the pool.  Up to depth blocks of a size
+      // class exist before a request waits.
       auto n = count_.find(key);
       if (n != count_.end() && n->second >= kn_.depth) {
         for (size_t i = 0; i < pending_.size(); ++i) {
@@ -139,6 +170,7 @@ class BlockPool {
     return p;
   }
 
+ public:
   // An unordered release returns the block at once.  A stream-ordered one returns it once the
   // work queued on `stream` up to now has completed (an event is recorded and polled on later
   // allocations); inside the thread's open ReleaseGroup of that stream it waits for the group's
@@ -161,13 +193,13 @@ class BlockPool {
     if (n == 0) return;
     if (adopted) {
       std::lock_guard<std::mutex> g(mu_);
-      for (size_t i = 0; i < n; ++i) retire(ps[i], adopted);
+      for (size_t i = 0; i < n; ++i) retire(ps[i], adopted, stream);
       return;
     }
     void* ev = recorded_event(stream);
     std::lock_guard<std::mutex> g(mu_);
     const size_t before = pending_.size();
-    for (size_t i = 0; i < n; ++i) retire(ps[i], ev);
+    for (size_t i = 0; i < n; ++i) retire(ps[i], ev, stream);
     if (!ev) return;
     if (pending_.size() > before) pending_.back().owns_ev = true;   // the last one queued
     else events_.push_back(ev);       // nothing queued: the event goes straight back
@@ -204,9 +236,9 @@ class BlockPool {
   Snapshot snapshot() {
     std::lock_guard<std::mutex> g(mu_);
     Snapshot s{{}, {}, pending_, events_.size(), cached_};
-    for (auto& kv : live_) s.live.push_back({kv.first, kv.second, nullptr, false});
+    for (auto& kv : live_) s.live.push_back({kv.first, kv.second, nullptr, false, nullptr});
     for (auto& kv : free_)
-      for (void* p : kv.second) s.free.push_back({p, kv.first, nullptr, false});
+      for (void* p : kv.second) s.free.push_back({p, kv.first, nullptr, false, nullptr});
     return s;
   }
 
@@ -221,10 +253,10 @@ class BlockPool {
     return p;
   }
   // p leaves live_: behind `ev` into pending_, or with no event straight into its free list
-  void retire(void* p, void* ev) {
+  void retire(void* p, void* ev, void* stream = nullptr) {
     auto it = live_.find(p);
     if (it == live_.end()) return;
-    const Block b{p, it->second, ev, false};
+    const Block b{p, it->second, ev, false, stream};
     live_.erase(it);
     if (ev) pending_.push_back(b);
     else settle(b);
@@ -237,9 +269,38 @@ class BlockPool {
     free_[b.key].push_back(b.p);
     cached_ += b.key.second;
   }
+  // The oldest pending block of (device, class) `key` released behind `stream`, taken while the
+  // work it waits for may still run: the caller's first use is queued on that stream, behind it.
+  // No wait and no query.  The batch's event, where this block owned it, goes to a block still
+  // pending behind it; the last one recycles it.
+  void* take_pending_of(const Key& key, void* stream) {
+    for (size_t i = 0; i < pending_.size(); ++i) {
+      if (pending_[i].key != key || pending_[i].stream != stream) continue;
+      const Block pd = pending_[i];
+      pending_.erase(pending_.begin() + (long)i);
+      if (pd.owns_ev) {
+        size_t heir = pending_.size();
+        for (size_t j = 0; j < pending_.size() && heir == pending_.size(); ++j)
+          if (pending_[j].ev == pd.ev) heir = j;
+        if (heir < pending_.size()) pending_[heir].owns_ev = true;
+        else events_.push_back(pd.ev);
+      }
+      live_[pd.p] = pd.key;
+      return pd.p;
+    }
+    return nullptr;
+  }
+  // Each distinct event is queried once per poll (the blocks of one build share one).
   void poll_pending() {
+    std::vector<std::pair<void*, bool>> seen;
+    const auto done = [&](void* ev) {
+      for (const auto& e : seen)
+        if (e.first == ev) return e.second;
+      seen.emplace_back(ev, dev_.done(ev));
+      return seen.back().second;
+    };
     for (size_t i = 0; i < pending_.size();) {
-      if (dev_.done(pending_[i].ev)) {
+      if (done(pending_[i].ev)) {
         settle(pending_[i]);
         pending_[i] = pending_.back();
         pending_.pop_back();
@@ -303,6 +364,59 @@ struct ReleaseGroupT {
   void adopt(void* ev) { adopted = ev; }
   ReleaseGroupT(const ReleaseGroupT&) = delete;
   ReleaseGroupT& operator=(const ReleaseGroupT&) = delete;
+};
+
+// Records that carry an event each (`Rec::ev`; the engine's pinned build records), and the bound
+// on how far the host runs ahead of the device: a record given back in flight (its build freed
+// before anyone waited for it) is pending until its event has completed, and while `ahead` of
+// them are pending a take waits for the oldest one's event first.  With same-stream block reuse
+// no allocation waits between such builds any more; this wait is the back-pressure.  Pending
+// records are kept oldest first.  `grow(std::vector<Rec>&)` makes more records when none is free.
+template <class Dev, class Rec>
+class RecordPool {
+ public:
+  explicit RecordPool(size_t ahead = PoolKnobs{}.ahead, Dev dev = {})
+      : ahead_(std::max<size_t>(ahead, 1)), dev_(dev) {}
+  RecordPool(const RecordPool&) = delete;
+  RecordPool& operator=(const RecordPool&) = delete;
+  template <class Grow>
+  Rec take(Grow&& grow) {
+    std::unique_lock<std::mutex> g(mu_);
+    for (size_t i = 0; i < pending_.size();) {
+      if (dev_.done(pending_[i].ev)) {
+        free_.push_back(pending_[i]);
+        pending_.erase(pending_.begin() + (long)i);
+      } else {
+        ++i;
+      }
+    }
+    while (pending_.size() >= ahead_) {
+      const Rec r = pending_.front();
+      pending_.erase(pending_.begin());
+      g.unlock();
+      dev_.wait_event(r.ev);
+      g.lock();
+      free_.push_back(r);
+    }
+    if (free_.empty()) grow(free_);
+    const Rec r = free_.back();
+    free_.pop_back();
+    return r;
+  }
+  void give(const Rec& r, bool in_flight) {
+    std::lock_guard<std::mutex> g(mu_);
+    (in_flight ? pending_ : free_).push_back(r);
+  }
+  std::pair<size_t, size_t> sizes() {       // for tests: free, pending
+    std::lock_guard<std::mutex> g(mu_);
+    return {free_.size(), pending_.size()};
+  }
+
+ private:
+  const size_t ahead_;
+  Dev dev_;
+  std::mutex mu_;
+  std::vector<Rec> free_, pending_;
 };
 
 }  // namespace kmhg

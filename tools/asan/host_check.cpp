@@ -77,10 +77,25 @@
 //                                             fail alloc-oom|alloc-error|event|record <n>   the
 //                                                                     next n such calls fail
 //                                             trim | cached
+//                                           and, for same-stream reuse and the run-ahead bound
+//                                           (tests/test_pool_stream_reuse.py):
+//                                             alloc_on <name> <bytes> <stream>   first used on
+//                                                                     <stream> (alloc(bytes, stream))
+//                                             dones                   ret = the backend's event
+//                                                                     queries so far
+//                                             ahead <n>               RecordPool's bound (before
+//                                                                     the first rec_take; default 2)
+//                                             rec_take <name>         ret = <event>:<free>:<pending>
+//                                                                     of the record pool after it
+//                                             rec_give <name> [<stream>]   with a stream: its event
+//                                                                     recorded there, in flight
 //   host_check pool threads <T> <ops>       T threads of <ops> mixed alloc / release / group
 //                                           operations over three classes while another thread
 //                                           completes the events; "ok" if every block is
 //                                           accounted for at the end
+//   host_check pool stream-threads <T> <ops>   the same, each thread asking for its blocks on its
+//                                           own stream (same-stream reuse) and taking records
+//                                           from one RecordPool
 #include <cinttypes>
 #include <condition_variable>
 #include <cstdio>
@@ -443,7 +458,7 @@ struct FakeState {
   std::vector<int> freed;              // ids in the order freed, negated if on another device
   std::vector<char> done{1};           // by event; [0] is not an event
   int next_id = 0;
-  long allocs = 0, frees = 0, creates = 0, records = 0, ewaits = 0, swaits = 0;
+  long allocs = 0, frees = 0, creates = 0, records = 0, ewaits = 0, swaits = 0, dones = 0;
   int fail_oom = 0, fail_error = 0, fail_event = 0, fail_record = 0;
   void complete_all() {
     std::lock_guard<std::mutex> g(mu);
@@ -493,6 +508,7 @@ struct FakeDev {
   }
   bool done(void* ev) {
     std::lock_guard<std::mutex> g(f->mu);
+    ++f->dones;
     return f->done[(uintptr_t)ev] != 0;
   }
   void wait_event(void* ev) {
@@ -511,6 +527,12 @@ struct FakeDev {
 };
 using FakePool = kmhg::BlockPool<FakeDev>;
 using FakeGroup = kmhg::ReleaseGroupT<FakeDev>;
+struct FakeRec { void* ev; };
+using FakeRecords = kmhg::RecordPool<FakeDev, FakeRec>;
+// four records at a time, each with an event of the fake device's
+static void fake_rec_grow(FakeDev d, std::vector<FakeRec>& out) {
+  for (int i = 0; i < 4; ++i) out.push_back(FakeRec{d.event()});
+}
 
 // "ret=<r> allocs= frees= creates= records= ewaits= swaits= cached= idle= dev= live= free= pending=
 // freed=": the backend's call counts, cached(), the idle events, the current device, and every
@@ -563,6 +585,9 @@ static int cmd_block_pool(const char* path) {
   FakePool pool(kn, FakeDev{&f});
   std::map<std::string, void*> names;
   std::vector<std::unique_ptr<FakeGroup>> groups;      // innermost last
+  size_t ahead = kn.ahead;
+  std::unique_ptr<FakeRecords> recs;
+  std::map<std::string, FakeRec> rec_names;
   char unknown = 0;
   const auto stream = [](const std::string& w) { return reinterpret_cast<void*>((uintptr_t)atoi(w.c_str())); };
   for (; at < ops.size(); ++at) {
@@ -581,6 +606,26 @@ static int cmd_block_pool(const char* path) {
         ret = e.st == kmhg::PoolAlloc::oom ? "oom" : "error:" + e.text;
         std::replace(ret.begin(), ret.end(), ' ', '_');
       }
+    } else if (op == "alloc_on" && a.size() == 4) {
+      void* p = pool.alloc((size_t)strtoull(a[2].c_str(), nullptr, 10), stream(a[3]));
+      names[a[1]] = p;
+      std::lock_guard<std::mutex> g(f.mu);
+      ret = std::to_string(f.ids.at(p));
+    } else if (op == "dones") {
+      std::lock_guard<std::mutex> g(f.mu);
+      ret = std::to_string(f.dones);
+    } else if (op == "ahead" && a.size() == 2 && !recs) {
+      ahead = (size_t)atoi(a[1].c_str());
+    } else if (op == "rec_take" && a.size() == 2) {
+      if (!recs) recs = std::make_unique<FakeRecords>(ahead, FakeDev{&f});
+      const FakeRec r = recs->take([&](std::vector<FakeRec>& out) { fake_rec_grow(FakeDev{&f}, out); });
+      rec_names[a[1]] = r;
+      const auto n = recs->sizes();
+      ret = std::to_string((uintptr_t)r.ev) + ":" + std::to_string(n.first) + ":" + std::to_string(n.second);
+    } else if (op == "rec_give" && (a.size() == 2 || a.size() == 3) && recs) {
+      const FakeRec r = rec_names.at(a[1]);
+      if (a.size() == 3 && !FakeDev{&f}.record(r.ev, stream(a[2]))) return 2;
+      recs->give(r, a.size() == 3);
     } else if (op == "release" && (a.size() == 2 || a.size() == 3)) {
       void* p = a[1] == "null" ? nullptr : a[1] == "unknown" ? (void*)&unknown : names.at(a[1]);
       if (a.size() == 3) pool.release(p, stream(a[2]), true);
@@ -619,10 +664,11 @@ static int cmd_block_pool(const char* path) {
   return 0;
 }
 
-static int cmd_block_pool_threads(int T, int nops) {
+static int cmd_block_pool_threads(int T, int nops, bool on_stream) {
   FakeState f;
   f.blocking = true;
   FakePool pool(kmhg::PoolKnobs{}, FakeDev{&f});
+  FakeRecords recs(2, FakeDev{&f});
   std::atomic<bool> stop{false};
   std::atomic<int> bad{0};
   std::thread completer([&] {
@@ -638,7 +684,8 @@ static int cmd_block_pool_threads(int T, int nops) {
       void* const other = reinterpret_cast<void*>((uintptr_t)(T + 1));
       std::vector<char*> held;
       const auto take = [&] {         // a block is this thread's alone: its first byte says so
-        char* p = static_cast<char*>(pool.alloc(classes[splitmix(x) % 3]));
+        const size_t sz = classes[splitmix(x) % 3];
+        char* p = static_cast<char*>(on_stream && splitmix(x) % 4 ? pool.alloc(sz, s) : pool.alloc(sz));
         *p = (char)t;
         held.push_back(p);
       };
@@ -660,6 +707,13 @@ static int cmd_block_pool_threads(int T, int nops) {
           for (int j = 0; j < 3; ++j) give(s, true);
           give(other, true);
           rg.synced = r == 7 && (i & 1);
+          if (on_stream) {            // a build's record: freed unwaited every other time
+            const FakeRec rec =
+                recs.take([&](std::vector<FakeRec>& out) { fake_rec_grow(FakeDev{&f}, out); });
+            const bool in_flight = (i & 2) && FakeDev{&f}.record(rec.ev, s);
+            if (in_flight && !rg.synced) rg.adopt(rec.ev);
+            recs.give(rec, in_flight);
+          }
         }
       }
       while (!held.empty()) give(nullptr, false);
@@ -857,7 +911,9 @@ int main(int argc, char** argv) {
   if (c == "pair-start" && argc == 3) return cmd_pair_start(argv[2]);
   if (c == "pool" && argc == 3) return cmd_block_pool(argv[2]);
   if (c == "pool" && argc == 5 && std::string(argv[2]) == "threads")
-    return cmd_block_pool_threads(atoi(argv[3]), atoi(argv[4]));
+    return cmd_block_pool_threads(atoi(argv[3]), atoi(argv[4]), false);
+  if (c == "pool" && argc == 5 && std::string(argv[2]) == "stream-threads")
+    return cmd_block_pool_threads(atoi(argv[3]), atoi(argv[4]), true);
   if (c == "pool" && argc == 6)
     return cmd_pool(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]) != 0);
   if (c == "read-call" && argc >= 4) return cmd_read_call(argc, argv);
