@@ -124,6 +124,24 @@ int kmhg_index_info(const kmhg_index *idx, kmhg_info *info);
  * on the host from the distinct keys (src/khash.h:230-348 semantics), once per index. */
 int kmhg_set_row_order(kmhg_index *idx, int order);
 int kmhg_get_row_order(const kmhg_index *idx, int *order);
+/* The occurrence cap of later queries on this position index, a setting like the row order.
+ * 0 (the default) is off: every entry behaves and launches exactly as without it.  With
+ * max_occ = n >= 1 a query window whose k-mer occurs at more than n positions of the index yields
+ * no hit, as if those rows had been deleted from seq.kmer.pos's result before anything else looked
+ * at it; a window with exactly n occurrences keeps all of them, and n = 1 keeps unique k-mers
+ * only.  It applies to seq.kmer.pos and seq.kmer.pos.rc (kmhg_query_run*, their range, runs and
+ * part entries, either strand, KMHG_DEVICES included -- a device's copy of the index takes this
+ * index's value on every call), to seq.kmer.segs, seq.kmer.blocks and seq.kmer.chains on both of
+ * their routes, and to seq.kmer.raster.  The hit totals the row-free entries return are the totals
+ * after masking, and the 2^31-row checks apply to what remains.  kmer.pos, kmer.pairs, the entries
+ * that take the caller's rows (kmhg_rows_*) and all counting entries ignore it.  Every query entry
+ * reads the value once, when it is called.  The setting is not part of an exported image (an
+ * imported index starts at 0) and kmhg_index_info does not report it.
+ * Errors: "max.occ must be between 0 and 2^31-1"; "External pointer has incorrect tag" for a
+ * canonical or suffix-hash index; "max.occ needs a position index" for a counts index.  A part of
+ * an owner-computes build is accepted: a key's occurrences all live in its owner's part. */
+int kmhg_set_max_occ(kmhg_index *idx, int64_t max_occ);
+int kmhg_get_max_occ(const kmhg_index *idx, int64_t *max_occ);
 /* The host replay itself: order[r] = index (into keys) of the r-th live khash bucket after
  * kh_put of the n distinct keys in the given order.  Host-only, no device work. */
 int kmhg_khash_order(const uint64_t *keys, int64_t n, uint32_t *order);

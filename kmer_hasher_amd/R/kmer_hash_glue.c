@@ -27,6 +27,7 @@
  *                                  -> named VECSXP[3]: INTSXP 6 x C, INTSXP 4 x B, INTSXP B
  *   sequence_kmer_raster(ptr, seq, k, bins, rc, i_range, j_range) (not in the reference)
  *                                                  -> named VECSXP[6], counts REALSXP n_i x n_j
+ *   kmer_max_occ(ptr, max_occ) (not in the reference)                 -> INTSXP 1: the old value
  *
  * Differences, all deliberate: the finaliser frees the whole payload (the reference leaks the
  * 32-B khash_ptr, src/kmer_hash.c:56-66); a freed pointer is detected instead of dereferenced;
@@ -676,6 +677,27 @@ SEXP kmer_row_order(SEXP ptr_r, SEXP order_r) {
   if (code < 0) error("order should be \"first\" or \"khash\"");
   if (kmhg_set_row_order(idx, code) != KMHG_OK) error("%s", kmhg_last_error());
   return R_NilValue;
+}
+
+/* Not in the reference: the occurrence cap of later queries on a position index (kmer.max.occ;
+ * include/kmhgpu.h, kmhg_set_max_occ).  0 is off; with n >= 1 a query window whose k-mer occurs at
+ * more than n positions of the index yields no hit, in seq.kmer.pos, seq.kmer.pos.rc,
+ * seq.kmer.segs, seq.kmer.blocks, seq.kmer.chains and seq.kmer.raster alike.  Returns the
+ * value read just before the set (a get and a set: not atomic against another thread setting the
+ * same index).  Like the other additions it is exported but not in the table below. */
+SEXP kmer_max_occ(SEXP ptr_r, SEXP max_occ_r) {
+  if (TYPEOF(max_occ_r) != INTSXP || length(max_occ_r) != 1 ||
+      INTEGER(max_occ_r)[0] == INT_MIN) /* NA_integer_: as.integer of a value beyond 2^31-1 */
+    error("max.occ should be an integer of length 1");
+  kmhg_index *idx = gpu_index_of(ptr_r);
+  int64_t before = 0;
+  if (kmhg_get_max_occ(idx, &before) != KMHG_OK) error("%s", kmhg_last_error());
+  if (kmhg_set_max_occ(idx, (int64_t)INTEGER(max_occ_r)[0]) != KMHG_OK)
+    error("%s", kmhg_last_error());
+  SEXP ret = PROTECT(allocVector(INTSXP, 1));
+  INTEGER(ret)[0] = (int)before;
+  UNPROTECT(1);
+  return ret;
 }
 
 static const R_CallMethodDef gpu_call_methods[] = {

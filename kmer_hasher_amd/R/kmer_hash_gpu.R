@@ -166,6 +166,15 @@ kmer.row.order <- function(ex.ptr, order="khash"){
     invisible(.Call("kmer_row_order", ex.ptr, as.character(order)))
 }
 
+## not in the reference: the repeat filter of later queries on a position index.  0 (default) is
+## off; with max.occ = n a query window whose k-mer occurs at more than n positions of the index
+## gives no hit -- as if those rows were deleted from seq.kmer.pos's result -- in seq.kmer.pos,
+## seq.kmer.pos.rc, seq.kmer.segs, seq.kmer.blocks, seq.kmer.chains and seq.kmer.raster; n = 1
+## keeps unique k-mers only.  kmer.pos and kmer.pairs ignore it.  Returns the previous value.
+kmer.max.occ <- function(ex.ptr, max.occ=0){
+    invisible(.Call("kmer_max_occ", ex.ptr, as.integer(max.occ)))
+}
+
 ## canonical k-mer counts of a FASTA/FASTQ file (plain or gzip) into a suffix_hash_n pointer;
 ## params = c(k, prefix_bits, min_q, thread_n, max_reads, max_mem, source_n, source)
 ## (reference kmer_hash.R:70-73; counted on the GPU, prefix_bits / thread_n / max_mem only

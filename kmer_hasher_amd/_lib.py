@@ -53,6 +53,8 @@ _PROTOS = {
     "kmhg_index_info": (C.c_int, [vp, C.POINTER(Info)]),
     "kmhg_set_row_order": (C.c_int, [vp, C.c_int]),
     "kmhg_get_row_order": (C.c_int, [vp, C.POINTER(C.c_int)]),
+    "kmhg_set_max_occ": (C.c_int, [vp, C.c_int64]),
+    "kmhg_get_max_occ": (C.c_int, [vp, C.POINTER(C.c_int64)]),
     "kmhg_khash_order": (C.c_int, [vp, C.c_int64, vp]),
     "kmhg_positions_size": (C.c_int, [vp, C.c_uint32, i64p, i64p, i64p, i64p]),
     "kmhg_positions_fill": (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp]),

@@ -12,6 +12,7 @@
     count_kmers_fq_sh(fq, params, ptr)     <- count.kmers.fq.sh    (kmer_hash.R:56-59)
     kmer_spec_sh(ptr, max_count)           <- kmer.spec.sh         (kmer_hash.R:89-91)
     set_row_order(ex_ptr, "khash")         kmer.pos rows in the reference's khash order (opt-in)
+    set_max_occ(ex_ptr, n)                 queries drop the windows whose k-mer occurs > n times
 
 Same argument meaning, same validation order and the reference's own error messages (raised as
 ``KmerHashError``, the analogue of R's error()).  Results follow the R wrappers after their
@@ -196,6 +197,34 @@ def set_row_order(ex_ptr, order: str = "first") -> None:
     if code is None:
         raise KmerHashError("order must be 'first' or 'khash'")
     _lib.check(_lib.lib().kmhg_set_row_order(p.handle, code))
+
+
+def set_max_occ(ex_ptr, max_occ=0) -> int:
+    """kmer.max.occ (not in the reference): the occurrence cap of later queries on a position
+    index.  0 is off; with max_occ = n >= 1 a query window whose k-mer occurs at more than n
+    positions of the index yields no hit, in seq_kmer_pos / seq_kmer_pos_rc, seq_kmer_segs,
+    seq_kmer_blocks, seq_kmer_chains and seq_kmer_raster alike (include/kmhgpu.h,
+    kmhg_set_max_occ); kmer_pos, kmer_pairs and the counting entries ignore it.  Returns the
+    value read just before the set (two library calls: with another thread setting the same index
+    at that moment it need not be the value this call replaced)."""
+    p = _extract(ex_ptr)
+    n = _as_int(max_occ, "max.occ must be between 0 and 2^31-1")
+    if not -2**63 <= n < 2**63:
+        raise KmerHashError("max.occ must be between 0 and 2^31-1")
+    before = get_max_occ(ex_ptr)
+    rc = _lib.lib().kmhg_set_max_occ(p.handle, n)
+    if rc == _lib.KMHG_EINVAL:
+        raise KmerHashError(_lib.lib().kmhg_last_error().decode())
+    _lib.check(rc)
+    return before
+
+
+def get_max_occ(ex_ptr) -> int:
+    """The index's occurrence cap (set_max_occ); 0: none."""
+    p = _extract(ex_ptr)
+    n = C.c_int64()
+    _lib.check(_lib.lib().kmhg_get_max_occ(p.handle, C.byref(n)))
+    return n.value
 
 
 def seq_kmer_pos(ex_ptr, seq, k) -> np.ndarray:

@@ -550,6 +550,9 @@ struct kmhg_index {
   DBuf<int32_t> positions;
   Canon canon;
   int row_order = default_row_order();   // kmer.pos k-mer order (KMHG_ORDER_*)
+  // kmhg_set_max_occ: the query entries' occurrence cap, 0 = none.  An entry reads it once
+  // (capped); a replica's own copy is never looked at -- its calls carry the home index's.
+  std::atomic<int64_t> max_occ{0};
   // asynchronous build (kmhg_build_device returns before the kernels finish): the totals land
   // in `rec`; `src` is kept for the overflow fallback until finish_build()
   bool pending = false;
@@ -722,6 +725,9 @@ QueryCall checked(const QueryCall& c) {
 }
 
 void check_query_args(size_t L, int k) { checked(query_call(L, k)); }
+
+// A query entry's call: not refused, and with the index's occurrence cap as it stands now.
+QueryCall capped(const kmhg_index* idx, const QueryCall& c);
 
 // fn(i) for every part i, one host thread per distinct key[i] (the first key's on the caller's);
 // the parts of one key run in order on its thread.  Every part's failure is kept and the first
@@ -1300,6 +1306,19 @@ bool ensure_diag(kmhg_index* idx, hipStream_t s) {
   return true;
 }
 
+QueryCall capped(const kmhg_index* idx, const QueryCall& c) {
+  return checked(c).with_max_occ(idx->max_occ.load(std::memory_order_relaxed));
+}
+
+// The occurrence cap on a probed query's records, before their tile totals are scanned
+// (k_qrec_mask); nothing is launched without a cap.
+void mask_records(const QueryCall& c, uint32_t* qrec, const uint2* qmulti, uint64_t* tile_rows,
+                  hipStream_t s) {
+  if (c.max_occ == 0) return;
+  LAUNCH("k_qrec_mask", s,
+         launch_qrec_mask(qrec, qmulti, c.w1 - c.w0, (uint32_t)c.max_occ, tile_rows, s));
+}
+
 // Windows [c.w0, c.w1) of the query.  Rows come out ordered by window end, so shards of
 // consecutive window ranges concatenate to the unsharded result.
 // c.rc: the reverse strand (kmhg_query_run_rc*).  d_seq is still the FORWARD sequence; only the
@@ -1349,6 +1368,7 @@ kmhg_query* query_device(kmhg_index* idx, const uint8_t* d_seq, const QueryCall&
          launch_query_probe(d_seq, L, kq, idx->table.p, idx->geom, qrec.p, qmulti.p, w0, w1, aligned,
                             tile_row0, s, diag ? idx->diag_view() : DiagIdx{nullptr, nullptr, 0},
                             diag && tags_on() ? idx->ptag.p : nullptr, elist.p + nt, c.rc));
+  mask_records(c, qrec.p, qmulti.p, tile_row0, s);
   LAUNCH("k_scan_tiles_u64", s, launch_scan_u64(tile_row0, nt, total, tiles.p + nt, s));
   if (c.runs) {
     // the rows as diagonal runs, made from the window records (k_qruns_*); rows written only
@@ -2363,7 +2383,9 @@ kmhg_query* query_multi_device(kmhg_index* idx, const char* seq, const QueryCall
     if (ch.end > ch.begin)
       h2d_host(d.p + ch.begin, seq + ch.begin, (size_t)(ch.end - ch.begin), s);
     q->parts[i] = query_device(
-        use, d.p, checked(query_call_range((size_t)L, whole.k, w.begin, w.end)), s);
+        use, d.p,
+        checked(query_call_range((size_t)L, whole.k, w.begin, w.end)).with_max_occ(whole.max_occ),
+        s);
     HIPC(hipStreamSynchronize(s));
   });
   if (bad.code != KMHG_OK) {
@@ -2993,6 +3015,23 @@ int kmhg_set_row_order(kmhg_index* idx, int order) {
   });
 }
 
+int kmhg_set_max_occ(kmhg_index* idx, int64_t max_occ) {
+  return guarded([&] {
+    if (!idx) fail(KMHG_EINVAL, "null index");
+    checked(max_occ_refusal(max_occ));
+    if (idx->canonical || idx->single) fail(KMHG_EINVAL, "External pointer has incorrect tag");
+    if (idx->sources) fail(KMHG_EINVAL, "max.occ needs a position index");
+    idx->max_occ.store(max_occ, std::memory_order_relaxed);
+  });
+}
+
+int kmhg_get_max_occ(const kmhg_index* idx, int64_t* max_occ) {
+  return guarded([&] {
+    if (!idx || !max_occ) fail(KMHG_EINVAL, "null argument");
+    *max_occ = idx->max_occ.load(std::memory_order_relaxed);
+  });
+}
+
 int kmhg_khash_order(const uint64_t* keys, int64_t n, uint32_t* order) {
   return guarded([&] {
     if (n < 0 || (n && (!keys || !order))) fail(KMHG_EINVAL, "null argument");
@@ -3116,7 +3155,7 @@ static void query_host(kmhg_index* idx, const char* seq, size_t L, int k, bool r
   hipStream_t s = lib_stream();
   DBuf<uint8_t> d(L + 16, s);
   L = h2d_cstring(d.p, seq, L, s);
-  *q = query_device(idx, d.p, checked(query_call(L, k)).on_rc(rc), s);
+  *q = query_device(idx, d.p, capped(idx, query_call(L, k)).on_rc(rc), s);
   HIPC(hipStreamSynchronize(s));
   if (n_rows) *n_rows = (*q)->H;
 }
@@ -3126,9 +3165,9 @@ static void query_host(kmhg_index* idx, const char* seq, size_t L, int k, bool r
 static void query_entry(kmhg_index* idx, const void* d_seq, const QueryCall& c, void* stream,
                         kmhg_query** q, int64_t* n_rows, int64_t* n_runs = nullptr) {
   if (!idx || !d_seq || !q) fail(KMHG_EINVAL, "null argument");
-  checked(c);
+  const QueryCall cc = capped(idx, c);
   DeviceGuard g(idx->device);
-  *q = query_device(idx, static_cast<const uint8_t*>(d_seq), c, (hipStream_t)stream);
+  *q = query_device(idx, static_cast<const uint8_t*>(d_seq), cc, (hipStream_t)stream);
   if (n_rows) *n_rows = (*q)->H;
   if (n_runs) *n_runs = (*q)->n_runs;
 }
@@ -3139,7 +3178,7 @@ int kmhg_query_run(kmhg_index* idx, const char* seq, size_t L, int k, kmhg_query
     if (!idx || !seq || !q) fail(KMHG_EINVAL, "null argument");
     const std::vector<int> devs = query_devices();
     if (devs.size() > 1 && idx->sources == 0) {   // position index over several devices
-      *q = query_multi_device(idx, seq, checked(query_call(effective_len(seq, L), k)), devs);
+      *q = query_multi_device(idx, seq, capped(idx, query_call(effective_len(seq, L), k)), devs);
       if (n_rows) *n_rows = (*q)->H;
       return;
     }
@@ -3512,6 +3551,7 @@ void probe_records(kmhg_index* idx, const uint8_t* d_seq, const QueryCall& c, ui
                             aligned, r.tiles.p, s,
                             diag ? idx->diag_view() : DiagIdx{nullptr, nullptr, 0},
                             diag && tags_on() ? idx->ptag.p : nullptr, nullptr, c.rc));
+  mask_records(c, r.qrec.p, r.qmulti.p, r.tiles.p, s);
   LAUNCH("k_scan_tiles_u64", s, launch_scan_u64(r.tiles.p, nt, total, r.tiles.p + nt, s));
 }
 
@@ -3776,7 +3816,7 @@ int kmhg_segments_run_device(kmhg_index* idx, const void* d_seq, size_t L, int k
   return guarded([&] {
     if (!idx || !d_seq) fail(KMHG_EINVAL, "null argument");
     check_segs_args(min_len, out);
-    const QueryCall c = checked(query_call(L, k)).on_rc(rc != 0);
+    const QueryCall c = capped(idx, query_call(L, k)).on_rc(rc != 0);
     DeviceGuard g(idx->device);
     uint64_t H = 0;
     *out = records_segments(idx, static_cast<const uint8_t*>(d_seq), c, min_len,
@@ -3800,7 +3840,7 @@ int kmhg_segments_run(kmhg_index* idx, const char* seq, size_t L, int k, int rc,
     DBuf<uint8_t> d(L + 16, s);
     L = h2d_cstring(d.p, seq, L, s);
     uint64_t H = 0;
-    *out = records_segments(idx, d.p, checked(query_call(L, k)).on_rc(rc != 0), min_len, s, &H);
+    *out = records_segments(idx, d.p, capped(idx, query_call(L, k)).on_rc(rc != 0), min_len, s, &H);
     if (n_segs) *n_segs = (*out)->S;
     if (n_rows) *n_rows = (int64_t)H;
   });
@@ -3886,7 +3926,7 @@ int kmhg_blocks_run_device(kmhg_index* idx, const void* d_seq, size_t L, int k, 
   return guarded([&] {
     if (!idx || !d_seq) fail(KMHG_EINVAL, "null argument");
     check_blocks_args(min_len, max_gap, min_hits, out);
-    const QueryCall c = checked(query_call(L, k)).on_rc(rc != 0);
+    const QueryCall c = capped(idx, query_call(L, k)).on_rc(rc != 0);
     DeviceGuard g(idx->device);
     uint64_t H = 0;
     *out = records_blocks(idx, static_cast<const uint8_t*>(d_seq), c, min_len, max_gap, min_hits,
@@ -3911,7 +3951,7 @@ int kmhg_blocks_run(kmhg_index* idx, const char* seq, size_t L, int k, int rc, i
     DBuf<uint8_t> d(L + 16, s);
     L = h2d_cstring(d.p, seq, L, s);
     uint64_t H = 0;
-    *out = records_blocks(idx, d.p, checked(query_call(L, k)).on_rc(rc != 0), min_len, max_gap,
+    *out = records_blocks(idx, d.p, capped(idx, query_call(L, k)).on_rc(rc != 0), min_len, max_gap,
                           min_hits, s, &H);
     if (n_blocks) *n_blocks = (*out)->B;
     if (n_rows) *n_rows = (int64_t)H;
@@ -4127,7 +4167,7 @@ int kmhg_chains_run_device(kmhg_index* idx, const void* d_seq, size_t L, int k, 
   return guarded([&] {
     if (!idx || !d_seq) fail(KMHG_EINVAL, "null argument");
     check_chains_args(min_len, max_gap, max_dist, max_drift, min_hits, out);
-    const QueryCall c = checked(query_call(L, k)).on_rc(rc != 0);
+    const QueryCall c = capped(idx, query_call(L, k)).on_rc(rc != 0);
     DeviceGuard g(idx->device);
     uint64_t H = 0;
     *out = query_chains(idx, static_cast<const uint8_t*>(d_seq), c, row_free != 0, min_len,
@@ -4154,7 +4194,7 @@ int kmhg_chains_run(kmhg_index* idx, const char* seq, size_t L, int k, int rc, i
     DBuf<uint8_t> d(L + 16, s);
     L = h2d_cstring(d.p, seq, L, s);
     uint64_t H = 0;
-    *out = query_chains(idx, d.p, checked(query_call(L, k)).on_rc(rc != 0), row_free != 0, min_len,
+    *out = query_chains(idx, d.p, capped(idx, query_call(L, k)).on_rc(rc != 0), row_free != 0, min_len,
                         max_gap, max_dist, max_drift, min_hits, s, &H);
     if (n_chains) *n_chains = (*out)->C;
     if (n_blocks) *n_blocks = (*out)->B;
@@ -4318,7 +4358,7 @@ int kmhg_raster_run_device(kmhg_index* idx, const void* d_seq, size_t L, int k, 
   return guarded([&] {
     if (!idx || !d_seq || !frame || !d_out) fail(KMHG_EINVAL, "null argument");
     const RasterFrame f = checked_frame(frame);
-    const QueryCall c = checked(query_call(L, k)).on_rc(rc != 0);
+    const QueryCall c = capped(idx, query_call(L, k)).on_rc(rc != 0);
     DeviceGuard g(idx->device);
     const uint64_t H = raster_device(idx, static_cast<const uint8_t*>(d_seq), c, f,
                                      static_cast<uint32_t*>(d_out), (hipStream_t)stream);
@@ -4340,7 +4380,7 @@ int kmhg_raster_run(kmhg_index* idx, const char* seq, size_t L, int k, int rc,
     DBuf<uint8_t> d(L + 16, s);
     DBuf<uint32_t> m(raster_cells(f), s);
     L = h2d_cstring(d.p, seq, L, s);
-    const uint64_t H = raster_device(idx, d.p, checked(query_call(L, k)).on_rc(rc != 0), f, m.p, s);
+    const uint64_t H = raster_device(idx, d.p, capped(idx, query_call(L, k)).on_rc(rc != 0), f, m.p, s);
     d2h_host(out, m.p, raster_cells(f) * 4, s);
     if (n_rows) *n_rows = (int64_t)H;
   });

@@ -86,6 +86,11 @@ void launch_query_probe(const uint8_t* seq, int64_t L, int kq, const Slot* T, Ge
                         uint64_t* tile_rows,
                         hipStream_t s, DiagIdx X = DiagIdx{nullptr, nullptr, 0},
                         const uint8_t* TG = nullptr, uint32_t* ecount = nullptr, bool rc = false);
+// The occurrence cap (kmhg_set_max_occ, max_occ >= 1) on a probed query's Nw window records,
+// between launch_query_probe and the scan of tile_rows: the records of the windows with more than
+// max_occ hits become 0 and tile_rows[t] the hits tile t keeps (kmhg_querycall.h has the rule)
+void launch_qrec_mask(uint32_t* qrec, const uint2* qmulti, int64_t Nw, uint32_t max_occ,
+                      uint64_t* tile_rows, hipStream_t s);
 // Once per index, before its first diagonal query: `uniq` = the indexed windows (from the N
 // flags: the reference's window rule), then TG[i] = slot_tag of slot i (0 empty), all nslots
 // slots, and the `uniq` bits of every position of a key seen more than once cleared

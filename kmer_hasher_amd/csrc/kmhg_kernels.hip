@@ -17,6 +17,7 @@
 #include "kmhg_common.h"
 #include "kmhg_kernels.h"
 #include "kmhg_parts_read.h"
+#include "kmhg_querycall.h"
 #include "kmhg_device.h"
 
 namespace kmhg {
@@ -722,6 +723,42 @@ k_query_probe(const uint8_t* __restrict__ seq, int64_t L, int kq, const Slot* __
   if (threadIdx.x == 0) tile_rows[tile] = tot;
 }
 
+// Q_mask (kmhg_set_max_occ, launched only for a cap of max_occ >= 1): between the probe and the
+// scan of its tile totals, the windows whose k-mer occurs more than max_occ times in the index
+// lose their hits -- qrec[s] = 0, as if the probe had missed -- and the tile's total becomes what
+// its windows keep.  Only a multi-hit record can exceed a cap, so only those read qmulti; a kept
+// record is not rewritten.  The rule is qrec_kept / qrec_rows of kmhg_querycall.h.  Windows as
+// Q_emit1 takes them (j * BLOCK + t: coalesced 4-B loads), records indexed from the range's
+// first window as the probe wrote them.  Plain loads and stores and the scan's LDS only: the
+// bytes are the same on every run.  Everything behind the probe reads qrec / qmulti / tile_rows
+// and nothing else, so a tile whose multi-hit windows are all masked takes Q_emit1's route.
+static_assert(QREC_MAXOCC_MULTI == QREC_MULTI, "kmhg_querycall.h's record rule is put_qrec's");
+__global__ void __launch_bounds__(BLOCK)
+k_qrec_mask(uint32_t* __restrict__ qrec, const uint2* __restrict__ qmulti, int64_t Nw,
+            uint32_t max_occ, uint64_t* __restrict__ tile_rows) {
+  __shared__ uint64_t sh[8];
+  const uint32_t tile = blockIdx.x;
+  const int64_t tile0 = (int64_t)tile * TILE;
+  uint32_t rec[WPT];
+#pragma unroll
+  for (int j = 0; j < WPT; ++j) {
+    const int64_t e = tile0 + j * BLOCK + threadIdx.x;
+    rec[j] = e < Nw ? qrec[e] : 0u;
+  }
+  uint64_t rows = 0;
+#pragma unroll
+  for (int j = 0; j < WPT; ++j) {
+    const int64_t e = tile0 + j * BLOCK + threadIdx.x;
+    // (rec[j] is 0 beyond Nw: no load, kept, no store)
+    const uint32_t count = rec[j] == QREC_MULTI ? qmulti[e].x : 1u;
+    if (!qrec_kept(rec[j], count, max_occ)) qrec[e] = 0u;
+    rows += qrec_rows(rec[j], count, max_occ);
+  }
+  uint64_t tot;
+  block_excl_scan(rows, sh, tot);
+  if (threadIdx.x == 0) tile_rows[tile] = tot;
+}
+
 // Exclusive scan of n per-tile u64 totals in one workgroup, any n (the fallback beyond
 // SCAN1_MAX: serial loads per thread, a Hillis-Steele pass over 1024 partials).
 __global__ void __launch_bounds__(1024)
@@ -1374,6 +1411,11 @@ void launch_query_probe(const uint8_t* seq, int64_t L, int kq, const Slot* T, Ge
     hipLaunchKernelGGL((k_query_probe<false, false, false, true>), dim3(nt), dim3(BLOCK), 0, s,
                        seq, L, kq, T, g, qrec, qmulti, w0, w1, aligned ? 1 : 0, tile_rows,
                        DiagIdx{nullptr, nullptr, 0}, nullptr, ecount);
+}
+void launch_qrec_mask(uint32_t* qrec, const uint2* qmulti, int64_t Nw, uint32_t max_occ,
+                      uint64_t* tile_rows, hipStream_t s) {
+  hipLaunchKernelGGL(k_qrec_mask, dim3(grid_for(Nw, TILE)), dim3(BLOCK), 0, s, qrec, qmulti, Nw,
+                     max_occ, tile_rows);
 }
 // ---------------------------------------------------------------- owner-routed query merge
 // dist.owner_query: rank r queried every window against its part of an owner-computes build and

@@ -5,10 +5,13 @@
 // code and text), the rules of the launch sequence (query_rows_guess, runs_pay, needs_exact_redo,
 // diag_eligible), the KMHG_DEVICES grammar (parse_device_list), the multi-device split and the
 // chars a window range reads (shard_windows, shard_chars) and the parts' row offsets
-// (part_offsets).  A refusal is a value; nothing here throws on a bad argument or reads the
-// environment.  The engine keeps every HIP call, every lock and the two lookups (the
-// KMHG_DEVICES text and the device count).
-// tools/asan/host_check runs all of it under ASan + UBSan (tests/test_query_host.py).
+// (part_offsets), and the occurrence cap (kmhg_set_max_occ): its argument rule (max_occ_refusal)
+// and the rule of one window record under it (qrec_kept, qrec_rows), which k_qrec_mask of
+// kmhg_kernels.hip evaluates per window -- the rule exists once.  A refusal is a value; nothing
+// here throws on a bad argument or reads the environment.  The engine keeps every HIP call,
+// every lock and the two lookups (the KMHG_DEVICES text and the device count).
+// tools/asan/host_check runs all of it under ASan + UBSan (tests/test_query_host.py), and
+// tools/asan/maxocc_check the occurrence cap's rules (tests/test_maxocc_host.py).
 //
 // KMHG_DEVICES routes kmhg_query_run alone.  kmhg_query_run_rc does not look at it and runs on
 // the index's own device, like every device-pointer entry.
@@ -21,6 +24,7 @@
 #include <vector>
 
 #include "../../include/kmhgpu.h"
+#include "kmhg_common.h"
 
 // (hidden: nothing of this header joins the library's dynamic symbols)
 #pragma GCC visibility push(hidden)
@@ -36,9 +40,11 @@ struct QueryCall {
   bool part = false;           // over a part of an owner-computes build: keeps its tile offsets
   bool runs = false;           // rows as diagonal runs where that is smaller (runs_pay)
   bool rc = false;             // the reverse strand: w0, w1 and the rows' i in rc(seq)'s coordinates
+  int64_t max_occ = 0;         // the index's occurrence cap when the entry was called; 0: none
   QueryCall of_part() const { QueryCall c = *this; c.part = true; return c; }
   QueryCall as_runs() const { QueryCall c = *this; c.runs = true; return c; }
   QueryCall on_rc(bool on = true) const { QueryCall c = *this; c.rc = on; return c; }
+  QueryCall with_max_occ(int64_t n) const { QueryCall c = *this; c.max_occ = n; return c; }
 };
 
 inline QueryCall query_refusal(int code, const char* text) {
@@ -72,6 +78,26 @@ inline QueryCall query_call_range(size_t L, int k, int64_t w_begin, int64_t w_en
   c.w0 = w_begin;
   c.w1 = w_end;
   return c;
+}
+
+// kmhg_set_max_occ's argument: 0 (off) or a cap of 1 .. 2^31-1 occurrences.
+inline QueryCall max_occ_refusal(int64_t n) {
+  if (n < 0 || n > (int64_t)INT32_MAX)
+    return query_refusal(KMHG_EINVAL, "max.occ must be between 0 and 2^31-1");
+  return QueryCall{};
+}
+
+// One window record under a cap of max_occ >= 1 occurrences.  `rec` is the window's qrec word
+// (put_qrec of kmhg_kernels.hip): 0 for no hit, the one hit's position, or QREC_MAXOCC_MULTI,
+// and only then `count` (qmulti's .x, >= 2) is looked at.  A window whose k-mer occurs more than
+// max_occ times in the index is dropped whole; one with exactly max_occ keeps every hit.
+constexpr uint32_t QREC_MAXOCC_MULTI = 0x80000000u;   // QREC_MULTI of kmhg_kernels.hip
+__host__ __device__ constexpr bool qrec_kept(uint32_t rec, uint32_t count, uint32_t max_occ) {
+  return rec != QREC_MAXOCC_MULTI || count <= max_occ;
+}
+// What the window adds to its tile's hit total: 0, 1 or its count.
+__host__ __device__ constexpr uint32_t qrec_rows(uint32_t rec, uint32_t count, uint32_t max_occ) {
+  return rec == 0 ? 0u : rec != QREC_MAXOCC_MULTI ? 1u : count <= max_occ ? count : 0u;
 }
 
 // Rows are written into a guessed capacity before their number is known (no host round trip

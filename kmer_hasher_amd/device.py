@@ -111,6 +111,19 @@ class DeviceIndex:
         _lib.check(_lib.lib().kmhg_index_info(self._h, C.byref(inf)))
         return {f: getattr(inf, f) for f, _ in _lib.Info._fields_}
 
+    def set_max_occ(self, n: int = 0) -> "DeviceIndex":
+        """The occurrence cap of later queries on this position index (kmhg_set_max_occ): 0 is
+        off; with n >= 1 a query window whose k-mer occurs at more than n positions of the index
+        yields no hit, in query*, segments, blocks, chains and raster alike."""
+        _lib.check(_lib.lib().kmhg_set_max_occ(self._h, int(n)))
+        return self
+
+    @property
+    def max_occ(self) -> int:
+        n = C.c_int64()
+        _lib.check(_lib.lib().kmhg_get_max_occ(self._h, C.byref(n)))
+        return n.value
+
     def query(self, seq: torch.Tensor, k: int, stream=None) -> "DeviceQuery":
         _check_seq(seq)
         q = C.c_void_p()
