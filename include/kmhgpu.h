@@ -142,6 +142,45 @@ int kmhg_get_row_order(const kmhg_index *idx, int *order);
  * an owner-computes build is accepted: a key's occurrences all live in its owner's part. */
 int kmhg_set_max_occ(kmhg_index *idx, int64_t max_occ);
 int kmhg_get_max_occ(const kmhg_index *idx, int64_t *max_occ);
+
+/* make.kmer.hash.min (not in the reference): a position index of the (w,k)-minimizer windows of
+ * the sequence alone, about 2 / (w + 1) of them on random input.  With Nw = L - k + 1 window
+ * starts, h(s) the 64-bit mix of window s's k-mer code that the build takes its bucket from (a
+ * bijection: equal h, equal k-mer) and a span any w consecutive window starts inside [1, Nw] that
+ * the unsampled build would all index, window s is selected iff it is the leftmost minimum of h in
+ * some span that contains it.  Windows in no span (fewer than w indexable windows in a row) are
+ * never selected; w = 1 selects every indexable window and takes kmhg_build's own path, kernel
+ * for kernel.  The index records its w (kmhg_get_sampling: 1 for every index of the other
+ * entries, counts and suffix-hash indexes included).  kmer.pos and kmer.pairs read it like any
+ * index and see only the selected positions.  A seq.kmer.pos-family query at the index's own k
+ * applies the same rule to the QUERY sequence (for the rc entries to rc(seq), in rc coordinates,
+ * N staying N) and returns exactly the rows (i, j) of the unsampled query with i selected in the
+ * query and j selected in the indexed sequence, in the unsampled order; segments, blocks, chains
+ * and the raster derive from those rows.  kmhg_set_max_occ applies on top (the intersection; a
+ * k-mer's occurrences are counted in the sampled index, which holds its selected positions only).
+ * The range entries (*_range, *_range_runs, forward and rc) select over the whole sequence of L
+ * chars they are given and mask only the windows [w_begin, w_end): they read up to w - 1 windows
+ * beyond the range on both sides.  A query at another k behaves as on an unsampled index.  Such
+ * an index never takes the diagonal shortcut of the probe.
+ * Errors: "w must be between 1 and 256"; "a sampled index needs k <= 31"; kmhg_build's own;
+ * "a sampled index needs the partitioned build" where the global-atomic build is forced, and
+ * KMHG_EOVERFLOW if a bucket overflowed (the fallback build does not sample);
+ * "a sampled index is queried on its own device" for a KMHG_DEVICES query;
+ * "index images do not carry a sampling" for kmhg_image_export.  kmhg_build_device_part has no
+ * sampled form.  The device entry waits once on `stream` (the number selected sizes the table)
+ * and is asynchronous after that, like kmhg_build_device. */
+int kmhg_build_sampled(const char *seq, size_t L, int k, int w, int do_sort, kmhg_index **out);
+int kmhg_build_sampled_device(const void *d_seq, size_t L, int k, int w, int do_sort,
+                              void *stream, kmhg_index **out);
+int kmhg_get_sampling(const kmhg_index *idx, int *w);
+/* The selection itself.  Device: bit (s - 1) % 32 of d_mask_words[(s - 1) / 32] = window start s
+ * of the strand (rc != 0: of rc(seq)) is selected; ceil(Nw / 32) words, every one written, bits
+ * past Nw zero; *n_selected = their number.  Waits for `stream`.  Host (CPU only, the same rule
+ * from the same header): mask[s - 1] = 0 / 1, Nw bytes.  Errors: the sampling entries' and
+ * seq.kmer.pos's argument rules. */
+int kmhg_minimizer_mask_device(const void *d_seq, size_t L, int k, int w, int rc,
+                               uint32_t *d_mask_words, void *stream, int64_t *n_selected);
+int kmhg_minimizer_mask(const char *seq, size_t L, int k, int w, int rc, uint8_t *mask);
 /* The host replay itself: order[r] = index (into keys) of the r-th live khash bucket after
  * kh_put of the n distinct keys in the given order.  Host-only, no device work. */
 int kmhg_khash_order(const uint64_t *keys, int64_t n, uint32_t *order);

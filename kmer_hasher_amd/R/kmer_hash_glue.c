@@ -28,6 +28,7 @@
  *   sequence_kmer_raster(ptr, seq, k, bins, rc, i_range, j_range) (not in the reference)
  *                                                  -> named VECSXP[6], counts REALSXP n_i x n_j
  *   kmer_max_occ(ptr, max_occ) (not in the reference)                 -> INTSXP 1: the old value
+ *   make_kmer_h_index_min(seq, k, w, sort_pos) (not in the reference) -> EXTPTRSXP, as make_kmer_h_index
  *
  * Differences, all deliberate: the finaliser frees the whole payload (the reference leaks the
  * 32-B khash_ptr, src/kmer_hash.c:56-66); a freed pointer is detected instead of dereferenced;
@@ -83,6 +84,35 @@ SEXP make_kmer_h_index(SEXP seq_r, SEXP k_r, SEXP sort_pos_r) {
   SEXP s = STRING_ELT(seq_r, 0);
   kmhg_index *idx = NULL;
   int rc = kmhg_build(CHAR(s), (size_t)length(s), k, do_sort, &idx);
+  if (rc != KMHG_OK) error("%s", kmhg_last_error());
+  SEXP tag = PROTECT(allocVector(STRSXP, 1));
+  SET_STRING_ELT(tag, 0, mkChar(kmer_hash_tag));
+  SEXP ptr = PROTECT(R_MakeExternalPtr(idx, tag, R_NilValue));
+  R_RegisterCFinalizerEx(ptr, finalise_gpu_index, TRUE);
+  UNPROTECT(2);
+  return ptr;
+}
+
+/* make.kmer.hash.min (not in the reference; include/kmhgpu.h, kmhg_build_sampled): the index of
+ * the (w,k)-minimizer windows of the sequence alone.  Exported and found by name, not in the
+ * registration table.  Every refusal of an argument is raised here, before the GPU is touched. */
+SEXP make_kmer_h_index_min(SEXP seq_r, SEXP k_r, SEXP w_r, SEXP sort_pos_r) {
+  if (TYPEOF(seq_r) != STRSXP || length(seq_r) < 1)
+    error("seq_r should be a character vector of length at least one");
+  if (TYPEOF(k_r) != INTSXP || length(k_r) < 1)
+    error("k_r must be an integer vector of length at least one");
+  if (TYPEOF(w_r) != INTSXP || length(w_r) != 1 || INTEGER(w_r)[0] == INT_MIN)
+    error("w should be an integer of length 1");
+  if (TYPEOF(sort_pos_r) != INTSXP || length(sort_pos_r) < 1)
+    error("sort_pos_r must be an integer vector of length at least one");
+  int w = INTEGER(w_r)[0];
+  if (w < 1 || w > 256) error("w must be between 1 and 256");
+  int k = INTEGER(k_r)[0];
+  if (k < 1 || k > 31) error("a sampled index needs k between 1 and 31");
+  SEXP s = STRING_ELT(seq_r, 0);
+  if (length(s) <= k) error("the length of the sequence must be at least k");
+  kmhg_index *idx = NULL;
+  int rc = kmhg_build_sampled(CHAR(s), (size_t)length(s), k, w, asInteger(sort_pos_r), &idx);
   if (rc != KMHG_OK) error("%s", kmhg_last_error());
   SEXP tag = PROTECT(allocVector(STRSXP, 1));
   SET_STRING_ELT(tag, 0, mkChar(kmer_hash_tag));

@@ -12,6 +12,13 @@ make.kmer.hash <- function(seq, k, do.sort=FALSE){
     .Call("make_kmer_h_index", as.character(seq), as.integer(k), as.integer(do.sort))
 }
 
+## Not in the reference: an index of the (w,k)-minimizer windows alone (about 2 / (w + 1) of them
+## on random sequence); w = 1 .. 256.  Queries on it apply the same rule to the query sequence.
+make.kmer.hash.min <- function(seq, k, w, do.sort=FALSE){
+    .Call("make_kmer_h_index_min", as.character(seq), as.integer(k), as.integer(w),
+          as.integer(do.sort))
+}
+
 ## opt.flag bits: 1 k-mer strings, 2 (i, pos) rows, 4 (i, x, y) pair rows, 8 counts
 kmer.pos <- function(ex.ptr, opt.flag){
     res <- .Call("kmer_positions", ex.ptr, as.integer(opt.flag))

@@ -53,6 +53,14 @@ _PROTOS = {
     "kmhg_index_info": (C.c_int, [vp, C.POINTER(Info)]),
     "kmhg_set_row_order": (C.c_int, [vp, C.c_int]),
     "kmhg_get_row_order": (C.c_int, [vp, C.POINTER(C.c_int)]),
+    "kmhg_build_sampled": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                     C.POINTER(vp)]),
+    "kmhg_build_sampled_device": (C.c_int, [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp,
+                                            C.POINTER(vp)]),
+    "kmhg_get_sampling": (C.c_int, [vp, C.POINTER(C.c_int)]),
+    "kmhg_minimizer_mask_device": (C.c_int, [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, vp,
+                                             C.POINTER(C.c_int64)]),
+    "kmhg_minimizer_mask": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int, vp]),
     "kmhg_set_max_occ": (C.c_int, [vp, C.c_int64]),
     "kmhg_get_max_occ": (C.c_int, [vp, C.POINTER(C.c_int64)]),
     "kmhg_khash_order": (C.c_int, [vp, C.c_int64, vp]),

@@ -102,17 +102,52 @@ def _as_int(x, what: str) -> int:
         raise KmerHashError(what) from None
 
 
-def make_kmer_hash(seq, k, do_sort=False) -> ExtPtr:
-    """make.kmer.hash -> .Call("make_kmer_h_index", ...)  (src/kmer_hash.c:506-540)."""
+def make_kmer_hash(seq, k, do_sort=False, w=1) -> ExtPtr:
+    """make.kmer.hash -> .Call("make_kmer_h_index", ...)  (src/kmer_hash.c:506-540).
+
+    w > 1 (make.kmer.hash.min, not in the reference): an index of the (w,k)-minimizer windows
+    alone (kmhg_build_sampled, include/kmhgpu.h); queries on it apply the same rule to the
+    query sequence.  w = 1 calls exactly what it always called."""
     b = _as_seq_bytes(seq, "seq_r should be a character vector of length at least one")
     kk = _as_int(k, "k_r must be an integer vector of length at least one")
     ds = _as_int(do_sort, "sort_pos_r must be an integer vector of length at least one")
+    ww = _as_int(w, "w must be between 1 and 256")
     out = C.c_void_p()
-    rc = _lib.lib().kmhg_build(b, len(b), kk, ds, C.byref(out))
+    if ww == 1:
+        rc = _lib.lib().kmhg_build(b, len(b), kk, ds, C.byref(out))
+    else:
+        rc = _lib.lib().kmhg_build_sampled(b, len(b), kk, ww, ds, C.byref(out))
     if rc == _lib.KMHG_EINVAL:
         raise KmerHashError(_lib.lib().kmhg_last_error().decode())
     _lib.check(rc)
     return ExtPtr(out.value)
+
+
+def get_sampling(ex_ptr) -> int:
+    """The minimizer w an index was built with (kmhg_get_sampling); 1: every window."""
+    if not isinstance(ex_ptr, ExtPtr):
+        raise KmerHashError("ptr_r should be an external pointer")
+    w = C.c_int()
+    _lib.check(_lib.lib().kmhg_get_sampling(ex_ptr.handle, C.byref(w)))
+    return w.value
+
+
+def minimizer_mask(seq, k, w, rc=False) -> np.ndarray:
+    """The (w,k)-minimizer selection of a sequence on the CPU (kmhg_minimizer_mask): a uint8
+    array of L - k + 1 entries, entry s - 1 = 1 iff window start s is selected; rc: of the
+    reverse complement, in its own coordinates."""
+    b = _as_seq_bytes(seq, "seq_r should be a character vector of length at least one")
+    kk = _as_int(k, "k should be an integer of length 1")
+    ww = _as_int(w, "w must be between 1 and 256")
+    n = b.find(b"\0")
+    L = len(b) if n < 0 else n
+    out = np.zeros(max(L - kk + 1, 1), dtype=np.uint8)
+    r = _lib.lib().kmhg_minimizer_mask(b, len(b), kk, ww, 1 if rc else 0,
+                                       out.ctypes.data_as(C.c_void_p))
+    if r == _lib.KMHG_EINVAL:
+        raise KmerHashError(_lib.lib().kmhg_last_error().decode())
+    _lib.check(r)
+    return out[:L - kk + 1]
 
 
 def _extract(ptr) -> ExtPtr:

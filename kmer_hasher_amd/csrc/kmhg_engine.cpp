@@ -35,6 +35,7 @@
 #include "kmhg_pool.h"
 #include "kmhg_reads.h"
 #include "kmhg_querycall.h"
+#include "kmhg_minimizer.h"
 #include "kmhg_segrec.h"
 #include "kmhg_parts_read.h"
 #include "kmhg_fastx.h"
@@ -553,6 +554,9 @@ struct kmhg_index {
   // kmhg_set_max_occ: the query entries' occurrence cap, 0 = none.  An entry reads it once
   // (capped); a replica's own copy is never looked at -- its calls carry the home index's.
   std::atomic<int64_t> max_occ{0};
+  // kmhg_build_sampled*: the (w,k)-minimizer sampling the index was built with (kmhg_minimizer.h);
+  // 1: every valid window.  A query at the index's own k applies the same rule to its sequence.
+  int sampling = 1;
   // asynchronous build (kmhg_build_device returns before the kernels finish): the totals land
   // in `rec`; `src` is kept for the overflow fallback until finish_build()
   bool pending = false;
@@ -882,6 +886,7 @@ void count_bid_pack(bool) {}
 struct StreamPtrs {
   const uint8_t* d_seq = nullptr;
   const uint64_t* d_keys = nullptr;
+  const uint32_t* d_mask = nullptr;   // a sampled build's selection mask of d_seq (rq.w > 1)
 };
 
 kmhg_index* build_device_v2(const BuildRequest& rq, const StreamPtrs& in, hipStream_t s) {
@@ -953,7 +958,8 @@ kmhg_index* build_device_v2(const BuildRequest& rq, const StreamPtrs& in, hipStr
   uint64_t* status = reinterpret_cast<uint64_t*>(sc + off_status);
   idx->rec = PinnedPool::get().take();                     // V_stats writes the totals here
   if (!co_auto) idx->table.reset(idx->slots(), on);
-  idx->positions.reset(P.no_pos ? 1 : Nw, on);
+  idx->sampling = rq.w;
+  idx->positions.reset(P.no_pos ? 1 : P.sampled ? std::max<int64_t>(1, rq.n_selected) : Nw, on);
   idx->bstats.reset(nb, on);          // kept: a batch index's walk takes its row offsets from it
   // co_auto: HLL rows of the first histogram pass, V_hll's registers + ticket, its pinned record
   DBuf<uint32_t> hll_rows(co_auto ? (size_t)ntiles * (HLL_REGS / 4) : 1, on);
@@ -981,12 +987,17 @@ kmhg_index* build_device_v2(const BuildRequest& rq, const StreamPtrs& in, hipStr
       idx->dcodes.reset(diag_block_words(Nw), on);
       db = idx->diag_block_of();
     }
-    LAUNCH("k_v2_hist0", s,
-           launch_v2_hist0(d_seq, L, k, Nw, g, mk_digit(1, R), hist.p, ntiles, status,
-                           n_status, meta, s, db.code, db.nbit,
-                           bid ? static_cast<uint32_t*>(kptr(-1)) : nullptr,
-                           partc ? kB.p : nullptr, partc ? pB.p : nullptr,
-                           partc ? tcnt.p : nullptr));
+    if (P.sampled)   // the selected windows, compacted per tile as a part's are
+      LAUNCH("k_minimizer_compact", s,
+             launch_minimizer_compact(d_seq, L, k, Nw, in.d_mask, kB.p, pB.p, tcnt.p, ntiles,
+                                      status, n_status, meta, s));
+    else
+      LAUNCH("k_v2_hist0", s,
+             launch_v2_hist0(d_seq, L, k, Nw, g, mk_digit(1, R), hist.p, ntiles, status,
+                             n_status, meta, s, db.code, db.nbit,
+                             bid ? static_cast<uint32_t*>(kptr(-1)) : nullptr,
+                             partc ? kB.p : nullptr, partc ? pB.p : nullptr,
+                             partc ? tcnt.p : nullptr));
     if (partc) {   // tile counts -> tile offsets, the part's window count -> n_valid
       LAUNCH("k_scan_u32", s, launch_scan_u32(tcnt.p, ntiles, status, n_valid, s));
     } else {       // pass 0: over the sequence, or over V_hist0's ids
@@ -1014,10 +1025,12 @@ kmhg_index* build_device_v2(const BuildRequest& rq, const StreamPtrs& in, hipStr
   uint32_t C = ntiles, nst = n_status;
   uint64_t nh = nhist;
   DBuf<uint32_t> hist1;
-  if (rq.n_parts >= 2 && (passes > 1 || partc)) {
-    uint32_t nv = 0;
-    HIPC(hipMemcpyAsync(&nv, n_valid, 4, hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));
+  if ((rq.n_parts >= 2 && (passes > 1 || partc)) || P.sampled) {
+    uint32_t nv = (uint32_t)rq.n_selected;   // a sampled build knows its count already
+    if (!P.sampled) {
+      HIPC(hipMemcpyAsync(&nv, n_valid, 4, hipMemcpyDeviceToHost, s));
+      HIPC(hipStreamSynchronize(s));
+    }
     C = std::max<uint32_t>(1u, (uint32_t)(((uint64_t)nv + PTILE - 1) / PTILE));
     nh = (uint64_t)R * C;
     nst = tiles_for(nh) + 1;
@@ -1238,6 +1251,39 @@ kmhg_index* build_device(const uint8_t* d_seq, int64_t L, int k, hipStream_t s, 
   return build_device_v1(d_seq, L, k, s);
 }
 
+// The selection mask of a strand of d_seq at (k, w) into d_mask (minimizer_mask_words words);
+// returns the number selected (one wait on s: the count sizes what follows).
+int64_t minimizer_mask_device(const uint8_t* d_seq, int64_t L, int k, int w, bool rc,
+                              uint32_t* d_mask, hipStream_t s) {
+  const bool aligned = (reinterpret_cast<uintptr_t>(d_seq) & 15) == 0;
+  DBuf<unsigned long long> total(1, s);
+  HIPC(hipMemsetAsync(total.p, 0, sizeof(unsigned long long), s));
+  LAUNCH("k_minimizer_mask", s,
+         launch_minimizer_mask(d_seq, L, k, w, rc, aligned, d_mask, total.p, s));
+  unsigned long long n = 0;
+  HIPC(hipMemcpyAsync(&n, total.p, sizeof(n), hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  return (int64_t)n;
+}
+
+void check_sampling_args(int k, int64_t w) {
+  if (const char* bad = minimizer_w_refusal(w)) fail(KMHG_EINVAL, bad);
+  if (w > 1 && k > 31) fail(KMHG_EINVAL, "a sampled index needs k <= 31");
+}
+
+// kmhg_build_sampled*: w = 1 is build_device itself; w > 1 selects first (one wait: the count
+// sizes the table), then builds the selected windows with the partitioned build.  The
+// global-atomic build does not sample.
+kmhg_index* build_device_sampled(const uint8_t* d_seq, int64_t L, int k, int w, hipStream_t s) {
+  if (w == 1) return build_device(d_seq, L, k, s);
+  if (build_version() != 2) fail(KMHG_EINVAL, "a sampled index needs the partitioned build");
+  ReleaseGroup rg(s);
+  DBuf<uint32_t> mask((size_t)minimizer_mask_words(L - k + 1), s);
+  const int64_t n_sel = minimizer_mask_device(d_seq, L, k, w, false, mask.p, s);
+  return build_device_v2(BuildRequest::sequence_sampled(L, k, w, n_sel),
+                         StreamPtrs{d_seq, nullptr, mask.p}, s);
+}
+
 // Wait for a pending build and collect its totals.  If a bucket's LDS sub-table overflowed
 // (position builds: never observed -- distinct keys per bucket ~ Binomial with mean <= V2_BW;
 // count-only builds do not come here), the index is rebuilt
@@ -1252,6 +1298,9 @@ void finish_build(kmhg_index* idx) {
   const uint8_t* src = idx->src;
   idx->src = nullptr;
   if (hm.overflow) {
+    if (idx->sampling > 1)
+      fail(KMHG_EOVERFLOW, "a bucket of a sampled build overflowed its LDS table (the global-atomic "
+                           "build does not sample)");
     if (idx->is_part) fail(KMHG_EOVERFLOW, "a bucket of a part build overflowed its LDS table");
     std::unique_ptr<kmhg_index> v1(build_device_v1(src, idx->L, idx->k, idx->stream));
     idx->build_kind = KMHG_BUILD_GLOBAL;
@@ -1307,13 +1356,29 @@ bool ensure_diag(kmhg_index* idx, hipStream_t s) {
 }
 
 QueryCall capped(const kmhg_index* idx, const QueryCall& c) {
-  return checked(c).with_max_occ(idx->max_occ.load(std::memory_order_relaxed));
+  return checked(c)
+      .with_max_occ(idx->max_occ.load(std::memory_order_relaxed))
+      .with_sampling(c.k == idx->k ? idx->sampling : 1);
 }
 
 // The occurrence cap on a probed query's records, before their tile totals are scanned
 // (k_qrec_mask); nothing is launched without a cap.
-void mask_records(const QueryCall& c, uint32_t* qrec, const uint2* qmulti, uint64_t* tile_rows,
-                  hipStream_t s) {
+// A sampled index (c.sampling > 1) first drops the records of the query windows its rule does
+// not select: the rule runs over the whole strand of c.L chars (k_minimizer_mask), the records
+// of windows [c.w0, c.w1) are masked (k_qrec_minmask).  Both are per-window drops: the result is
+// their intersection.
+void mask_records(const QueryCall& c, const uint8_t* d_seq, uint32_t* qrec, const uint2* qmulti,
+                  uint64_t* tile_rows, hipStream_t s) {
+  if (c.sampling > 1) {
+    const bool aligned = (reinterpret_cast<uintptr_t>(d_seq) & 15) == 0;
+    DBuf<uint32_t> mask((size_t)minimizer_mask_words(c.L - c.k + 1), s);
+    DBuf<unsigned long long> total(1, s);
+    HIPC(hipMemsetAsync(total.p, 0, sizeof(unsigned long long), s));
+    LAUNCH("k_minimizer_mask", s,
+           launch_minimizer_mask(d_seq, c.L, c.k, c.sampling, c.rc, aligned, mask.p, total.p, s));
+    LAUNCH("k_qrec_minmask", s,
+           launch_qrec_minmask(qrec, qmulti, c.w1 - c.w0, c.w0, mask.p, tile_rows, s));
+  }
   if (c.max_occ == 0) return;
   LAUNCH("k_qrec_mask", s,
          launch_qrec_mask(qrec, qmulti, c.w1 - c.w0, (uint32_t)c.max_occ, tile_rows, s));
@@ -1351,7 +1416,7 @@ kmhg_query* query_device(kmhg_index* idx, const uint8_t* d_seq, const QueryCall&
   // and its tags and repeated-key bits come from its own table, k_query_probe<..., PART>)
   const char* de = test_build_knob("KMHG_QUERY_DIAG");
   const bool diag = diag_eligible(kq, idx->k, idx->sources, idx->L - idx->k + 1, idx->U,
-                                  idx->dcodes.p != nullptr, !(de && de[0] == '0')) &&
+                                  idx->dcodes.p != nullptr, !(de && de[0] == '0'), idx->sampling) &&
                     ensure_diag(idx, s);
 
   DBuf<uint32_t> qrec(Nw, s);         // per window: 0, the one hit's position, or multi
@@ -1368,7 +1433,7 @@ kmhg_query* query_device(kmhg_index* idx, const uint8_t* d_seq, const QueryCall&
          launch_query_probe(d_seq, L, kq, idx->table.p, idx->geom, qrec.p, qmulti.p, w0, w1, aligned,
                             tile_row0, s, diag ? idx->diag_view() : DiagIdx{nullptr, nullptr, 0},
                             diag && tags_on() ? idx->ptag.p : nullptr, elist.p + nt, c.rc));
-  mask_records(c, qrec.p, qmulti.p, tile_row0, s);
+  mask_records(c, d_seq, qrec.p, qmulti.p, tile_row0, s);
   LAUNCH("k_scan_tiles_u64", s, launch_scan_u64(tile_row0, nt, total, tiles.p + nt, s));
   if (c.runs) {
     // the rows as diagonal runs, made from the window records (k_qruns_*); rows written only
@@ -2359,6 +2424,8 @@ kmhg_query* query_multi_device(kmhg_index* idx, const char* seq, const QueryCall
     finish_build(idx);
     if (idx->canonical) fail(KMHG_EINVAL, "External pointer has incorrect tag");
   }
+  // (the slices shard_chars cuts carry no halo of w - 1 windows for the selection rule)
+  if (idx->sampling > 1) fail(KMHG_EINVAL, "a sampled index is queried on its own device");
   const int G = (int)devs.size();
   const int64_t L = whole.L;
   auto q = std::make_unique<kmhg_query>();
@@ -2447,6 +2514,24 @@ void free_index(kmhg_index* idx) {
 
 bool kmhg::ballot_ranks() { return lane_ballot(); }
 
+// make.kmer.hash over a host string, synchronous like make_kmer_h_index: the checks and the copy
+// of both host-string entries, `build` being build_device or its sampled form.
+template <class Build>
+void build_host_string(const char* seq, size_t L, int k, kmhg_index** out, Build&& build) {
+  // small or refused strings: the C length and the checks before anything touches the device
+  if (L < H2D_SCAN_MIN || k < 1 || k > 32 || L >= (size_t)INT32_MAX) {
+    L = effective_len(seq, L);
+    check_build_args(L, k);
+  }
+  hipStream_t s = lib_stream();
+  DBuf<uint8_t> d(L + 16, s);
+  L = h2d_cstring(d.p, seq, L, s);
+  check_build_args(L, k);
+  std::unique_ptr<kmhg_index> idx(build(d.p, (int64_t)L, s));
+  finish_build(idx.get());   // (and d dies here)
+  *out = idx.release();
+}
+
 // ============================================================================ C-ABI
 extern "C" {
 
@@ -2457,18 +2542,9 @@ int kmhg_build(const char* seq, size_t L, int k, int do_sort, kmhg_index** out) 
   (void)do_sort;
   return guarded([&] {
     if (!seq || !out) fail(KMHG_EINVAL, "null argument");
-    // small or refused strings: the C length and the checks before anything touches the device
-    if (L < H2D_SCAN_MIN || k < 1 || k > 32 || L >= (size_t)INT32_MAX) {
-      L = effective_len(seq, L);
-      check_build_args(L, k);
-    }
-    hipStream_t s = lib_stream();
-    DBuf<uint8_t> d(L + 16, s);
-    L = h2d_cstring(d.p, seq, L, s);
-    check_build_args(L, k);
-    std::unique_ptr<kmhg_index> idx(build_device(d.p, (int64_t)L, k, s));
-    finish_build(idx.get());   // synchronous, like make_kmer_h_index (and d dies here)
-    *out = idx.release();
+    build_host_string(seq, L, k, out, [&](const uint8_t* d, int64_t n, hipStream_t s) {
+      return build_device(d, n, k, s);
+    });
   });
 }
 
@@ -2480,6 +2556,57 @@ int kmhg_build_device(const void* d_seq, size_t L, int k, int do_sort, void* str
     check_build_args(L, k);
     hipStream_t s = (hipStream_t)stream;   // caller stream; NULL = HIP null stream
     *out = build_device((const uint8_t*)d_seq, (int64_t)L, k, s);
+  });
+}
+
+int kmhg_build_sampled(const char* seq, size_t L, int k, int w, int do_sort, kmhg_index** out) {
+  (void)do_sort;
+  return guarded([&] {
+    if (!seq || !out) fail(KMHG_EINVAL, "null argument");
+    check_sampling_args(k, w);
+    build_host_string(seq, L, k, out, [&](const uint8_t* d, int64_t n, hipStream_t s) {
+      return build_device_sampled(d, n, k, w, s);
+    });
+  });
+}
+
+int kmhg_build_sampled_device(const void* d_seq, size_t L, int k, int w, int do_sort,
+                              void* stream, kmhg_index** out) {
+  (void)do_sort;
+  return guarded([&] {
+    if (!d_seq || !out) fail(KMHG_EINVAL, "null argument");
+    check_sampling_args(k, w);
+    check_build_args(L, k);
+    *out = build_device_sampled((const uint8_t*)d_seq, (int64_t)L, k, w, (hipStream_t)stream);
+  });
+}
+
+int kmhg_get_sampling(const kmhg_index* idx, int* w) {
+  return guarded([&] {
+    if (!idx || !w) fail(KMHG_EINVAL, "null argument");
+    *w = idx->sampling;
+  });
+}
+
+int kmhg_minimizer_mask_device(const void* d_seq, size_t L, int k, int w, int rc,
+                               uint32_t* d_mask_words, void* stream, int64_t* n_selected) {
+  return guarded([&] {
+    if (!d_seq || !d_mask_words || !n_selected) fail(KMHG_EINVAL, "null argument");
+    check_sampling_args(k, w);
+    check_query_args(L, k);
+    *n_selected = minimizer_mask_device((const uint8_t*)d_seq, (int64_t)L, k, w, rc != 0,
+                                        d_mask_words, (hipStream_t)stream);
+  });
+}
+
+int kmhg_minimizer_mask(const char* seq, size_t L, int k, int w, int rc, uint8_t* mask) {
+  return guarded([&] {
+    if (!seq || !mask) fail(KMHG_EINVAL, "null argument");
+    check_sampling_args(k, w);
+    L = effective_len(seq, L);
+    check_query_args(L, k);
+    if (minimizer_mask_host((const uint8_t*)seq, (int64_t)L, k, w, rc != 0, mask) < 0)
+      fail(KMHG_EINVAL, "w must be between 1 and 256");
   });
 }
 
@@ -3538,7 +3665,7 @@ void probe_records(kmhg_index* idx, const uint8_t* d_seq, const QueryCall& c, ui
   const uint32_t nt = tiles_for(Nw);
   const char* de = test_build_knob("KMHG_QUERY_DIAG");
   const bool diag = diag_eligible(kq, idx->k, idx->sources, idx->L - idx->k + 1, idx->U,
-                                  idx->dcodes.p != nullptr, !(de && de[0] == '0')) &&
+                                  idx->dcodes.p != nullptr, !(de && de[0] == '0'), idx->sampling) &&
                     ensure_diag(idx, s);
   r.qrec.reset(Nw);
   r.qrec.bind(s);
@@ -3551,7 +3678,7 @@ void probe_records(kmhg_index* idx, const uint8_t* d_seq, const QueryCall& c, ui
                             aligned, r.tiles.p, s,
                             diag ? idx->diag_view() : DiagIdx{nullptr, nullptr, 0},
                             diag && tags_on() ? idx->ptag.p : nullptr, nullptr, c.rc));
-  mask_records(c, r.qrec.p, r.qmulti.p, r.tiles.p, s);
+  mask_records(c, d_seq, r.qrec.p, r.qmulti.p, r.tiles.p, s);
   LAUNCH("k_scan_tiles_u64", s, launch_scan_u64(r.tiles.p, nt, total, r.tiles.p + nt, s));
 }
 
@@ -4410,6 +4537,7 @@ int kmhg_image_export(const kmhg_index* cidx, void* d_table, void* d_positions, 
     if (!cidx) fail(KMHG_EINVAL, "null index");
     kmhg_index* idx = const_cast<kmhg_index*>(cidx);
     if (idx->sources) fail(KMHG_EINVAL, "index images hold position indices only");
+    if (idx->sampling > 1) fail(KMHG_EINVAL, "index images do not carry a sampling");
     DeviceGuard g(idx->device);
     finish_build(idx);
     hipStream_t s = (hipStream_t)stream;   // caller stream; NULL = HIP null stream

@@ -91,6 +91,22 @@ void launch_query_probe(const uint8_t* seq, int64_t L, int kq, const Slot* T, Ge
 // max_occ hits become 0 and tile_rows[t] the hits tile t keeps (kmhg_querycall.h has the rule)
 void launch_qrec_mask(uint32_t* qrec, const uint2* qmulti, int64_t Nw, uint32_t max_occ,
                       uint64_t* tile_rows, hipStream_t s);
+// (w,k)-minimizer sampling (kmhg_minimizer.hip; the rule is kmhg_minimizer.h's).
+// The selection mask of a strand of the sequence: bit u & 31 of mask[u >> 5] for 0-based window
+// u, ceil(Nw / 32) words, all of them written; *total (zeroed by the caller) += the number
+// selected.
+void launch_minimizer_mask(const uint8_t* seq, int64_t L, int k, int w, bool rc, bool aligned,
+                           uint32_t* mask, unsigned long long* total, hipStream_t s);
+// The selected windows as V_hist0's part compaction leaves a part's (ckeys / cpos / tcnt of
+// launch_v2_hist0), for launch_part_dense; seq 16-B aligned.  Zeroes scan_status and meta.
+void launch_minimizer_compact(const uint8_t* seq, int64_t L, int k, int64_t Nw,
+                              const uint32_t* mask, uint64_t* ckeys, uint32_t* cpos,
+                              uint32_t* tcnt, uint32_t ntiles, uint64_t* scan_status,
+                              uint32_t n_status, BuildMeta* meta, hipStream_t s);
+// A probed query's Nw records (window w0 + e of the strand `mask` covers), where launch_qrec_mask
+// runs: the records of unselected windows become 0, tile_rows[t] what tile t keeps.
+void launch_qrec_minmask(uint32_t* qrec, const uint2* qmulti, int64_t Nw, int64_t w0,
+                         const uint32_t* mask, uint64_t* tile_rows, hipStream_t s);
 // Once per index, before its first diagonal query: `uniq` = the indexed windows (from the N
 // flags: the reference's window rule), then TG[i] = slot_tag of slot i (0 empty), all nslots
 // slots, and the `uniq` bits of every position of a key seen more than once cleared

@@ -88,6 +88,10 @@ inline const char* fmt_name(StreamFmt f) {
 // the first pass drops them, and the valid count comes from its scan.
 // codes: the build keeps the sequence's code words (the diagonal query path; bucket-id streams).
 // n_parts >= 1: part `part` of an owner-computes build (n_parts = 0: a whole build).
+// w > 1: a minimizer-sampled build (kmhg_minimizer.h) of the n_selected windows the selection
+// pass kept, which reach the radix passes as a part's compacted windows do; the result is a whole
+// index that holds only those, in a table of the unsampled geometry (plan_geometry).  w = 1
+// changes nothing in the plan.
 struct BuildRequest {
   bool from_keys = false;
   int64_t L = 0;
@@ -98,6 +102,8 @@ struct BuildRequest {
   bool skip_empty = false;
   bool codes = false;
   uint32_t part = 0, n_parts = 0;
+  int w = 1;
+  int64_t n_selected = 0;
 
   int64_t windows() const { return from_keys ? n_keys : L - k + 1; }
 
@@ -112,6 +118,12 @@ struct BuildRequest {
     BuildRequest r = sequence(L, k, true);
     r.part = part;
     r.n_parts = n_parts;
+    return r;
+  }
+  static BuildRequest sequence_sampled(int64_t L, int k, int w, int64_t n_selected) {
+    BuildRequest r = sequence(L, k, false);
+    r.w = w;
+    r.n_selected = n_selected;
     return r;
   }
   static BuildRequest key_stream(int k, int64_t n_keys) {
@@ -272,7 +284,8 @@ struct BuildPlan {
   uint64_t seg8 = 0;
   uint32_t nseg8 = 0;
   bool ds_on = false, ds8 = false;   // digit streams, u8 digits
-  bool partc = false;          // a part build compacts its own windows first
+  bool partc = false;          // a part build compacts its own windows first (a sampled build:
+  bool sampled = false;        //   its selected windows, by V_min_compact)
   bool fuse_bounds = true;     // BuildKnobs::fuse_bounds
   bool want_tags = false;      // build-time tags
   uint32_t first_pass = 0;     // the first pass of the launch loop (pass 0 has its own launches
@@ -319,6 +332,12 @@ inline uint32_t radix_for(uint32_t nbk, uint32_t maxr, uint32_t& R) {
 // Buckets, the part's range of them, radix and passes.  False: refused, or an empty part.
 inline bool plan_geometry(BuildPlan& P, const BuildRequest& rq, const BuildKnobs& kn,
                           uint32_t device_round) {
+  // A sampled build keeps the unsampled table's geometry.  The selected windows are those with
+  // the smallest mix64(key), and a key's bucket is that value's high bits (bucket_of): every
+  // window whose hash is small enough is selected, so the first buckets of a sampled table hold
+  // nearly what they hold unsampled, however few windows are selected overall, and the last
+  // ones next to nothing.  With the unsampled bucket count every bucket's keys are a subset of
+  // the unsampled build's, so a sampled build overflows no bucket that build would not.
   const int64_t Nw = P.Nw;
   // group buckets: 1024 windows, one workgroup each.  (Wave buckets of 256 windows were
   // removed in round 4: group buckets halve the radix -- config 2 26.1 vs 24.8 Gbp/s -- and save
@@ -393,7 +412,8 @@ inline bool plan_streams(BuildPlan& P, const BuildRequest& rq, const BuildKnobs&
   // line per window beyond.  Measured (A/B in one run): config 2 (10 M windows, 2.5 MB of code)
   // 30.1 -> 31.1 Gbp/s; config 3 (100 M, 25 MB) 28.5 -> 24.0 (bucket kernel 0.84 -> 2.0 ms).
   // So on up to BID_MAX_WINDOWS; KMHG_BUILD_BID=0 / 1 forces key / bucket-id streams.
-  const bool bid = P.bid = rq.codes && !from_keys && !count_only && bid_streams_for(Nw, kn);
+  const bool bid = P.bid =
+      rq.codes && !from_keys && !count_only && !P.sampled && bid_streams_for(Nw, kn);
   // position builds on key streams carry packed 12-B (key, pos) elements: a tile's digit run is
   // one contiguous write instead of a key piece and a position piece in two arrays
   // (tools/scatter_pattern.hip layout, profiles/r5a_scatter_layout.txt: radix 313 1.09 -> 0.87
@@ -408,7 +428,7 @@ inline bool plan_streams(BuildPlan& P, const BuildRequest& rq, const BuildKnobs&
   P.seg8 = P.sh8 >= 12 && P.sh8 < 64 ? (1ull << P.sh8) : 0;
   P.nseg8 = P.seg8 ? (uint32_t)(((uint64_t)Nw + P.seg8 - 1) / P.seg8) : 0;
   const bool pack8 = P.pack8 =
-      aos && passes == 2 && n_parts < 2 && P.seg8 && P.nseg8 <= 256 && kn.pack8;
+      aos && passes == 2 && n_parts < 2 && !P.sampled && P.seg8 && P.nseg8 <= 256 && kn.pack8;
   // Digit streams (DS): each pass before the last also writes every output element's digit of
   // the next pass (u8 up to radix 256, else u16), and that pass's histogram reads 1-2 B per
   // element instead of the keys -- which also takes away the reason to leave the middle streams
@@ -429,7 +449,7 @@ inline bool plan_streams(BuildPlan& P, const BuildRequest& rq, const BuildKnobs&
   // (profiles/r5y_ab_ds_bid_config2.log).  KMHG_DS_BID=1 (or KMHG_DIGIT_STREAM=1) turns them on.
   constexpr int64_t DS_MIN_WINDOWS = 25'000'000;
   // (a part build's later streams hold ~1/n_parts of the windows)
-  const int64_t ds_windows = n_parts >= 2 ? Nw / n_parts : Nw;
+  const int64_t ds_windows = P.sampled ? rq.n_selected : n_parts >= 2 ? Nw / n_parts : Nw;
   const bool ds_keys = !bid && !from_keys && !count_only && passes >= 2 &&
                        (kn.digit_stream >= 0 ? kn.digit_stream == 1
                                              : !pack8 && R <= 256 && ds_windows >= DS_MIN_WINDOWS);
@@ -458,8 +478,9 @@ inline bool plan_streams(BuildPlan& P, const BuildRequest& rq, const BuildKnobs&
   // parts on (one-GPU rehearsal, tools/part_step.py, per-rank step of 10 Mbp per part: 2 parts
   // 0.397 -> 0.467 ms, 4 parts 0.504 -> 0.495, 8 parts 0.749 -> 0.581).  KMHG_PART_COMPACT=0 / 1
   // forces the first pass over every window / the compaction (tests).
-  P.partc = !from_keys && n_parts >= 2 && !bid && rq.codes &&
-            (kn.part_compact >= 0 ? kn.part_compact == 1 : n_parts >= 4);
+  // (a sampled build always: the selection pass's mask is what compacts)
+  P.partc = P.sampled || (!from_keys && n_parts >= 2 && !bid && rq.codes &&
+                          (kn.part_compact >= 0 ? kn.part_compact == 1 : n_parts >= 4));
   // Build-time tags (round 6): a position build beyond the cache (key
   // streams, Nw > BID_MAX_WINDOWS) writes the diagonal query path's slot tags and repeated-key
   // bits itself, so the first seq.kmer.pos of a new index does not pay V_diag_prep (2.6 ms at
@@ -468,7 +489,8 @@ inline bool plan_streams(BuildPlan& P, const BuildRequest& rq, const BuildKnobs&
   // A part of an owner-computes build does the same for its own slots and keys (the owner-
   // routed query runs the diagonal path on it).  KMHG_BUILD_TAGS=0 / 1 (test build) forces
   // either on key streams.
-  P.want_tags = rq.codes && !bid && !from_keys && !count_only &&
+  // A sampled index never takes the diagonal path (it does not hold every valid window): no tags.
+  P.want_tags = rq.codes && !bid && !from_keys && !count_only && !P.sampled &&
                 (kn.build_tags >= 0 ? kn.build_tags == 1 : Nw > BID_MAX_WINDOWS);
   return ds_keys && kn.ds_pack;
 }
@@ -540,7 +562,12 @@ inline BuildPlan plan_build(const BuildRequest& rq, const BuildKnobs& kn, uint32
     refuse(P, KMHG_EINVAL, "padded key stream outside a count-only build (internal error)");
   } else if (rq.n_parts >= 1 && (rq.from_keys || rq.count_only)) {
     refuse(P, KMHG_EINVAL, "part builds index sequences only");
+  } else if (rq.w > 1 && rq.n_parts >= 1) {
+    refuse(P, KMHG_EINVAL, "part builds index every window (w must be 1)");
+  } else if (rq.w > 1 && (rq.from_keys || rq.count_only)) {
+    refuse(P, KMHG_EINVAL, "sampling selects windows of a sequence (internal error)");
   }
+  P.sampled = rq.w > 1;
   if (P.err != KMHG_OK) return P;
   P.ntiles = (uint32_t)((P.Nw + PTILE - 1) / PTILE);
   if (!plan_geometry(P, rq, kn, device_round)) return P;

@@ -41,10 +41,12 @@ struct QueryCall {
   bool runs = false;           // rows as diagonal runs where that is smaller (runs_pay)
   bool rc = false;             // the reverse strand: w0, w1 and the rows' i in rc(seq)'s coordinates
   int64_t max_occ = 0;         // the index's occurrence cap when the entry was called; 0: none
+  int sampling = 1;            // the index's minimizer w where the query is at the index's k; 1: none
   QueryCall of_part() const { QueryCall c = *this; c.part = true; return c; }
   QueryCall as_runs() const { QueryCall c = *this; c.runs = true; return c; }
   QueryCall on_rc(bool on = true) const { QueryCall c = *this; c.rc = on; return c; }
   QueryCall with_max_occ(int64_t n) const { QueryCall c = *this; c.max_occ = n; return c; }
+  QueryCall with_sampling(int w) const { QueryCall c = *this; c.sampling = w; return c; }
 };
 
 inline QueryCall query_refusal(int code, const char* text) {
@@ -114,9 +116,12 @@ inline bool needs_exact_redo(uint64_t H, uint64_t cap) { return H > cap; }
 
 // The diagonal path (k_query_probe) serves a position index (no sources) queried at its own k
 // that has windows, keys and the build's code words; `knob`: KMHG_QUERY_DIAG is not 0 (test build).
+// Never a sampled index (sampling > 1, kmhg_minimizer.h): the path predicts a hit at the index
+// window after a verified one, which holds only where every valid window is in the index.
 inline bool diag_eligible(int kq, int index_k, uint32_t sources, int64_t index_windows, uint64_t U,
-                          bool has_codes, bool knob) {
-  return knob && kq == index_k && sources == 0 && index_windows > 0 && U > 0 && has_codes;
+                          bool has_codes, bool knob, int sampling = 1) {
+  return knob && kq == index_k && sources == 0 && index_windows > 0 && U > 0 && has_codes &&
+         sampling <= 1;
 }
 
 struct DeviceList {

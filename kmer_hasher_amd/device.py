@@ -30,13 +30,42 @@ class DeviceIndex:
         self._h = C.c_void_p(handle)
 
     @classmethod
-    def build(cls, seq: torch.Tensor, k: int, stream=None) -> "DeviceIndex":
+    def build(cls, seq: torch.Tensor, k: int, stream=None, w: int = 1) -> "DeviceIndex":
+        """w > 1: an index of the (w,k)-minimizer windows alone (kmhg_build_sampled_device);
+        w = 1 calls kmhg_build_device as ever."""
         _check_seq(seq)
         with torch.cuda.device(seq.device):
             out = C.c_void_p()
-            _lib.check(_lib.lib().kmhg_build_device(C.c_void_p(seq.data_ptr()), seq.numel(), k, 0,
-                                                    _stream_ptr(stream), C.byref(out)))
+            if w == 1:
+                _lib.check(_lib.lib().kmhg_build_device(C.c_void_p(seq.data_ptr()), seq.numel(),
+                                                        k, 0, _stream_ptr(stream), C.byref(out)))
+            else:
+                _lib.check(_lib.lib().kmhg_build_sampled_device(
+                    C.c_void_p(seq.data_ptr()), seq.numel(), k, int(w), 0, _stream_ptr(stream),
+                    C.byref(out)))
         return cls(out.value)
+
+    @property
+    def sampling(self) -> int:
+        """The minimizer w the index was built with (kmhg_get_sampling); 1: every window."""
+        w = C.c_int()
+        _lib.check(_lib.lib().kmhg_get_sampling(self._h, C.byref(w)))
+        return w.value
+
+    @staticmethod
+    def minimizer_mask(seq: torch.Tensor, k: int, w: int, rc: bool = False, stream=None):
+        """The (w,k)-minimizer selection of an HBM-resident sequence
+        (kmhg_minimizer_mask_device): (mask words, number selected); bit (s - 1) % 32 of int32
+        word (s - 1) // 32 is window start s, of rc(seq) with rc."""
+        _check_seq(seq)
+        nw = max(seq.numel() - k + 1, 1)
+        words = torch.empty(((nw + 31) // 32,), dtype=torch.int32, device=seq.device)
+        n = C.c_int64()
+        with torch.cuda.device(seq.device):
+            _lib.check(_lib.lib().kmhg_minimizer_mask_device(
+                C.c_void_p(seq.data_ptr()), seq.numel(), k, int(w), 1 if rc else 0,
+                C.c_void_p(words.data_ptr()), _stream_ptr(stream), C.byref(n)))
+        return words, n.value
 
     @classmethod
     def build_part(cls, seq: torch.Tensor, k: int, part: int, n_parts: int,
