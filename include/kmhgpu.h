@@ -737,6 +737,63 @@ int kmhg_sh1_count_reads_device(kmhg_index **sh, const void *d_seq, const void *
  * "Unsuitable value of max_count" (outside 1 .. 2^30). */
 int kmhg_sh1_spectrum(kmhg_index *sh, int max_count, double *counts);
 
+/* reads.kmer.pos / reads.kmer.vote (no reference counterpart): a batch of packed reads queried
+ * against a position index on both strands in one call.
+ *
+ * The reads are packed as kmhg_reads_copy packs them: seq = the n_bases bases of all reads, off =
+ * int64[n_reads + 1] with off[0] = 0, non-decreasing, off[n_reads] = n_bases; read r (1-based) is
+ * seq[off[r - 1], off[r]).  strands: 1 forward, 2 reverse, 3 both.  1 <= k <= 31; k need not be
+ * the index's.
+ *
+ * The result is H rows of four int32 (read, strand, i, j): the rows with read = r and strand = +1
+ * are exactly those of seq.kmer.pos(idx, read_r, k) (kmhg_query_run), the rows with strand = -1
+ * exactly those of seq.kmer.pos.rc(idx, read_r, k) (kmhg_query_run_rc: i in rc(read_r)'s
+ * coordinates), ordered by read, forward before reverse, then (i, j).  Every rule of the single
+ * query -- N, ambiguity codes, lowercase, the dropped end window -- applies to each read as if it
+ * were the whole sequence, and the index's occurrence cap (kmhg_set_max_occ) applies.  A read of at
+ * most k bases has no row; that is no error.  The bytes are the same on every run.
+ *
+ * Refused: k outside 1 .. 31 or strands outside 1 .. 3 (KMHG_EINVAL); a counts index; a
+ * minimizer-sampled index queried at its own k (per-read minimizer selection is a follow-up);
+ * more than 2^31 - 2 bases or 2^31 - 1 reads in one call (KMHG_EOVERFLOW); bases without a read
+ * (n_reads = 0, n_bases > 0: KMHG_EINVAL, before any launch); offsets that break the
+ * rule above (KMHG_EINVAL: the host entries look before anything is copied, the device entry
+ * checks on the device and reads nothing outside d_seq[0, n_bases) and d_off[0 .. n_reads]
+ * whatever d_off holds); kmhg_rquery_fill of more than 2^31 - 1 rows (KMHG_EOVERFLOW).
+ *
+ * kmhg_reads_query_run_device runs on `stream` and waits for it once (the row total sizes the
+ * result); the other two copy the reads up and run on the library's stream. */
+typedef struct kmhg_rquery kmhg_rquery;
+int kmhg_reads_query_run_device(kmhg_index *idx, const void *d_seq, int64_t n_bases,
+                                const int64_t *d_off, int64_t n_reads, int k, int strands,
+                                void *stream, kmhg_rquery **q, int64_t *n_rows);
+int kmhg_reads_query_run_packed(kmhg_index *idx, const uint8_t *seq, int64_t n_bases,
+                                const int64_t *off, int64_t n_reads, int k, int strands,
+                                kmhg_rquery **q, int64_t *n_rows);
+int kmhg_reads_query_run(kmhg_index *idx, const kmhg_reads *r, int k, int strands,
+                         kmhg_rquery **q, int64_t *n_rows);
+int kmhg_rquery_rows_device(kmhg_rquery *q, const int32_t **d_rows, int64_t *n_rows); /* owned by q */
+int kmhg_rquery_copy_device(kmhg_rquery *q, void *d_dst, void *stream);
+int kmhg_rquery_fill(kmhg_rquery *q, int32_t *rows);             /* host, 4 * n_rows int32 */
+int kmhg_rquery_free(kmhg_rquery *q);
+
+/* reads.kmer.vote: one row of six int32 per read, in read order:
+ *   read, strand, pos, hits, second, total
+ * A row (read, strand, i, j) of a query at k votes for pos = j - i + k, the index position at
+ * which base 1 of the read (strand +1) or of rc(read) (strand -1) lies; it may be <= 0.  Its cell
+ * is (strand, bin = floor(pos / band)), floored toward minus infinity, 1 <= band <= 2^30.  The
+ * winning cell has the most votes; ties go to the forward strand, then to the smaller bin.
+ * strand and pos = bin * band name it, hits is its votes, second the most votes among the read's
+ * other cells (0: none), total all of the read's rows.  A read without rows: (r, 0, 0, 0, 0, 0).
+ * The rows may come in any order; the bytes are the same on every run; scratch is O(n_rows).
+ * kmhg_rrows_votes: d_rows = n_rows x 4 int32 and d_votes = n_reads x 6 int32 on the current
+ * device; waits for `stream`.  Refused: band or k out of range, more than 2^31 - 1 rows, a row
+ * whose read is outside 1 .. n_reads or whose strand is not +-1 (KMHG_EINVAL). */
+int kmhg_rrows_votes(const void *d_rows, int64_t n_rows, int64_t n_reads, int k, int64_t band,
+                     void *d_votes, void *stream);
+int kmhg_rquery_votes(kmhg_rquery *q, int64_t band, int32_t *votes);   /* host, 6 * n_reads int32 */
+int kmhg_rquery_votes_device(kmhg_rquery *q, int64_t band, void *d_votes, void *stream);
+
 /* Rows of a counts index or suffix hash: keys[U] and counts[U * sources] in row order. */
 int kmhg_counts_export(kmhg_index *idx, uint64_t *keys, int32_t *counts);
 

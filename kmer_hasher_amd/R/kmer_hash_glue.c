@@ -29,6 +29,8 @@
  *                                                  -> named VECSXP[6], counts REALSXP n_i x n_j
  *   kmer_max_occ(ptr, max_occ) (not in the reference)                 -> INTSXP 1: the old value
  *   make_kmer_h_index_min(seq, k, w, sort_pos) (not in the reference) -> EXTPTRSXP, as make_kmer_h_index
+ *   reads_kmer_positions(ptr, seqs, k, strand) (not in the reference) -> INTSXP 4 x H
+ *   reads_kmer_votes(ptr, seqs, k, band, strand) (not in the reference) -> INTSXP 6 x n
  *
  * Differences, all deliberate: the finaliser frees the whole payload (the reference leaks the
  * 32-B khash_ptr, src/kmer_hash.c:56-66); a freed pointer is detected instead of dereferenced;
@@ -726,6 +728,79 @@ SEXP kmer_max_occ(SEXP ptr_r, SEXP max_occ_r) {
     error("%s", kmhg_last_error());
   SEXP ret = PROTECT(allocVector(INTSXP, 1));
   INTEGER(ret)[0] = (int)before;
+  UNPROTECT(1);
+  return ret;
+}
+
+/* Not in the reference: reads.kmer.pos / reads.kmer.vote (include/kmhgpu.h,
+ * kmhg_reads_query_run_packed, kmhg_rquery_votes): every element of the character vector seqs_r is
+ * one read, queried against the position index on both strands in one device call.  strand: 0 both,
+ * 1 forward, -1 reverse.  reads_kmer_positions returns INTSXP 4 x H of (read, strand, i, j),
+ * reads_kmer_votes INTSXP 6 x n of (read, strand, pos, hits, second, total); the R wrappers
+ * transpose and name them.  Every refusal of an argument is raised here, before the library is
+ * called.  Exported, not in the table below. */
+/* The query a reads_* call holds while it allocates its result: allocMatrix may leave the call by
+ * R's error jump, so the handle is parked here and released by whichever comes first, the call's
+ * own end or the next reads_* call (.Call entries of one session do not run concurrently). */
+static kmhg_rquery *parked_rquery = NULL;
+static void release_parked_rquery(void) {
+  if (parked_rquery) kmhg_rquery_free(parked_rquery);
+  parked_rquery = NULL;
+}
+
+static kmhg_rquery *reads_query_of(SEXP ptr_r, SEXP seqs_r, SEXP k_r, SEXP strand_r, int64_t *h) {
+  release_parked_rquery();
+  if (TYPEOF(seqs_r) != STRSXP) error("seqs should be a character vector");
+  if (TYPEOF(k_r) != INTSXP || length(k_r) != 1) error("k should be an integer of length 1");
+  if (TYPEOF(strand_r) != INTSXP || length(strand_r) != 1)
+    error("strand should be 0 (both), 1 (forward) or -1 (reverse)");
+  int k = INTEGER(k_r)[0], strand = INTEGER(strand_r)[0];
+  if (k < 1 || k > 31) error("k should be between 1 and 31");
+  if (strand != 0 && strand != 1 && strand != -1)
+    error("strand should be 0 (both), 1 (forward) or -1 (reverse)");
+  kmhg_index *idx = gpu_index_of(ptr_r);
+  int n = length(seqs_r);
+  int64_t *off = (int64_t *)R_alloc((size_t)n + 1, sizeof(int64_t));
+  off[0] = 0;
+  for (int r = 0; r < n; ++r) off[r + 1] = off[r] + (int64_t)length(STRING_ELT(seqs_r, r));
+  if (off[n] > (int64_t)INT_MAX - 1) error("more than 2^31-2 bases in one call: split the reads");
+  uint8_t *seq = (uint8_t *)R_alloc((size_t)off[n] + 1, 1);
+  for (int r = 0; r < n; ++r)
+    memcpy(seq + off[r], CHAR(STRING_ELT(seqs_r, r)), (size_t)(off[r + 1] - off[r]));
+  if (kmhg_reads_query_run_packed(idx, seq, off[n], off, (int64_t)n, k,
+                                  strand == 0 ? 3 : strand == 1 ? 1 : 2, &parked_rquery, h) !=
+      KMHG_OK)
+    error("%s", kmhg_last_error());
+  return parked_rquery;
+}
+
+SEXP reads_kmer_positions(SEXP ptr_r, SEXP seqs_r, SEXP k_r, SEXP strand_r) {
+  int64_t h = 0;
+  kmhg_rquery *q = reads_query_of(ptr_r, seqs_r, k_r, strand_r, &h);
+  if (h > INT_MAX) {
+    release_parked_rquery();
+    error("result has more than 2^31-1 columns (R matrix limit)");
+  }
+  SEXP ret = PROTECT(allocMatrix(INTSXP, 4, (int)h));
+  int rc = h ? kmhg_rquery_fill(q, INTEGER(ret)) : KMHG_OK;
+  release_parked_rquery();
+  if (rc != KMHG_OK) error("%s", kmhg_last_error());
+  UNPROTECT(1);
+  return ret;
+}
+
+SEXP reads_kmer_votes(SEXP ptr_r, SEXP seqs_r, SEXP k_r, SEXP band_r, SEXP strand_r) {
+  if (TYPEOF(band_r) != INTSXP || length(band_r) != 1 || INTEGER(band_r)[0] == INT_MIN)
+    error("band should be an integer of length 1");
+  int band = INTEGER(band_r)[0];
+  if (band < 1 || band > (1 << 30)) error("band must be between 1 and 2^30");
+  int64_t h = 0;
+  kmhg_rquery *q = reads_query_of(ptr_r, seqs_r, k_r, strand_r, &h);
+  int n = length(seqs_r);
+  SEXP ret = PROTECT(allocMatrix(INTSXP, 6, n));
+  int rc = n ? kmhg_rquery_votes(q, (int64_t)band, INTEGER(ret)) : KMHG_OK;
+  release_parked_rquery();
+  if (rc != KMHG_OK) error("%s", kmhg_last_error());
   UNPROTECT(1);
   return ret;
 }

@@ -182,6 +182,31 @@ kmer.max.occ <- function(ex.ptr, max.occ=0){
     invisible(.Call("kmer_max_occ", ex.ptr, as.integer(max.occ)))
 }
 
+## not in the reference: every read of a character vector (one read per element) against a
+## position index on both strands in one device call.  Columns read, strand, i, j: read is the
+## element's number, strand +1 or -1; the rows of read r on strand +1 are exactly
+## seq.kmer.pos(ex.ptr, seqs[r], k), those on strand -1 exactly seq.kmer.pos.rc(ex.ptr, seqs[r], k);
+## ordered by read, forward before reverse, then (i, j).  A read of at most k bases has no row.
+## strand: 0 both, 1 forward, -1 reverse.
+reads.kmer.pos <- function(ex.ptr, seqs, k, strand=0){
+    m <- .Call("reads_kmer_positions", ex.ptr, as.character(seqs), as.integer(k), as.integer(strand))
+    rownames(m) <- c("read", "strand", "i", "j")
+    t(m)
+}
+
+## not in the reference: where each read of reads.kmer.pos lies.  A row votes for pos = j - i + k,
+## the index position of base 1 of the read (strand +1) or of its reverse complement (strand -1),
+## possibly <= 0, in the cell (strand, floor(pos / band)).  One row per read: the cell with the
+## most votes (ties: forward, then the smaller bin) as strand and pos = bin * band, its votes
+## (hits), the most votes among the read's other cells (second) and all of the read's rows (total);
+## a read without rows gives zeros.
+reads.kmer.vote <- function(ex.ptr, seqs, k, band=64, strand=0){
+    m <- .Call("reads_kmer_votes", ex.ptr, as.character(seqs), as.integer(k), as.integer(band),
+               as.integer(strand))
+    rownames(m) <- c("read", "strand", "pos", "hits", "second", "total")
+    t(m)
+}
+
 ## canonical k-mer counts of a FASTA/FASTQ file (plain or gzip) into a suffix_hash_n pointer;
 ## params = c(k, prefix_bits, min_q, thread_n, max_reads, max_mem, source_n, source)
 ## (reference kmer_hash.R:70-73; counted on the GPU, prefix_bits / thread_n / max_mem only

@@ -151,6 +151,18 @@ _PROTOS = {
     "kmhg_reads_free": (C.c_int, [vp]),
     "kmhg_sh_count_reads": (C.c_int, [C.POINTER(vp), vp, vp]),
     "kmhg_sh_count_reads_device": (C.c_int, [C.POINTER(vp), vp, vp, vp, vp, C.c_int64, vp, vp]),
+    "kmhg_reads_query_run_device": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int,
+                                              vp, C.POINTER(vp), i64p]),
+    "kmhg_reads_query_run_packed": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int,
+                                              C.POINTER(vp), i64p]),
+    "kmhg_reads_query_run": (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(vp), i64p]),
+    "kmhg_rquery_rows_device": (C.c_int, [vp, C.POINTER(vp), i64p]),
+    "kmhg_rquery_copy_device": (C.c_int, [vp, vp, vp]),
+    "kmhg_rquery_fill": (C.c_int, [vp, vp]),
+    "kmhg_rquery_free": (C.c_int, [vp]),
+    "kmhg_rrows_votes": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, C.c_int64, vp, vp]),
+    "kmhg_rquery_votes": (C.c_int, [vp, C.c_int64, vp]),
+    "kmhg_rquery_votes_device": (C.c_int, [vp, C.c_int64, vp, vp]),
     "kmhg_sh_depth": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_int, vp]),
     "kmhg_sh_depth_device": (C.c_int, [vp, vp, C.c_size_t, C.c_int, vp, vp]),
     "kmhg_sh_spectrum": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp,

@@ -283,6 +283,111 @@ def seq_kmer_pos_rc(ex_ptr, seq, k) -> np.ndarray:
     return _seq_kmer_pos(ex_ptr, seq, k, "kmhg_query_run_rc")
 
 
+_STRANDS = {"both": 3, "forward": 1, "fwd": 1, "+": 1, "reverse": 2, "rev": 2, "-": 2,
+            0: 3, 1: 1, -1: 2}
+
+
+def _reads_query(ex_ptr, reads, k, strand, max_reads):
+    """Runs reads.kmer.pos; returns (library, rquery handle, rows, reads)."""
+    p = _extract(ex_ptr)
+    if isinstance(k, (list, tuple, np.ndarray)) and len(k) != 1:
+        raise KmerHashError("k should be an integer of length 1")
+    kk = _as_int(k, "k should be an integer of length 1")
+    if kk < 1 or kk > 31:
+        raise KmerHashError("k should be between 1 and 31")
+    try:
+        strands = _STRANDS[strand]
+    except (KeyError, TypeError):
+        raise KmerHashError('strand should be "both", "forward" or "reverse"') from None
+    L = _lib.lib()
+    q = C.c_void_p()
+    h = C.c_int64()
+    if isinstance(reads, (str, bytes)):          # a FASTA / FASTQ file, gzipped or not
+        path = reads.encode() if isinstance(reads, str) else reads
+        r = C.c_void_p()
+        _lib.check(L.kmhg_fastx_read(path, int(max_reads), 0, C.byref(r)))
+        try:
+            nr = C.c_int64()
+            _lib.check(L.kmhg_reads_info(r, None, C.byref(nr), None))
+            rc = L.kmhg_reads_query_run(p.handle, r, kk, strands, C.byref(q), C.byref(h))
+        finally:
+            L.kmhg_reads_free(r)
+        n_reads = nr.value
+    else:
+        if not isinstance(reads, (list, tuple)):
+            raise KmerHashError("reads should be a list of sequences or a file name")
+        bs = []
+        for x in reads:
+            if isinstance(x, str):
+                x = x.encode("latin-1")
+            elif not isinstance(x, (bytes, bytearray)):
+                raise KmerHashError("reads should be a list of sequences or a file name")
+            z = x.find(b"\0")                    # a C string ends at its first NUL
+            bs.append(bytes(x) if z < 0 else bytes(x[:z]))
+        n_reads = len(bs)
+        off = np.zeros(n_reads + 1, np.int64)
+        np.cumsum([len(b) for b in bs], out=off[1:])
+        seq = np.frombuffer(b"".join(bs) + b"\0", np.uint8)
+        rc = L.kmhg_reads_query_run_packed(p.handle, seq.ctypes.data, int(off[-1]),
+                                           off.ctypes.data, n_reads, kk, strands, C.byref(q),
+                                           C.byref(h))
+    if rc == _lib.KMHG_EINVAL:
+        raise KmerHashError(L.kmhg_last_error().decode())
+    _lib.check(rc)
+    return L, q, h.value, n_reads
+
+
+def reads_kmer_pos(ex_ptr, reads, k, strand="both", max_reads=INT_MAX) -> np.ndarray:
+    """reads.kmer.pos (not in the reference): every read of a batch against a position index, on
+    both strands, in one device call.
+
+    reads: a list of str or bytes, one read each, or the name of a FASTA / FASTQ file (gzipped or
+    not).  A file is read with kmhg_fastx_read(path, max_reads, 0): with k = 0 that call keeps
+    every non-empty record, so read numbers are the numbers of the file's non-empty records.
+    strand: "both", "forward" or "reverse".
+
+    Returns an (H, 4) int32 matrix with columns (read, strand, i, j): read 1-based, strand +1 or
+    -1; the rows of read r on strand +1 are exactly seq_kmer_pos(ptr, read_r, k), those on strand
+    -1 exactly seq_kmer_pos_rc(ptr, read_r, k) (i in rc(read_r)'s coordinates); ordered by read,
+    forward before reverse, then (i, j).  A read of at most k bases has no row."""
+    L, q, h, _ = _reads_query(ex_ptr, reads, k, strand, max_reads)
+    try:
+        if h > INT_MAX:
+            raise KmerHashError("result has more than 2^31-1 rows (R matrix limit)")
+        rows = np.empty(4 * h, np.int32)
+        if h:
+            _lib.check(L.kmhg_rquery_fill(q, rows.ctypes.data))
+    finally:
+        L.kmhg_rquery_free(q)
+    return rows.reshape(-1, 4)
+
+
+def reads_kmer_vote(ex_ptr, reads, k, band=64, strand="both", max_reads=INT_MAX) -> np.ndarray:
+    """reads.kmer.vote (not in the reference): where each read of reads_kmer_pos(ptr, reads, k,
+    strand) lies.  A row votes for pos = j - i + k, the index position of base 1 of the read
+    (strand +1) or of its reverse complement (strand -1), possibly <= 0, in the cell (strand,
+    floor(pos / band)); 1 <= band <= 2^30.
+
+    Returns an (n_reads, 6) int32 matrix (read, strand, pos, hits, second, total), one row per
+    read in read order: the cell with the most votes (ties: forward, then the smaller bin) as
+    strand and pos = bin * band, its votes, the most votes among the read's other cells, and all
+    of the read's rows; (r, 0, 0, 0, 0, 0) for a read without rows."""
+    bb = _as_int(band, "band should be an integer of length 1")
+    if bb < 1 or bb > 2**30:
+        raise KmerHashError("band must be between 1 and 2^30")
+    L, q, _, n_reads = _reads_query(ex_ptr, reads, k, strand, max_reads)
+    try:
+        votes = np.empty(6 * n_reads, np.int32)
+        if n_reads:
+            rc = L.kmhg_rquery_votes(q, bb, votes.ctypes.data)
+            if rc == _lib.KMHG_EINVAL:
+                raise KmerHashError(L.kmhg_last_error().decode())
+            _lib.check(rc)
+    finally:
+        L.kmhg_rquery_free(q)
+    return votes.reshape(-1, 6)
+
+
 def seq_kmer_segs(ex_ptr, seq, k, min_len=1, rc=False, row_free=False) -> np.ndarray:
     """seq.kmer.segs (not in the reference): the dot plot of seq against the index as maximal
     diagonal segments instead of points.

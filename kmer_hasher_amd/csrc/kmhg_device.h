@@ -544,6 +544,15 @@ __device__ __forceinline__ uint32_t table_find4(const Slot* __restrict__ T, Geom
   }
 }
 
+// A query window's probe result as the emit kernels read it (kmhg_kernels.hip "Q_probe" has the
+// format): written by k_query_probe and by the batched read probe of kmhg_readsq.hip.
+constexpr uint32_t QREC_MULTI = 0x80000000u;
+__device__ __forceinline__ void put_qrec(uint32_t* qrec, uint2* qmulti, int64_t i, uint32_t count,
+                                         uint32_t aux) {
+  qrec[i] = count == 0 ? 0u : (count == 1 ? aux : QREC_MULTI);
+  if (count > 1) qmulti[i] = make_uint2(count, aux - count);
+}
+
 // Slot tags, the diagonal query path's filter for windows that miss (built with the position
 // slots, kmhg_kernels.hip k_pos_slots): one byte per table slot, 0 for an empty slot, else the
 // low byte of the key's hash (the bucket takes the high word, the home bits 16..31), 0 -> 1.

@@ -35,6 +35,8 @@
 #include "kmhg_pool.h"
 #include "kmhg_reads.h"
 #include "kmhg_querycall.h"
+#include "kmhg_readsq.h"
+#include "kmhg_readsq_dev.h"
 #include "kmhg_minimizer.h"
 #include "kmhg_segrec.h"
 #include "kmhg_parts_read.h"
@@ -643,6 +645,17 @@ struct kmhg_query {
   // n_runs diagonal runs {first row, i, j} instead of `rows` (n_runs = -1: it holds rows)
   DBuf<int32_t> runs;
   int64_t n_runs = -1;
+};
+
+// reads.kmer.pos: the (read, strand, i, j) rows of a batch of reads (kmhg_readsq.h), with what a
+// vote over them needs.
+struct kmhg_rquery {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  int64_t H = 0;
+  int64_t n_reads = 0;
+  int k = 0;
+  DBuf<int32_t> rows;            // 4 per row
 };
 
 // seq.kmer.segs: the {i, j, len} segments of some rows (kmhg_rows_segments), complete when the
@@ -3595,6 +3608,236 @@ int kmhg_query_copy_device(kmhg_query* q, void* d_dst, void* stream) {
 
 int kmhg_query_free(kmhg_query* q) {
   return guarded([&] { free_query(q); });
+}
+
+// ---------------------------------------------------------------------------- reads.kmer.pos
+extern "C++" {
+namespace {
+
+ReadsCall checked(const ReadsCall& c) {
+  if (c.code != KMHG_OK) fail(c.code, c.text);
+  return c;
+}
+
+// What a batched read query refuses of the index and of the call, before anything is launched.
+ReadsCall reads_checked(const kmhg_index* idx, int64_t n_bases, int64_t n_reads, int k,
+                        int strands) {
+  if (idx->canonical) fail(KMHG_EINVAL, "External pointer has incorrect tag");
+  if (idx->is_part) fail(KMHG_EINVAL, "a part index must be assembled before it is queried");
+  return checked(reads_call(n_bases, n_reads, k, strands, idx->sources, idx->k, idx->sampling))
+      .with_max_occ(idx->max_occ.load(std::memory_order_relaxed));
+}
+
+// The batch on the index's device (kmhg_readsq.hip): the offsets' check, probe, mask, scan and
+// emit queued on `s`, one wait for the row total and the check's flag, and the rows emitted again
+// into an exact buffer where the guess was short.
+kmhg_rquery* reads_query_device(kmhg_index* idx, const uint8_t* d_seq, const int64_t* d_off,
+                                const ReadsCall& c, hipStream_t s) {
+  ReleaseGroup rg(s);
+  finish_build(idx);
+  auto q = std::make_unique<kmhg_rquery>();
+  q->device = idx->device;
+  q->stream = s;
+  q->n_reads = c.n_reads;
+  q->k = c.k;
+  idx->stream = s;
+  PinnedRec hrec = PinnedPool::get().take();
+  GiveBack give_back{hrec, s};
+  uint64_t* total = &hrec.meta->n_kmers;
+  uint32_t* bad_off = &hrec.meta->n_small;
+  LAUNCH("k_rq_check", s, launch_rq_check(d_off, c.n_reads, c.n_bases, bad_off, s));
+  const int64_t V = rq_virtual(c.n_bases, c.ns);
+  if (V == 0) {
+    HIPC(hipStreamSynchronize(s));
+    if (__atomic_load_n(bad_off, __ATOMIC_ACQUIRE)) fail(KMHG_EINVAL, RQ_OFF_TEXT);
+    return q.release();
+  }
+  const uint32_t nt = tiles_for((uint64_t)V);
+  uint64_t cap = rq_rows_guess(V);
+  q->rows.reset(RQ_ROW_INTS * cap);
+  DBuf<uint32_t> qrec(V, s);
+  DBuf<uint2> qmulti(V, s);
+  DBuf<uint64_t> tiles((size_t)nt + scan_u64_scratch(nt), s);
+  LAUNCH("k_rq_probe", s,
+         launch_rq_probe(d_seq, c.n_bases, d_off, c.n_reads, c.k, c.ns, c.rev_only, idx->table.p,
+                         idx->geom, qrec.p, qmulti.p, tiles.p, s));
+  if (c.max_occ)
+    LAUNCH("k_qrec_mask", s,
+           launch_qrec_mask(qrec.p, qmulti.p, V, (uint32_t)c.max_occ, tiles.p, s));
+  LAUNCH("k_scan_tiles_u64", s, launch_scan_u64(tiles.p, nt, total, tiles.p + nt, s));
+  LAUNCH("k_rq_emit", s,
+         launch_rq_emit(qrec.p, qmulti.p, d_off, c.n_reads, c.n_bases, c.k, c.ns, c.rev_only,
+                        idx->positions.p, tiles.p, q->rows.p, cap, s));
+  HIPC(hipStreamSynchronize(s));
+  if (__atomic_load_n(bad_off, __ATOMIC_ACQUIRE)) fail(KMHG_EINVAL, RQ_OFF_TEXT);
+  const uint64_t H = __atomic_load_n(total, __ATOMIC_ACQUIRE);
+  q->H = (int64_t)H;
+  if (!needs_exact_redo(H, cap)) {
+    rg.synced = true;                              // nothing queued behind the synchronize
+    return q.release();
+  }
+  q->rows.bind(s);
+  q->rows.reset(RQ_ROW_INTS * H);
+  LAUNCH("k_rq_emit", s,
+         launch_rq_emit(qrec.p, qmulti.p, d_off, c.n_reads, c.n_bases, c.k, c.ns, c.rev_only,
+                        idx->positions.p, tiles.p, q->rows.p, H, s));
+  HIPC(hipStreamSynchronize(s));
+  return q.release();
+}
+
+// Host reads: the offsets are looked at before anything is copied.
+void reads_query_host(kmhg_index* idx, const uint8_t* seq, int64_t n_bases, const int64_t* off,
+                      int64_t n_reads, int k, int strands, kmhg_rquery** q, int64_t* n_rows) {
+  if (!idx || !q || !off || (n_bases > 0 && !seq)) fail(KMHG_EINVAL, "null argument");
+  const ReadsCall c = reads_checked(idx, n_bases, n_reads, k, strands);
+  checked(reads_off_refusal(off, n_reads, n_bases));
+  DeviceGuard g(idx->device);
+  hipStream_t s = lib_stream();
+  DBuf<uint8_t> d_seq((size_t)n_bases + 16, s);
+  DBuf<int64_t> d_off((size_t)n_reads + 1, s);
+  h2d_host(d_seq.p, seq, (size_t)n_bases, s);
+  h2d_host(d_off.p, off, ((size_t)n_reads + 1) * sizeof(int64_t), s);
+  *q = reads_query_device(idx, d_seq.p, d_off.p, c, s);
+  if (n_rows) *n_rows = (*q)->H;
+}
+
+// reads.kmer.vote of n_rows rows on the current device into d_votes; waits for `s`.
+void rows_votes_device(const int32_t* d_rows, int64_t n_rows, int64_t n_reads, int k, int64_t band,
+                       int32_t* d_votes, hipStream_t s) {
+  checked(vote_refusal(n_rows, n_reads, k, band));
+  if (!n_reads && n_rows)
+    fail(KMHG_EINVAL, "rows must have a read in 1 .. n_reads and a strand of +1 or -1");
+  if (!n_reads) return;
+  if (!d_votes || (n_rows && !d_rows)) fail(KMHG_EINVAL, "null argument");
+  ReleaseGroup rg(s);
+  const uint64_t n = (uint64_t)n_rows;
+  size_t tb = 0;
+  if (n) HIPC(vote_temp_bytes(n, &tb));
+  DBuf<uint8_t> temp(std::max<size_t>(tb, 16), s);
+  DBuf<uint64_t> keys(3 * n + (size_t)n_reads, s);     // keys, sorted keys, cells; then best
+  DBuf<uint32_t> u32s(n + 1 + 2 * (size_t)n_reads, s); // votes, n_cells; then second, total
+  uint64_t* cells = keys.p + 2 * n;
+  uint64_t* best = keys.p + 3 * n;
+  uint32_t* votes = u32s.p;
+  uint32_t* n_cells = u32s.p + n;
+  uint32_t* second = u32s.p + n + 1;
+  uint32_t* total = second + n_reads;
+  PinnedRec hrec = PinnedPool::get().take();
+  GiveBack give_back{hrec, s};
+  uint32_t* bad = &hrec.meta->n_small;
+  hipError_t err = hipSuccess;
+  LAUNCH("k_votes", s,
+         err = launch_votes(d_rows, n, n_reads, k, band, keys.p, cells, votes, n_cells, temp.p, tb,
+                            best, second, total, d_votes, bad, s));
+  HIPC(err);
+  HIPC(hipStreamSynchronize(s));
+  rg.synced = true;
+  if (__atomic_load_n(bad, __ATOMIC_ACQUIRE))
+    fail(KMHG_EINVAL, "rows must have a read in 1 .. n_reads and a strand of +1 or -1");
+}
+
+}  // namespace
+}  // extern "C++"
+
+int kmhg_reads_query_run_device(kmhg_index* idx, const void* d_seq, int64_t n_bases,
+                                const int64_t* d_off, int64_t n_reads, int k, int strands,
+                                void* stream, kmhg_rquery** q, int64_t* n_rows) {
+  return guarded([&] {
+    if (!idx || !q || !d_off || (n_bases > 0 && !d_seq)) fail(KMHG_EINVAL, "null argument");
+    const ReadsCall c = reads_checked(idx, n_bases, n_reads, k, strands);
+    DeviceGuard g(idx->device);
+    *q = reads_query_device(idx, static_cast<const uint8_t*>(d_seq), d_off, c, (hipStream_t)stream);
+    if (n_rows) *n_rows = (*q)->H;
+  });
+}
+
+int kmhg_reads_query_run_packed(kmhg_index* idx, const uint8_t* seq, int64_t n_bases,
+                                const int64_t* off, int64_t n_reads, int k, int strands,
+                                kmhg_rquery** q, int64_t* n_rows) {
+  return guarded([&] { reads_query_host(idx, seq, n_bases, off, n_reads, k, strands, q, n_rows); });
+}
+
+int kmhg_reads_query_run(kmhg_index* idx, const kmhg_reads* r, int k, int strands, kmhg_rquery** q,
+                         int64_t* n_rows) {
+  return guarded([&] {
+    if (!r) fail(KMHG_EINVAL, "null argument");
+    reads_query_host(idx, r->r.seq.data(), (int64_t)r->r.seq.size(), r->r.off.data(),
+                     (int64_t)r->r.n(), k, strands, q, n_rows);
+  });
+}
+
+int kmhg_rquery_rows_device(kmhg_rquery* q, const int32_t** d_rows, int64_t* n_rows) {
+  return guarded([&] {
+    if (!q || !d_rows) fail(KMHG_EINVAL, "null argument");
+    *d_rows = q->rows.p;
+    if (n_rows) *n_rows = q->H;
+  });
+}
+
+int kmhg_rquery_copy_device(kmhg_rquery* q, void* d_dst, void* stream) {
+  return guarded([&] {
+    if (!q) fail(KMHG_EINVAL, "null query");
+    if (!q->H) return;
+    if (!d_dst) fail(KMHG_EINVAL, "null output");
+    DeviceGuard g(q->device);
+    HIPC(hipMemcpyAsync(d_dst, q->rows.p, rq_rows_bytes((uint64_t)q->H), hipMemcpyDeviceToDevice,
+                        (hipStream_t)stream));
+  });
+}
+
+int kmhg_rquery_fill(kmhg_rquery* q, int32_t* rows) {
+  return guarded([&] {
+    if (!q) fail(KMHG_EINVAL, "null query");
+    checked(rq_fill_refusal(q->H));
+    if (!q->H) return;
+    if (!rows) fail(KMHG_EINVAL, "null output");
+    DeviceGuard g(q->device);
+    hipStream_t s = lib_stream();
+    d2h_host(rows, q->rows.p, rq_rows_bytes((uint64_t)q->H), s);
+    HIPC(hipStreamSynchronize(s));
+  });
+}
+
+int kmhg_rquery_free(kmhg_rquery* q) {
+  return guarded([&] {
+    if (!q) return;
+    DeviceGuard g(q->device);
+    HIPC(hipStreamSynchronize(q->stream));
+    q->rows.ordered = false;               // its stream is idle: straight back to the pool
+    delete q;
+  });
+}
+
+int kmhg_rrows_votes(const void* d_rows, int64_t n_rows, int64_t n_reads, int k, int64_t band,
+                     void* d_votes, void* stream) {
+  return guarded([&] {
+    rows_votes_device(static_cast<const int32_t*>(d_rows), n_rows, n_reads, k, band,
+                      static_cast<int32_t*>(d_votes), (hipStream_t)stream);
+  });
+}
+
+int kmhg_rquery_votes_device(kmhg_rquery* q, int64_t band, void* d_votes, void* stream) {
+  return guarded([&] {
+    if (!q) fail(KMHG_EINVAL, "null query");
+    DeviceGuard g(q->device);
+    rows_votes_device(q->rows.p, q->H, q->n_reads, q->k, band, static_cast<int32_t*>(d_votes),
+                      (hipStream_t)stream);
+  });
+}
+
+int kmhg_rquery_votes(kmhg_rquery* q, int64_t band, int32_t* votes) {
+  return guarded([&] {
+    if (!q) fail(KMHG_EINVAL, "null query");
+    checked(vote_refusal(q->H, q->n_reads, q->k, band));
+    if (!q->n_reads) return;
+    if (!votes) fail(KMHG_EINVAL, "null output");
+    DeviceGuard g(q->device);
+    hipStream_t s = lib_stream();
+    DBuf<int32_t> d((size_t)VOTE_COLS * (size_t)q->n_reads, s);
+    rows_votes_device(q->rows.p, q->H, q->n_reads, q->k, band, d.p, s);
+    d2h_host(votes, d.p, d.bytes(), s);
+    HIPC(hipStreamSynchronize(s));
+  });
 }
 
 // ---------------------------------------------------------------------------- seq.kmer.segs

@@ -369,13 +369,8 @@ void launch_diag_prep(const uint16_t* nbit, int64_t L, int k, uint32_t* uniq, co
 // A window's probe result as Q_emit reads it: qrec[s] = 0 (no hit), the 1-based index position
 // (one hit: a key seen once keeps its position inline, < 2^31), or QREC_MULTI with qmulti[s] =
 // {count, first index into positions} -- 4 B per window written and read back instead of 8 (only
-// windows with several hits, rare outside repeats, touch qmulti).
-constexpr uint32_t QREC_MULTI = 0x80000000u;
-__device__ __forceinline__ void put_qrec(uint32_t* qrec, uint2* qmulti, int64_t i, uint32_t count,
-                                         uint32_t aux) {
-  qrec[i] = count == 0 ? 0u : (count == 1 ? aux : QREC_MULTI);
-  if (count > 1) qmulti[i] = make_uint2(count, aux - count);
-}
+// windows with several hits, rare outside repeats, touch qmulti).  QREC_MULTI and put_qrec are
+// kmhg_device.h's: the batched read probe (kmhg_readsq.hip) writes the same records.
 
 // Q_probe: per query window (query k) probe the table; qrec / qmulti (put_qrec); per-tile row
 // totals go through the look-back so each tile learns its first output row.

@@ -163,6 +163,31 @@ class DeviceIndex:
                                                         C.byref(q), C.byref(h)))
         return DeviceQuery(q.value, h.value, seq.device)
 
+    def query_reads(self, reads, k: int, strands: int = 3, stream=None) -> "DeviceReadsQuery":
+        """reads.kmer.pos on the device (kmhg_reads_query_run_device): every read of a packed
+        batch against this position index, strands 1 forward, 2 reverse, 3 both.  `reads` is a
+        DeviceReads, or a (seq, off) pair of CUDA tensors: seq uint8 with the bases of all reads
+        and nothing else, off int64[n + 1] non-decreasing from 0 to seq.numel() (checked on the
+        device: KMHG_EINVAL).  Rows (read, strand, i, j) as include/kmhgpu.h defines them."""
+        if isinstance(reads, DeviceReads):
+            seq, off, n_bases = reads.seq, reads.off, reads.n_bases
+        else:
+            seq, off = reads
+            n_bases = seq.numel()
+        _check_seq(seq)
+        if not (off.is_cuda and off.dtype == torch.int64 and off.dim() == 1 and
+                off.is_contiguous() and off.numel() >= 1 and off.device == seq.device):
+            raise TypeError("offsets must be a contiguous 1-D torch.int64 CUDA tensor of n + 1 "
+                            "entries on the bases' device")
+        n_reads = off.numel() - 1
+        q = C.c_void_p()
+        h = C.c_int64()
+        with torch.cuda.device(seq.device):
+            _lib.check(_lib.lib().kmhg_reads_query_run_device(
+                self._h, C.c_void_p(seq.data_ptr()), n_bases, C.c_void_p(off.data_ptr()), n_reads,
+                k, strands, _stream_ptr(stream), C.byref(q), C.byref(h)))
+        return DeviceReadsQuery(q.value, h.value, n_reads, k, seq.device)
+
     def query_range(self, seq: torch.Tensor, k: int, w0: int, w1: int, stream=None) -> "DeviceQuery":
         """Windows [w0, w1) of `seq` (the multi-GPU shard unit, see dist.py)."""
         _check_seq(seq)
@@ -848,6 +873,60 @@ class DeviceQuery:
             self.free()
         except Exception:
             pass
+
+
+class DeviceReadsQuery:
+    """The rows of DeviceIndex.query_reads, held by the library until free()."""
+
+    def __init__(self, handle: int, n_rows: int, n_reads: int, k: int, device: torch.device):
+        self._h = C.c_void_p(handle)
+        self.n_rows, self.n_reads, self.k, self.device = n_rows, n_reads, k, device
+
+    def rows(self, stream=None) -> torch.Tensor:
+        """A copy of the (H, 4) int32 rows (read, strand, i, j) on the query's device."""
+        t = torch.empty((self.n_rows, 4), dtype=torch.int32, device=self.device)
+        if self.n_rows:
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().kmhg_rquery_copy_device(self._h, C.c_void_p(t.data_ptr()),
+                                                              _stream_ptr(stream)))
+        return t
+
+    def votes(self, band: int = 64, stream=None) -> torch.Tensor:
+        """reads.kmer.vote of these rows (kmhg_rquery_votes_device): (n_reads, 6) int32
+        (read, strand, pos, hits, second, total) on the query's device."""
+        t = torch.empty((self.n_reads, 6), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().kmhg_rquery_votes_device(self._h, int(band),
+                                                           C.c_void_p(t.data_ptr()),
+                                                           _stream_ptr(stream)))
+        return t
+
+    def free(self):
+        if self._h:
+            _lib.lib().kmhg_rquery_free(self._h)
+            self._h = C.c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def rows_votes(rows: torch.Tensor, n_reads: int, k: int, band: int = 64,
+               stream=None) -> torch.Tensor:
+    """reads.kmer.vote of any (H, 4) int32 CUDA rows (read, strand, i, j) of a query at `k`, in
+    any order (kmhg_rrows_votes): (n_reads, 6) int32 on the rows' device.  A row votes for
+    pos = j - i + k, which is why the query's k is an argument."""
+    if not (rows.is_cuda and rows.dtype == torch.int32 and rows.dim() == 2 and
+            rows.shape[1] == 4 and rows.is_contiguous()):
+        raise TypeError("rows must be a contiguous (H, 4) torch.int32 CUDA tensor")
+    t = torch.empty((int(n_reads), 6), dtype=torch.int32, device=rows.device)
+    with torch.cuda.device(rows.device):
+        _lib.check(_lib.lib().kmhg_rrows_votes(C.c_void_p(rows.data_ptr()), rows.shape[0],
+                                               int(n_reads), int(k), int(band),
+                                               C.c_void_p(t.data_ptr()), _stream_ptr(stream)))
+    return t
 
 
 class _RowsBuffer:
